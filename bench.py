@@ -1,6 +1,23 @@
 """Benchmark: path-table construction (source rows/sec), BASELINE.json metric.
 
 python bench.py --gpus N --steps K --warmup W [--workload c4] [--no-allgather]
+                [--dump-outputs DIR] [--full]
+
+A plain run does only what the headline needs: set-up (graph, engine, variant
+pick), W warm-up steps, K timed steps, the optional --dump-outputs, and the
+JSON line (value, ms_per_step, the roofline of the timed kernel from the
+engine's own event times).  Everything that takes runs of its own -- the
+device-copy bandwidth reference, the D2H rate, the CPU baselines, the host
+fill, the secondary configs and the tie-stress variants -- runs only with
+--full, where the options that select among them (--no-cpu, --secondary, ...)
+apply as before.
+
+--dump-outputs DIR writes what the last timed step left in the table, as a
+caller reads it through shd_pe_get_rows: a fixed, seeded sample of the rank's
+rows (all of them when they fit in 48 MB) as DIR/lat.npy, rel.npy (float64),
+hops.npy, flags.npy (float32), pred.npy (float64), each (rows x T), and the
+sampled table positions as DIR/rows.npy.  Inputs are seeded, so the same
+arguments give the same inputs and the same sample on every run.
 
 A step = one full path-table construction for the workload (all S source
 rows, S = T = attached vertices).  With N ranks (one process per GPU,
@@ -27,10 +44,10 @@ Default workload: C4 (BASELINE.json configs[3], the north_star target:
 attached set) are uploaded before the timed region; rows stay in HBM (the
 D2H to the host path cache is outside `value`).
 
-rank 0 prints ONE JSON line.  cpu_baseline = the oracle (C restatement of
+rank 0 prints ONE JSON line.  cpu_baseline (--full) = the oracle (C restatement of
 igraph 0.7.1 Dijkstra + topology.c fold) on 1 host thread, on a bounded
 sample of the same rows (the reference serialises all Dijkstra runs under
-graphLock, topology.c:1747-1781).  --tie-stress adds the 0.005-quantised
+graphLock, topology.c:1747-1781).  --full --tie-stress adds the 0.005-quantised
 variants (c2q, c4q: SURVEY.md §8d) with their tie-row counts.
 """
 import argparse
@@ -204,6 +221,14 @@ def main():
                          "process starts the N rank processes itself")
     ap.add_argument("--dry-launch", action="store_true",
                     help="launcher self-test: every rank prints its rank env as JSON and exits")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run everything that takes runs of its own: "
+                         "stream bandwidth, D2H rate, CPU baselines, host fill, secondary "
+                         "configs, tie stress (off: the options below that pick among them "
+                         "have no effect)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write the table rows of the last step (a seeded "
+                         "sample of this rank's rows, <= 48 MB) as DIR/<field>.npy")
     ap.add_argument("--secondary", default="c1,c2,c3a,c3b,c5",
                     help="comma list of further configs timed after the headline (rank 0, N=1; "
                          "'' = off): ms_per_step, rows/s and roofline of each")
@@ -238,6 +263,8 @@ def main():
 
     if args.gpus < 1:
         sys.exit("bench.py: --gpus must be >= 1")
+    if args.steps < 1 or args.warmup < 0:
+        sys.exit("bench.py: --steps must be >= 1 and --warmup >= 0")
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -316,6 +343,9 @@ def main():
     barrier_sync()
     elapsed = time.perf_counter() - t0
     st = eng.stats()
+    if args.dump_outputs and rank == 0:
+        # before anything else touches the table: the last timed step's rows
+        dump_outputs(eng, args.dump_outputs)
     rl = roofline_of(st, n, m_arcs, T, count)
     per_rank = None
     if dist is not None:
@@ -345,6 +375,7 @@ def main():
         "n_gpus": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": bool(args.full),
         "ms_per_step": elapsed / args.steps * 1e3,
         "higher_is_better": True,
         "scaling": "strong",
@@ -406,8 +437,10 @@ def main():
         wd.cancel()
         gather_res["fields"] = "lat f64, rel f64, hops i32, flags u8" + (", pred i32" if eng.store_pred else "")
         out["allgather"] = gather_res
+    # ---- --full only from here to the line: runs of their own, never in `value` ----
+    solo_full = args.full and rank == 0 and world == 1
     d2h = None
-    if args.d2h_rows > 0 and count > 0:
+    if args.full and args.d2h_rows > 0 and count > 0:
         # PCIe-inclusive: the shard's rows into host buffers after the timed
         # region, (a) page-locked buffers from shd_pe_host_alloc (DMA lands in
         # place), (b) fresh pageable numpy arrays (pinned staging + threaded
@@ -430,7 +463,7 @@ def main():
                "note": "shd_pe_get_rows after the timed region (not in value): GB/s into "
                        "shd_pe_host_alloc buffers; pageable_GB/s into fresh numpy arrays"}
 
-    if rank == 0 and not args.no_stream:
+    if args.full and rank == 0 and not args.no_stream:
         sbw = eng.stream_bandwidth()     # 16-B streaming copy kernel, same device
         out["roofline"]["stream_GBps"] = sbw
         if bound == "hbm":
@@ -445,21 +478,21 @@ def main():
                 out["roofline"]["traffic_over_algorithmic"] = tb / bytes_per_launch
     if d2h:
         out["d2h"] = d2h
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if solo_full and not args.no_cpu:
         out["cpu_baseline"] = cpu_baseline(top, att, budget_s=args.cpu_budget)
         out["speedup_vs_cpu"] = value / out["cpu_baseline"]["value"]
         if args.cpu_threads > 1:
             allc = cpu_baseline(top, att, budget_s=args.cpu_budget / 2, threads=args.cpu_threads)
             out["cpu_baseline_all_cores"] = allc
             out["speedup_vs_cpu_all_cores"] = value / allc["value"]
-    if rank == 0 and world == 1 and args.host_fill:
+    if solo_full and args.host_fill:
         out["host_fill"] = host_fill(eng, top)
     eng.close()
-    if rank == 0 and world == 1 and args.host_fill:
+    if solo_full and args.host_fill:
         host_fill_image(out["host_fill"], top, att, dbg)
-    if rank == 0 and world == 1 and args.secondary:
+    if solo_full and args.secondary:
         out["secondary"] = [secondary(wl, args.steps, dbg) for wl in args.secondary.split(",") if wl]
-    if rank == 0 and world == 1 and args.tie_stress:
+    if solo_full and args.tie_stress:
         out["tie_stress"] = [tie_stress(wl, args.steps, dbg) for wl in args.tie_stress.split(",") if wl]
     done.set()
     emit_once(out)
@@ -528,6 +561,41 @@ def per_rank_summary(records):
     out["kernel_max_over_mean"] = (out["kernel_ms_per_step"]["max"] /
                                    max(1e-12, out["kernel_ms_per_step"]["mean"]))
     return out
+
+
+DUMP_BUDGET_BYTES = 48 << 20
+DUMP_SEED = 20260101
+
+
+def dump_outputs(eng, dirpath, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: the table as it stands (the last timed step's result),
+    read back the way a caller does (shd_pe_get_rows), into dirpath/<field>.npy.
+    All of this engine's rows if they fit in `budget` bytes as written,
+    otherwise a seeded sample of them (sorted table positions, the same for
+    the same workload and shard on every run and every build).  lat / rel stay
+    float64 (bit for bit); hops and flags are small integers, exact in
+    float32; pred (vertex ids) is written as float64."""
+    T = eng.T
+    start, count = eng.owned
+    if count < 1:
+        return
+    row_bytes = T * (8 + 8 + 4 + 4 + (8 if eng.store_pred else 0))
+    k = int(max(1, min(count, budget // row_bytes)))
+    if k == count:
+        pos = np.arange(start, start + count, dtype=np.int64)
+        rows = eng.get_rows(start, count)
+    else:
+        rng = np.random.default_rng(DUMP_SEED)
+        pos = np.sort(rng.choice(count, size=k, replace=False)).astype(np.int64) + start
+        got = [eng.get_rows(int(p), 1) for p in pos]
+        rows = {f: (np.concatenate([g[f] for g in got]) if got[0][f] is not None else None)
+                for f in got[0]}
+    os.makedirs(dirpath, exist_ok=True)
+    np.save(os.path.join(dirpath, "rows.npy"), pos.astype(np.float64))
+    for f, dt in (("lat", np.float64), ("rel", np.float64), ("hops", np.float32),
+                  ("flags", np.float32), ("pred", np.float64)):
+        if rows.get(f) is not None:
+            np.save(os.path.join(dirpath, f + ".npy"), rows[f].astype(dt, copy=False))
 
 
 def secondary(workload, steps, dbg):

@@ -63,6 +63,16 @@ def test_library_stdout_chatter_goes_to_stderr():
     assert "[Gloo]" in r.stderr
 
 
+def test_full_and_dump_outputs_options_exist(tmp_path):
+    """--full and --dump-outputs DIR parse (nothing is written by a dry
+    launch); --steps 0 cannot set a number of timed steps and is refused."""
+    r = _run(["--gpus", "1", "--full", "--dump-outputs", str(tmp_path / "d"), "--dry-launch"])
+    assert r.returncode == 0, r.stderr
+    assert not (tmp_path / "d").exists()
+    r = _run(["--gpus", "1", "--steps", "0", "--dry-launch"])
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
 # ---- N > 1 line shape: per-rank block and the exit status of the assembly ----
 def _import_bench():
     import importlib.util

@@ -537,7 +537,7 @@ def test_native_graphml_to_engine(E, oracle_mod):
     """§8 f4 end to end: shipped GraphML -> shd_graphml_parse -> shd_pe_create
     (complete graph: direct rows), and the same file minus one edge (Dijkstra
     rows), both bit-exact against the oracle."""
-    path = os.path.join(os.path.dirname(__file__), "data", "topology.graphml.xml.xz")
+    path = os.path.join(os.path.dirname(__file__), "golden", "topology.graphml.xml.xz")
     top = E.parse_graphml(path)
     att = np.arange(top.n, dtype=np.int32)
     og = oracle_mod.OracleGraph(top)

@@ -2,7 +2,7 @@
 harness reader (shdpe.graph.read_graphml, igraph's import order) and the
 committed fixtures.  Host-only: no GPU needed.
 
-tests/data/topology.graphml.xml.xz is Shadow's shipped topology
+tests/golden/topology.graphml.xml.xz is Shadow's shipped topology
 (resource/topology.graphml.xml.xz, a data file), the input of
 tests/golden/shipped_topology.npz."""
 import os
@@ -14,7 +14,7 @@ from shdpe import generators as G
 from shdpe.engine import EngineError, parse_graphml
 from shdpe.graph import Topology, read_graphml, write_graphml
 
-DATA = os.path.join(os.path.dirname(__file__), "data")
+DATA = os.path.join(os.path.dirname(__file__), "golden")
 GOLDEN = os.path.join(os.path.dirname(__file__), "golden")
 
 

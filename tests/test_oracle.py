@@ -276,7 +276,7 @@ def test_topology_prefers_direct(oracle_mod):
 
 
 def test_graphml_reader_doc_example():
-    xml = open(os.path.join(os.path.dirname(__file__), "data", "doc_example.graphml")).read()
+    xml = open(os.path.join(os.path.dirname(__file__), "golden", "doc_example.graphml")).read()
     top = read_graphml(xml)
     assert top.n == 1 and top.m == 1 and not top.directed
     assert top.latency[0] == 50.0 and top.loss[0] == 0.001 and top.vloss[0] == 0.0

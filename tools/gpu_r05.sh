@@ -8,7 +8,7 @@
 #             N = $SHARD_NS, once per SHDPE_* setting in $SHARD_ENVS (';' list)
 #   envs      quick bench lines for $WLS per SHDPE_* setting in $ENVS (';' list)
 #   bench     quick bench.py lines for $WLS (no CPU leg / extras)
-#   default   the driver's command (python bench.py, all legs)
+#   default   python bench.py --full (all legs)
 #   trace     rocprofv3 --kernel-trace --stats of quick bench lines for $WLS
 #   pmc       FETCH_SIZE / WRITE_SIZE / TCC hit+miss passes -> traffic_<wl>.json
 #   hostfill  bench's host_fill block alone (C4)
@@ -72,7 +72,7 @@ for st in ${STAGES:-tests bench}; do
       line $OUT/bench_$wl.json $wl
     done ;;
   default)
-    timeout -k 10 600 python3 -u bench.py > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
+    timeout -k 10 600 python3 -u bench.py --full > $OUT/bench_default.json 2> $OUT/bench_default.err || { tail -20 $OUT/bench_default.err; exit 1; }
     line $OUT/bench_default.json "default" ;;
   trace)
     for wl in ${WLS//,/ }; do
@@ -89,7 +89,7 @@ for st in ${STAGES:-tests bench}; do
     done ;;
   hostfill)
     # the host_fill block alone (C4: rows path + fresh-engine fill_rowstore)
-    SHDPE_FILL_LOG=1 timeout -k 10 400 python3 -u bench.py --workload c4 --steps 3 --warmup 1 --no-cpu --tie-stress= --secondary= --d2h-rows 0 --no-stream > $OUT/hostfill.json 2> $OUT/hostfill.err || { tail -20 $OUT/hostfill.err; exit 1; }
+    SHDPE_FILL_LOG=1 timeout -k 10 400 python3 -u bench.py --full --workload c4 --steps 3 --warmup 1 --no-cpu --tie-stress= --secondary= --d2h-rows 0 --no-stream > $OUT/hostfill.json 2> $OUT/hostfill.err || { tail -20 $OUT/hostfill.err; exit 1; }
     python3 -c "import json; h=json.load(open('$OUT/hostfill.json'))['host_fill']; print({k: (round(v, 3) if isinstance(v, float) else v) for k, v in h.items() if k not in ('how', 'rows_path')}); print('rows_path', {k: (round(v, 3) if isinstance(v, float) else v) for k, v in h['rows_path'].items() if k != 'how'})"
     grep "fill_rowstore" $OUT/hostfill.err || true ;;
   exactdbg)
