@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 3
+#define SHD_PE_ABI_VERSION 4
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -290,16 +290,35 @@ int shd_pe_row_checksums(ShdPe* pe, int32_t start, int32_t count, uint64_t* out)
 /* The whole-table path-cache fill in one pass: rows 0..T-1 (computed first
  * if needed -- then the host image is prepared on a host thread while the
  * device computes, so the drop-in's cheapest call is this one alone; a
- * sharded engine must be gathered) into an EMPTY row store, with
- * exactly the result of shd_rowstore_store_rows over every row in position
- * order (isComplete from the graph, no prefersDirectPaths adjacency --
- * topology.c:1805-1864 per row).  The device packs the store's triangular
- * row image (shd_rowstore_image_layout: 17 B per unordered pair instead of
- * 34 B of two rows) and one DMA lands it in page-locked memory the store
- * adopts.  rowResult (optional, T entries): each row's store_row result.
- * msOut (optional, 3 entries): ms of compute (if any) overlapped with the
- * host image preparation, device pack, DMA. */
+ * sharded engine must be gathered: SHD_PE_ENOTOWNED) into an EMPTY row store
+ * (SHD_PE_EINVAL otherwise, as for unknown fillFlags bits).  The store ends
+ * exactly as after this sequence of host calls:
+ *   1. shd_rowstore_store_rows over every row in position order, isComplete
+ *      from the graph (topology.c:1805-1864 per row); with
+ *      SHD_PE_FILL_PREFER_DIRECT its adjacency argument is
+ *      adjacent[p][q] = _topology_verticesAreAdjacent(attached[p],
+ *      attached[q]) (an arc p -> q; p == q: a self-loop), so the Dijkstra
+ *      path of an adjacent pair is refused (:1325-1332), else it is NULL;
+ *   2. with SHD_PE_FILL_DIRECT_PAIRS, for every ordered pair (p, q) in
+ *      position order, p outer, that topology.c:2019-2021 serves with the
+ *      edge itself (complete graph, or PREFER_DIRECT and adjacent) and whose
+ *      edge exists: shd_rowstore_store(isDirect = 1) of the
+ *      _topology_lookupDirectPath values (:1877-1927), refused where either
+ *      direction is cached already.
+ * fillFlags == 0 is shd_pe_fill_rowstore (a complete graph stores nothing).
+ * The device packs the store's triangular row image
+ * (shd_rowstore_image_layout: 17 B per unordered pair instead of 34 B of two
+ * rows) and one DMA lands it in page-locked memory the store adopts; the
+ * prefer-direct pack keeps one row's adjacency as bitmaps in LDS
+ * (SHD_PE_ETOOBIG past 262,144 attached vertices undirected, half that
+ * directed -- tables no device holds).  rowResult (optional, T entries): each
+ * row's store_row result.  msOut (optional, 3 entries): ms of compute (if
+ * any) overlapped with the host image preparation, device pack, DMA. */
 struct ShdRowStore;
+#define SHD_PE_FILL_PREFER_DIRECT 0x1   /* the graph's preferdirectpaths is true */
+#define SHD_PE_FILL_DIRECT_PAIRS  0x2   /* also store the direct entries */
+int shd_pe_fill_rowstore_ex(ShdPe* pe, struct ShdRowStore* st, int32_t fillFlags,
+                            int32_t* rowResult, double* msOut);
 int shd_pe_fill_rowstore(ShdPe* pe, struct ShdRowStore* st, int32_t* rowResult, double* msOut);
 
 /* Wait for outstanding device work of this engine. */
@@ -457,6 +476,14 @@ int shd_topology_cached(const ShdTopology* top, int32_t srcV, int32_t dstV,
 double shd_topology_min_latency(const ShdTopology* top);
 int64_t shd_topology_cache_size(const ShdTopology* top);
 int64_t shd_topology_rows_computed(const ShdTopology* top);
+/* The whole cache in one call, before the first query (SHD_PE_EINVAL once the
+ * cache holds an entry): shd_pe_fill_rowstore_ex on the mirror's own store
+ * with SHD_PE_FILL_DIRECT_PAIRS, plus SHD_PE_FILL_PREFER_DIRECT when the
+ * mirror prefers direct paths.  Afterwards every stored pair of an undirected
+ * graph is a lock-free hit and no query computes a row; on a directed graph
+ * a pair stored under its reverse key still takes the miss path once, which
+ * re-probes that key.  msOut (optional, 3 entries) as shd_pe_fill_rowstore. */
+int shd_topology_fill(ShdTopology* top, double* msOut);
 
 /* ------------------------------------------------------------------------
  * GraphML ingestion (host only, no GPU work).  Replaces

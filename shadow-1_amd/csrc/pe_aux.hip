@@ -11,6 +11,8 @@
 // = igraph incidence order): HBM/L2 latency-bound, no arithmetic to speak of.
 #include <hip/hip_runtime.h>
 
+#include <type_traits>
+
 #include "pe_device.hpp"
 #include "pe_devutil.hpp"
 #include "shd_pathengine.h"
@@ -84,6 +86,29 @@ __global__ __launch_bounds__(256) void k_self_paths(DevGraph g0, const int32_t* 
     }
 }
 
+// _topology_verticesAreAdjacent: an arc s -> t exists (s == t: a self-loop);
+// *arc = its CSR index (unset for s == t)
+__device__ __forceinline__ bool find_arc(const DevGraph& g, int s, int t, int* arc) {
+    if (s == t) return g.hasSelf[s] != 0;
+    const int a = row_lower_bound(g, s, t);
+    *arc = a;
+    return a < g.rowPtr[s + 1] && g.col[a] == t;
+}
+
+// _topology_lookupDirectPath over the arc find_arc found: lat = 0.0 + w of the
+// newest parallel edge (flat[] where it is not the fastest), rel =
+// ((1 * a_s) * a_t) * r_e.  Shared by k_pairs and the prefer-direct pack
+// kernel so that the two cannot drift apart.
+__device__ __forceinline__ void direct_values(const DevGraph& g, int s, int t, int arc, double* L,
+                                              double* R) {
+    double acc = 1.0 * g.vrel[s];                            // :1901-1907
+    acc = acc * g.vrel[t];
+    const double w = s == t ? g.selfLat[s] : (g.flat ? g.flat[arc] : g.lat[arc]);   // get_eid: newest
+    const double r = s == t ? g.selfRel[s] : g.rel[arc];
+    *L = 0.0 + w;                                            // :1920
+    *R = acc * r;                                            // :1921
+}
+
 // One thread per pair.  mode 0: direct path (lat = 0.0 + w, rel =
 // ((1 * a_s) * a_t) * r_e, flags F_DIRECT or F_NOEDGE); mode 1: adjacency
 // only (flags[i] = 1 adjacent, 0 not; s == t adjacent iff it has a loop).
@@ -102,26 +127,15 @@ __global__ __launch_bounds__(256) void k_pairs(DevGraph g0, const int32_t* __res
         return;
     }
     int a = -1;
-    bool found;
-    if (s == t) {
-        found = g.hasSelf[s] != 0;
-    } else {
-        a = row_lower_bound(g, s, t);
-        found = a < g.rowPtr[s + 1] && g.col[a] == t;
-    }
+    const bool found = find_arc(g, s, t, &a);
     if (mode == 1) {
         flags[i] = found ? 1 : 0;
         return;
     }
-    double acc = 1.0 * g.vrel[s];                            // :1901-1907
-    acc = acc * g.vrel[t];
     double L = 0.0, R = 0.0;
     uint8_t f = F_NOEDGE;
     if (found) {
-        const double w = s == t ? g.selfLat[s] : (g.flat ? g.flat[a] : g.lat[a]);   // get_eid: newest
-        const double r = s == t ? g.selfRel[s] : g.rel[a];
-        L = 0.0 + w;                                          // :1920
-        R = acc * r;                                          // :1921
+        direct_values(g, s, t, a, &L, &R);
         f = F_DIRECT;
     }
     lat[i] = L;
@@ -261,19 +275,56 @@ void launch_row_checksums(const DevTable& tab, int64_t firstLocal, int32_t rows,
 namespace shdpe {
 
 // ---------------------------------------------------------------------------
-// Path-cache image (shd_pe_fill_rowstore): the triangular row store of
-// pe_rowstore.cpp filled from the whole table exactly as
-// shd_rowstore_store_rows over rows 0, 1, ..., T-1 in order would fill it
-// (topology.c:1805-1864 per row, :1307-1386 per target, no complete graph,
-// no prefersDirectPaths): slot (a, a + k) takes row a's entry a + k when that
-// fold succeeded (neither F_UNREACHABLE nor F_NOEDGE), else row a + k's
-// entry a (stored under the reversed key), else stays empty.  One workgroup
-// per triangular row: coalesced along row a, the reverse column gathered
-// only for the (rare) failed forward entries.
+// Path-cache image (shd_pe_fill_rowstore[_ex]): the triangular row store of
+// pe_rowstore.cpp filled from the whole table exactly as this sequence of
+// host calls on an empty store would fill it:
+//   1. shd_rowstore_store_rows over rows 0, 1, ..., T-1 in order
+//      (topology.c:1805-1864 per row, :1307-1386 per target), with the
+//      prefersDirectPaths adjacency when SHD_PE_FILL_PREFER_DIRECT is set;
+//   2. with SHD_PE_FILL_DIRECT_PAIRS, shd_rowstore_store(isDirect = 1) of the
+//      _topology_lookupDirectPath values (:1877-1927) for every ordered pair
+//      (p, q) in position order that topology.c:2019-2021 serves directly
+//      (complete graph, or prefersDirectPaths and adjacent).
+// One workgroup per triangular row a, three instantiations:
+//   PACK_PLAIN     slot (a, a + k) takes row a's entry a + k when that fold
+//                  succeeded (neither F_UNREACHABLE nor F_NOEDGE), else row
+//                  a + k's entry a (stored under the reversed key), else
+//                  stays empty: coalesced along row a, the reverse column
+//                  gathered only for the (rare) failed forward entries.
+//   PACK_COMPLETE  a complete graph's table (k_direct_rows) with DIRECT_PAIRS:
+//                  the same slot rule, the entries ARE the direct paths
+//                  (F_NOEDGE where the edge is missing): S_DIRECT is set.
+//   PACK_ADJ       prefersDirectPaths (or a complete graph whose table holds
+//                  Dijkstra rows, forceMode): per slot, u = attached[a], v =
+//                  attached[a + k], the first of
+//                    forward fold ok and not (P and u->v)   non-direct
+//                    k > 0, reverse fold ok, not (P and v->u)   non-direct, REVERSED
+//                    D and P and u->v                       direct
+//                    k > 0, D and P and v->u                direct, REVERSED
+//                  (a complete graph: P set, the non-direct branches off).
+//                  Adjacency comes from two T-bit bitmaps in LDS, Aout (arcs
+//                  u -> attached[q]) and Ain (attached[q] -> u; the same
+//                  bitmap when undirected), which the workgroup fills first by
+//                  striding over u's OUT (and IN) arcs and mapping each head
+//                  through posOf[]: one row's arcs are read once, instead of
+//                  T binary searches per row.  Only slots of a direct branch
+//                  look the arc up (direct_values, k_pairs' arithmetic).
 // ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void k_pack_rowstore(DevTable tab0, const int64_t* __restrict__ off,
-                                                       uint8_t* __restrict__ img,
-                                                       unsigned long long* __restrict__ acc) {
+constexpr int PACK_PLAIN = 0, PACK_COMPLETE = 1, PACK_ADJ = 2;
+
+struct PackNone {};
+struct PackAdj {
+    DevGraph g;              // caller's ids (the graph posOf / attached index)
+    const int32_t* posOf;    // [n] vertex -> table position or -1
+    int32_t words;           // 32-bit words per bitmap, (T + 31) / 32
+    int32_t direct;          // SHD_PE_FILL_DIRECT_PAIRS
+    int32_t complete;        // complete graph: no non-direct entry
+};
+
+template <int MODE>
+__global__ __launch_bounds__(256) void k_pack_rowstore(
+    DevTable tab0, const int64_t* __restrict__ off, uint8_t* __restrict__ img,
+    unsigned long long* __restrict__ acc, std::conditional_t<MODE == PACK_ADJ, PackAdj, PackNone> pa) {
     const DevTable tab = global_view(tab0);
     __shared__ unsigned long long cnt[4], mnb[4];
     const int64_t T = tab.T;
@@ -283,31 +334,94 @@ __global__ __launch_bounds__(256) void k_pack_rowstore(DevTable tab0, const int6
     double* R = L + len;
     uint8_t* S = reinterpret_cast<uint8_t*>(R + len);
     constexpr uint8_t FAILED = F_UNREACHABLE | F_NOEDGE;
+    constexpr uint8_t DIRECT = MODE == PACK_COMPLETE ? SHD_ROWSTORE_S_DIRECT : 0;
     unsigned long long c = 0, mn = INF_BITS;
-    for (int64_t k = threadIdx.x; k < len; k += 256) {
-        const int64_t b = a + k;
-        const size_t fo = (size_t)a * T + b;
-        double lat = 0.0, rel = 0.0;
-        uint8_t s = 0;
-        if (!(tab.flags[fo] & FAILED)) {
-            lat = tab.lat[fo];
-            rel = tab.rel[fo];
-            s = SHD_ROWSTORE_S_STORED;
-        } else if (k > 0) {
-            const size_t ro = (size_t)b * T + a;
-            if (!(tab.flags[ro] & FAILED)) {
+    if constexpr (MODE == PACK_ADJ) {
+        extern __shared__ uint32_t adjBits[];
+        const DevGraph g = global_view(pa.g);
+        const int32_t* __restrict__ posOf = as_global(pa.posOf);
+        const bool directed = g.inCol != g.col;
+        uint32_t* Aout = adjBits;
+        uint32_t* Ain = directed ? adjBits + pa.words : adjBits;
+        for (int w = threadIdx.x; w < (directed ? 2 : 1) * pa.words; w += 256) adjBits[w] = 0u;
+        __syncthreads();
+        const int u = g.attached[a];
+        for (int e = g.rowPtr[u] + threadIdx.x; e < g.rowPtr[u + 1]; e += 256) {
+            const int q = posOf[g.col[e]];
+            if (q >= 0) atomicOr(&Aout[q >> 5], 1u << (q & 31));
+        }
+        if (directed)
+            for (int e = g.inPtr[u] + threadIdx.x; e < g.inPtr[u + 1]; e += 256) {
+                const int q = posOf[g.inCol[e]];
+                if (q >= 0) atomicOr(&Ain[q >> 5], 1u << (q & 31));
+            }
+        if (threadIdx.x == 0 && g.hasSelf[u]) {
+            atomicOr(&Aout[a >> 5], 1u << (a & 31));
+            if (directed) atomicOr(&Ain[a >> 5], 1u << (a & 31));
+        }
+        __syncthreads();
+        const bool nonDirect = !pa.complete, wantDirect = pa.direct != 0;
+        for (int64_t k = threadIdx.x; k < len; k += 256) {
+            const int64_t b = a + k;
+            const size_t fo = (size_t)a * T + b;
+            const bool adjF = (Aout[b >> 5] >> (b & 31)) & 1u;     // u -> v
+            const bool adjR = (Ain[b >> 5] >> (b & 31)) & 1u;      // v -> u
+            double lat = 0.0, rel = 0.0;
+            uint8_t s = 0;
+            if (nonDirect && !adjF && !(tab.flags[fo] & FAILED)) {
+                lat = tab.lat[fo];
+                rel = tab.rel[fo];
+                s = SHD_ROWSTORE_S_STORED;
+            } else if (nonDirect && k > 0 && !adjR && !(tab.flags[(size_t)b * T + a] & FAILED)) {
+                const size_t ro = (size_t)b * T + a;
                 lat = tab.lat[ro];
                 rel = tab.rel[ro];
                 s = SHD_ROWSTORE_S_STORED | SHD_ROWSTORE_S_REVERSED;
+            } else if (wantDirect && (adjF || (k > 0 && adjR))) {
+                const int v = g.attached[b];
+                const int from = adjF ? u : v, to = adjF ? v : u;
+                int arc = -1;
+                if (find_arc(g, from, to, &arc)) {     // (always: the bitmaps came from these arcs)
+                    direct_values(g, from, to, arc, &lat, &rel);
+                    s = SHD_ROWSTORE_S_STORED | SHD_ROWSTORE_S_DIRECT |
+                        (adjF ? 0 : SHD_ROWSTORE_S_REVERSED);
+                }
+            }
+            L[k] = lat;
+            R[k] = rel;
+            S[k] = s;
+            if (s) {
+                ++c;
+                const unsigned long long lb = (unsigned long long)__double_as_longlong(lat);
+                mn = lb < mn ? lb : mn;
             }
         }
-        L[k] = lat;
-        R[k] = rel;
-        S[k] = s;
-        if (s) {
-            ++c;
-            const unsigned long long lb = (unsigned long long)__double_as_longlong(lat);
-            mn = lb < mn ? lb : mn;      // stored latencies are > 0: bit order = value order
+    } else {
+        for (int64_t k = threadIdx.x; k < len; k += 256) {
+            const int64_t b = a + k;
+            const size_t fo = (size_t)a * T + b;
+            double lat = 0.0, rel = 0.0;
+            uint8_t s = 0;
+            if (!(tab.flags[fo] & FAILED)) {
+                lat = tab.lat[fo];
+                rel = tab.rel[fo];
+                s = SHD_ROWSTORE_S_STORED | DIRECT;
+            } else if (k > 0) {
+                const size_t ro = (size_t)b * T + a;
+                if (!(tab.flags[ro] & FAILED)) {
+                    lat = tab.lat[ro];
+                    rel = tab.rel[ro];
+                    s = SHD_ROWSTORE_S_STORED | SHD_ROWSTORE_S_REVERSED | DIRECT;
+                }
+            }
+            L[k] = lat;
+            R[k] = rel;
+            S[k] = s;
+            if (s) {
+                ++c;
+                const unsigned long long lb = (unsigned long long)__double_as_longlong(lat);
+                mn = lb < mn ? lb : mn;      // stored latencies are > 0: bit order = value order
+            }
         }
     }
     for (int d = 32; d >= 1; d >>= 1) {
@@ -340,11 +454,31 @@ __global__ __launch_bounds__(256) void k_rows_all_success(DevTable tab0, int32_t
     if (threadIdx.x == 0) out[blockIdx.x] = bad ? 0 : 1;
 }
 
-void launch_pack_rowstore(const DevTable& tab, const int64_t* dOff, uint8_t* dImg,
-                          unsigned long long* dAcc, void* stream) {
-    if (tab.T <= 0) return;
-    hipLaunchKernelGGL(k_pack_rowstore, dim3((unsigned)tab.T), dim3(256), 0,
-                       reinterpret_cast<hipStream_t>(stream), tab, dOff, dImg, dAcc);
+int pack_adj_lds_bytes(int64_t T, bool directed) {
+    const int64_t b = (T + 31) / 32 * 4 * (directed ? 2 : 1);
+    return b <= 64 * 1024 ? (int)b : -1;
+}
+
+int launch_pack_rowstore(const DevTable& tab, const int64_t* dOff, uint8_t* dImg,
+                         unsigned long long* dAcc, int mode, const DevGraph* g, const int32_t* dPosOf,
+                         bool direct, bool complete, void* stream) {
+    if (tab.T <= 0) return 0;
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    const dim3 grid((unsigned)tab.T), block(256);
+    if (mode == PACK_ADJ) {
+        if (!g || !dPosOf) return -1;
+        const int lds = pack_adj_lds_bytes(tab.T, g->inCol != g->col);
+        if (lds < 0) return -1;
+        const PackAdj pa{*g, dPosOf, (int32_t)((tab.T + 31) / 32), direct ? 1 : 0, complete ? 1 : 0};
+        hipLaunchKernelGGL(k_pack_rowstore<PACK_ADJ>, grid, block, (size_t)lds, st, tab, dOff, dImg, dAcc, pa);
+    } else if (mode == PACK_COMPLETE) {
+        hipLaunchKernelGGL(k_pack_rowstore<PACK_COMPLETE>, grid, block, 0, st, tab, dOff, dImg, dAcc,
+                           PackNone{});
+    } else {
+        hipLaunchKernelGGL(k_pack_rowstore<PACK_PLAIN>, grid, block, 0, st, tab, dOff, dImg, dAcc,
+                           PackNone{});
+    }
+    return 0;
 }
 
 void launch_rows_all_success(const DevTable& tab, int32_t* dOut, void* stream) {

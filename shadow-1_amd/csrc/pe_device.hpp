@@ -291,9 +291,17 @@ void launch_pairs(const DevGraph& g, const int32_t* dSrc, const int32_t* dDst, i
 void launch_incident_min(const DevGraph& g, const int32_t* dEdgeCount, int32_t* dOut, void* stream);
 // path-cache image of the whole table (rows 0..T-1 of `tab`, rowStart 0) in
 // the row store's layout (dOff: shd_rowstore_image_layout); dAcc[0] += stored
-// entries, dAcc[1] = min stored latency bits (init INF_BITS)
-void launch_pack_rowstore(const DevTable& tab, const int64_t* dOff, uint8_t* dImg,
-                          unsigned long long* dAcc, void* stream);
+// entries, dAcc[1] = min stored latency bits (init INF_BITS).  mode 0: the
+// non-direct store rule alone; 1: a complete graph's direct table, entries
+// stored as direct; 2: the prefersDirectPaths rule (or, `complete`, a complete
+// graph whose table holds Dijkstra rows) with adjacency bitmaps in LDS -- g =
+// the graph in the caller's ids, dPosOf[n] = vertex -> table position or -1,
+// `direct` = also store the direct entries.  -1: mode 2's bitmaps exceed LDS
+// (pack_adj_lds_bytes < 0) or its arguments are missing; nothing launched.
+int pack_adj_lds_bytes(int64_t T, bool directed);
+int launch_pack_rowstore(const DevTable& tab, const int64_t* dOff, uint8_t* dImg,
+                         unsigned long long* dAcc, int mode, const DevGraph* g, const int32_t* dPosOf,
+                         bool direct, bool complete, void* stream);
 // per table row: 1 = no F_NOEDGE target (isAllSuccess of topology.c:1815-1859)
 void launch_rows_all_success(const DevTable& tab, int32_t* dOut, void* stream);
 // 64-bit fingerprint per table row (local rows firstLocal .. + rows), pe_aux.hip

@@ -96,6 +96,9 @@ struct Shard {
     void* dXList = nullptr;         // k_exact_dense: per slot its pushes / modifies of a pop
     int32_t* dAny = nullptr;
     int32_t denseRows = 0;
+    int32_t* dPosOf = nullptr;      // vertex -> table position (caller's ids, as dgAux):
+                                    // uploaded by the first prefer-direct fill under copyMu
+                                    // (not in `allocs`, which the compute lock guards)
     DevTable full{};                // whole table on this device after gather
     bool fullOwner = false;         // first shard on its device owns `full`
     ncclComm_t comm = nullptr;      // in-process communicator (distinct devices)
@@ -517,6 +520,7 @@ static void destroy_shard(Shard* s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     for (void* p : s->allocs) (void)hipFree(p);
+    if (s->dPosOf) (void)hipFree(s->dPosOf);
     for (hipEvent_t e : {s->ev0, s->ev1, s->evA, s->evB, s->evP[0], s->evP[1], s->evP[2]})
         if (e) (void)hipEventDestroy(e);
     if (s->stream) (void)hipStreamDestroy(s->stream);
@@ -2137,16 +2141,30 @@ static void host_image_free_cb(void* ctx, void* p) {
     delete static_cast<HostImage*>(ctx);
 }
 
-extern "C" int shd_pe_fill_rowstore(ShdPe* pe, ShdRowStore* st, int32_t* rowResult, double* msOut) {
+extern "C" int shd_pe_fill_rowstore_ex(ShdPe* pe, ShdRowStore* st, int32_t fillFlags,
+                                       int32_t* rowResult, double* msOut) {
     if (!pe || !st) return SHD_PE_EINVAL;
+    if (fillFlags & ~(SHD_PE_FILL_PREFER_DIRECT | SHD_PE_FILL_DIRECT_PAIRS)) return SHD_PE_EINVAL;
     if (shd_rowstore_size(st) != 0) return SHD_PE_EINVAL;   // (adopt_image re-checks under its lock)
     const int32_t T = (int32_t)pe->attached.size();
+    const bool wantDirect = (fillFlags & SHD_PE_FILL_DIRECT_PAIRS) != 0;
+    // the pack kernel's variant: 0 the non-direct rule alone (no flag, or
+    // DIRECT_PAIRS without a pair topology.c:2019-2021 serves directly), 1 a
+    // complete graph's direct table (k_direct_rows wrote the entries), 2 the
+    // adjacency rule (prefersDirectPaths; a complete graph whose table holds
+    // Dijkstra rows, forceMode)
+    int packMode = 0;
+    if (pe->hg.isComplete) packMode = pe->mode == 2 ? 1 : 2;
+    else if (fillFlags & SHD_PE_FILL_PREFER_DIRECT) packMode = 2;
+    if (packMode == 2 && pack_adj_lds_bytes(T, pe->hg.directed) < 0) return SHD_PE_ETOOBIG;
+    static const char* const modeName[3] = {"plain", "complete-direct", "prefer-direct"};
     auto now = [] { return std::chrono::steady_clock::now(); };
     auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
     std::vector<int64_t> off((size_t)T + 1);
     shd_rowstore_image_layout(T, off.data());
     const size_t bytes = (size_t)off[(size_t)T];
-    const bool pack = !pe->hg.isComplete;    // a complete graph stores no non-direct path (:1321)
+    // a complete graph stores no non-direct path (:1321): only its direct pairs
+    const bool pack = !pe->hg.isComplete || wantDirect;
     const auto t0 = now();
     std::unique_ptr<HostImage> him(new HostImage);
     std::thread prep;
@@ -2155,8 +2173,9 @@ extern "C" int shd_pe_fill_rowstore(ShdPe* pe, ShdRowStore* st, int32_t* rowResu
     const auto tc = now();
     if (prep.joinable()) prep.join();
     if (std::getenv("SHDPE_FILL_LOG"))
-        std::fprintf(stderr, "[shdpe] fill_rowstore: compute %.1f ms, image %.2f GB touch %.1f ms + "
-                     "register %.1f ms (%s), join wait %.1f ms\n", ms(t0, tc), bytes / 1e9, him->msTouch,
+        std::fprintf(stderr, "[shdpe] fill_rowstore (%s%s): compute %.1f ms, image %.2f GB touch %.1f ms + "
+                     "register %.1f ms (%s), join wait %.1f ms\n", pack ? modeName[packMode] : "nothing stored",
+                     pack && wantDirect ? ", direct pairs" : "", ms(t0, tc), bytes / 1e9, him->msTouch,
                      him->msRegister, him->registered ? "registered" : "NOT registered", ms(tc, now()));
     if (rc) return rc;
     if (pack && !him->p) return SHD_PE_ENOMEM;
@@ -2167,6 +2186,15 @@ extern "C" int shd_pe_fill_rowstore(ShdPe* pe, ShdRowStore* st, int32_t* rowResu
     else if (pe->G == 1) tab = &s->tab;
     else return SHD_PE_ENOTOWNED;          // rows spread over shards: gather first
     if (hipSetDevice(s->device) != hipSuccess) return SHD_PE_EHIP;
+    if (pack && packMode == 2 && !s->dPosOf) {   // once per engine
+        void* d = nullptr;
+        if (hipMalloc(&d, pe->posOf.size() * 4) != hipSuccess) return SHD_PE_ENOMEM;
+        if (hipMemcpy(d, pe->posOf.data(), pe->posOf.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+            (void)hipFree(d);
+            return SHD_PE_EHIP;
+        }
+        s->dPosOf = static_cast<int32_t*>(d);
+    }
     void *dImg = nullptr, *dOff = nullptr, *dAcc = nullptr, *dAll = nullptr;
     void* const hImg = him->p;
     struct Free {   // device temporaries, every exit path (the host image: ~HostImage)
@@ -2185,9 +2213,10 @@ extern "C" int shd_pe_fill_rowstore(ShdPe* pe, ShdRowStore* st, int32_t* rowResu
     hipError_t e = hipMemcpyAsync(dOff, off.data(), off.size() * 8, hipMemcpyHostToDevice, s->copyStream);
     if (e == hipSuccess) e = hipMemcpyAsync(dAcc, acc0, 16, hipMemcpyHostToDevice, s->copyStream);
     if (e == hipSuccess) {
-        if (pack)
-            launch_pack_rowstore(*tab, (const int64_t*)dOff, (uint8_t*)dImg, (unsigned long long*)dAcc,
-                                 s->copyStream);
+        if (pack && launch_pack_rowstore(*tab, (const int64_t*)dOff, (uint8_t*)dImg,
+                                         (unsigned long long*)dAcc, packMode, &s->dgAux, s->dPosOf,
+                                         wantDirect, pe->hg.isComplete, s->copyStream))
+            return SHD_PE_ETOOBIG;
         launch_rows_all_success(*tab, (int32_t*)dAll, s->copyStream);
         e = hipGetLastError();
     }
@@ -2210,6 +2239,10 @@ extern "C" int shd_pe_fill_rowstore(ShdPe* pe, ShdRowStore* st, int32_t* rowResu
     }
     if (msOut) { msOut[0] = ms(t0, t1); msOut[1] = ms(t1, t2); msOut[2] = ms(t2, t3); }
     return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_fill_rowstore(ShdPe* pe, ShdRowStore* st, int32_t* rowResult, double* msOut) {
+    return shd_pe_fill_rowstore_ex(pe, st, 0, rowResult, msOut);
 }
 
 // ---------------------------------------------------------------------------

@@ -190,6 +190,22 @@ extern "C" int64_t shd_topology_cache_size(const ShdTopology* t) {
     return t ? shd_rowstore_size(t->store) : 0;
 }
 
+// The whole cache before the first query: the engine's one-call fill with
+// the store rule of get_path_entry's two branches (direct pairs where
+// :2019-2021 serves the edge, Dijkstra rows elsewhere).  Later misses
+// (directed graphs: a pair stored under its reverse key) find the table
+// computed and only re-probe.
+extern "C" int shd_topology_fill(ShdTopology* t, double* msOut) {
+    if (!t) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (shd_rowstore_size(t->store) != 0) return SHD_PE_EINVAL;
+    const int32_t flags = SHD_PE_FILL_DIRECT_PAIRS | (t->prefersDirectPaths ? SHD_PE_FILL_PREFER_DIRECT : 0);
+    const int rc = shd_pe_fill_rowstore_ex(t->pe, t->store, flags, nullptr, msOut);
+    if (rc) return rc;
+    t->allComputed = true;
+    return SHD_PE_OK;
+}
+
 extern "C" int64_t shd_topology_rows_computed(const ShdTopology* t) {
     return t ? t->rowsComputed.load(std::memory_order_relaxed) : 0;
 }

@@ -22,6 +22,7 @@ DEBUG_ENV, DEBUG_COUNTERS = 0x1, 0x2
 F_UNREACHABLE, F_NOEDGE, F_ZEROLAT, F_DIRECT, F_EXACT = 0x01, 0x02, 0x04, 0x08, 0x10
 F_FAILED = F_UNREACHABLE | F_NOEDGE
 F_INVALID = 0x80
+FILL_PREFER_DIRECT, FILL_DIRECT_PAIRS = 0x1, 0x2
 
 EXPORTS = [
     "shd_pe_default_options", "shd_pe_create", "shd_pe_destroy", "shd_pe_strerror",
@@ -43,6 +44,7 @@ EXPORTS = [
     "shd_pe_host_alloc", "shd_pe_host_free", "shd_pe_tune", "shd_pe_get_path",
     "shd_rowstore_foreach", "shd_rowstore_store_rows", "shd_pe_put_rows", "shd_pe_row_checksums",
     "shd_rowstore_image_layout", "shd_rowstore_adopt_image", "shd_pe_fill_rowstore",
+    "shd_pe_fill_rowstore_ex", "shd_topology_fill",
 ]
 
 
@@ -164,10 +166,13 @@ def load_library(path: str = LIB_PATH):
         "shd_rowstore_image_layout": (C.c_int, [i32, vp]),
         "shd_rowstore_adopt_image": (C.c_int, [vp, vp, i64, vp, vp, i64, f64]),
         "shd_pe_fill_rowstore": (C.c_int, [vp, vp, vp, vp]),
+        "shd_pe_fill_rowstore_ex": (C.c_int, [vp, vp, i32, vp, vp]),
+        "shd_topology_fill": (C.c_int, [vp, vp]),
     }
-    # ABI-3 additions: an older build loaded through SHDPE_LIB (same-box A/B)
-    # lacks them; the in-tree library must have every symbol
-    optional = {"shd_pe_get_stats_sized", "shd_pe_stats_size"} if os.environ.get("SHDPE_LIB") else set()
+    # ABI-3 / ABI-4 additions: an older build loaded through SHDPE_LIB (same-box
+    # A/B) lacks them; the in-tree library must have every symbol
+    optional = {"shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_fill_rowstore_ex",
+                "shd_topology_fill"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -502,14 +507,25 @@ class Engine:
                   "shd_pe_adjacent_pairs")
         return out
 
-    def fill_rowstore(self, store) -> tuple:
+    def fill_rowstore(self, store, prefers_direct: bool = False, direct_pairs: bool = False,
+                      fill_flags: int | None = None) -> tuple:
         """shd_pe_fill_rowstore: the whole table (computed first if needed,
         the host image prepared meanwhile) into an empty RowStore in one
         device pack + DMA; returns (per-row store_row results, ms of
-        compute-and-image-preparation ("alloc") / pack / DMA)."""
+        compute-and-image-preparation ("alloc") / pack / DMA).
+        prefers_direct / direct_pairs (shd_pe_fill_rowstore_ex,
+        SHD_PE_FILL_PREFER_DIRECT / _DIRECT_PAIRS): refuse the Dijkstra path
+        of adjacent pairs / also store the direct entries topology.c serves
+        from the edge itself; fill_flags passes the flag word as given."""
         res = np.empty(self.T, np.int32)
         ms = np.zeros(3)
-        self._chk(self._lib.shd_pe_fill_rowstore(self.h, store.h, _p(res), _p(ms)), "shd_pe_fill_rowstore")
+        if fill_flags is None:
+            fill_flags = (FILL_PREFER_DIRECT if prefers_direct else 0) | (FILL_DIRECT_PAIRS if direct_pairs else 0)
+        if fill_flags == 0:
+            self._chk(self._lib.shd_pe_fill_rowstore(self.h, store.h, _p(res), _p(ms)), "shd_pe_fill_rowstore")
+        else:
+            self._chk(self._lib.shd_pe_fill_rowstore_ex(self.h, store.h, int(fill_flags), _p(res), _p(ms)),
+                      "shd_pe_fill_rowstore_ex")
         return res, {"alloc": ms[0], "pack": ms[1], "dma": ms[2]}
 
     def is_complete_device(self) -> bool:
@@ -658,6 +674,16 @@ class TopologyShim:
 
     def is_routable(self, s, d):
         return bool(self._lib.shd_topology_is_routable(self.h, int(s), int(d)))
+
+    def fill(self) -> dict:
+        """shd_topology_fill: the whole path cache in one device pack + DMA,
+        before the first query (direct pairs included; EINVAL once the cache
+        holds entries); returns the ms of alloc / pack / DMA."""
+        ms = np.zeros(3)
+        rc = self._lib.shd_topology_fill(self.h, _p(ms))
+        if rc:
+            raise EngineError(rc, "shd_topology_fill")
+        return {"alloc": ms[0], "pack": ms[1], "dma": ms[2]}
 
     def increment(self, s, d):
         return self._lib.shd_topology_increment_path_packet_counter(self.h, int(s), int(d))
