@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 4
+#define SHD_PE_ABI_VERSION 5   /* 5: batched host attachment (shd_pe_attach_*) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -505,6 +505,109 @@ int shd_graphml_describe(const ShdGraphml* g, ShdPeGraphDesc* desc, int32_t* pre
 /* The GraphML id string of vertex v (NULL if out of range). */
 const char* shd_graphml_vertex_id(const ShdGraphml* g, int32_t v);
 void shd_graphml_free(ShdGraphml* g);
+
+/* The vertex attributes topology_attach reads (topology.c:2094-2430), kept by
+ * shd_graphml_parse: keys are matched by exact attr.name as
+ * igraph_cattribute_has_attr does (_topology_findVertexAttributeString /
+ * Double, topology.c:308-347); <default> handling as for the other node keys. */
+#define SHD_PE_VATTR_IP          0
+#define SHD_PE_VATTR_CITYCODE    1
+#define SHD_PE_VATTR_COUNTRYCODE 2
+#define SHD_PE_VATTR_GEOCODE     3
+#define SHD_PE_VATTR_TYPE        4
+#define SHD_PE_VATTR_COUNT       5
+typedef struct ShdPeVertexAttrs {
+    int32_t nVertices;
+    const uint32_t* ip;          /* address_stringToIP(ipStr) (address.c:145-152): inet_pton's s_addr as
+                                    the host reads it; 0xffffffff (INADDR_NONE) when the attribute is
+                                    absent, empty or unparsable.  NULL = graph has no 'ip' key */
+    const int32_t *citycode, *countrycode, *geocode, *type;
+                                 /* interned codes >= 0; -1 = absent or empty string
+                                    (topology.c:316); NULL = no such key */
+    const double *bandwidthDown, *bandwidthUp;   /* NaN = absent; NULL = no key */
+} ShdPeVertexAttrs;
+/* The arrays live in g (valid until shd_graphml_free). */
+int shd_graphml_vertex_attrs(const ShdGraphml* g, ShdPeVertexAttrs* out);
+/* A host's hint string in the code space of attribute `attr` (SHD_PE_VATTR_*):
+ * two strings share a code iff g_ascii_strcasecmp returns 0 (only ASCII A-Z
+ * fold; topology.c:2117-2120).  NULL -> -1 (no hint); an empty string or one
+ * no vertex carries -> -2 (a hint that matches nothing); else the code. */
+int32_t shd_graphml_attr_code(const ShdGraphml* g, int32_t attr, const char* value);
+/* The raw attribute string of vertex v, NULL where
+ * _topology_findVertexAttributeString finds none (absent or empty): what the
+ * attach message() prints (topology.c:2411-2429). */
+const char* shd_graphml_vertex_attr_string(const ShdGraphml* g, int32_t v, int32_t attr);
+
+/* ------------------------------------------------------------------------
+ * Host attachment (topology_attach -> _topology_findAttachmentVertex,
+ * topology.c:2094-2430): which vertex a host with the given hints lands on.
+ * shd_pe_attach_hosts answers `count` hosts at once on the device (attaches do
+ * not depend on each other: each host draws from its own Random, host.c:
+ * 176-181); shd_pe_attach_host is the same rule for one host on the CPU (an
+ * attach after start-up).  Both give identical integers.  The handle is its
+ * own object: attach runs before shd_pe_create has its attached[] list.
+ *
+ * The rule, with usable(x) = x not in {INADDR_NONE 0xffffffff, INADDR_ANY 0,
+ * INADDR_LOOPBACK 0x7f000001} compared against the raw s_addr as :2127 and
+ * :2264 do (on a little-endian host that keeps 127.0.0.1 = 0x0100007f usable
+ * and excludes 1.0.0.127), reqUsable = ipHintGiven && usable(ipHint) and
+ * requestedIP = reqUsable ? ipHint : 0 (the helper is g_new0'd, :2255-2268):
+ *  - exact IP (:2134-2159): if reqUsable and some vertex has usable(vip) &&
+ *    vip == requestedIP, the candidates are exactly those vertices and the
+ *    choice is the random one (:2324); candidateSet 8.
+ *  - otherwise a vertex matches city when code[v] >= 0 && hint >= 0 &&
+ *    code[v] == hint (likewise country, geo, type; :2117-2120), and the first
+ *    non-empty set in the order of :2293-2317 is used: 0 city+type, 1 city,
+ *    2 country+type, 3 country, 4 geo+type, 5 geo, 6 type, 7 all vertices.
+ *  - longest prefix (:2295-2316) applies to sets 0-6 iff reqUsable and the set
+ *    holds a usable vertex address, to set 7 iff ipHintGiven and it does (a
+ *    given but unusable hint then matches against 0).  _topology_
+ *    getLongestPrefixMatch (:2219-2246): match = ~(vip ^ requestedIP) with the
+ *    raw vip of every candidate; the first candidate in vertex order with the
+ *    maximum match wins, except that a maximum of 0 gives the LAST candidate
+ *    (`|| bestMatch == 0` lets every zero replace the previous one).
+ *  - random (:2327-2333): the candidate at ordinal
+ *    (gint) round((gdouble)((numCandidates - 1) * randomDouble)) in vertex
+ *    order (= vertex index order, _topology_iterateAllVertices :980-1017).
+ * randomDouble is what random_nextDouble WOULD return for the host; the
+ * reference only draws on the random branch, so usedRandom tells the caller
+ * whether to advance the host's real Random. */
+typedef struct ShdPeAttachHints {            /* `count` hosts, SoA */
+    int64_t count;
+    const uint8_t*  ipHintGiven;    /* ipHint != NULL */
+    const uint32_t* ipHint;         /* address_stringToIP(ipHint), raw */
+    const int32_t *citycode, *countrycode, *geocode, *type;   /* -1 none, -2 matches nothing, else code */
+    const double*   randomDouble;   /* the value random_nextDouble WOULD return for this host, in [0,1] */
+} ShdPeAttachHints;
+typedef struct ShdPeAttachResult {           /* any pointer but vertex may be NULL */
+    int32_t* vertex;
+    uint8_t* candidateSet;          /* 0 city+type, 1 city, 2 country+type, 3 country, 4 geo+type,
+                                       5 geo, 6 type, 7 all, 8 exact-IP matches */
+    int32_t* numCandidates;
+    uint8_t* usedRandom;            /* 1: the reference consumed the draw (:2327); 0: longest prefix */
+    uint64_t *bwDown, *bwUp;        /* (guint64) of the chosen vertex's bandwidth (:2398-2409), 0 if NaN
+                                       or the graph has no such key */
+} ShdPeAttachResult;
+
+typedef struct ShdPeAttach ShdPeAttach;
+/* Uploads the vertex table (20 B per vertex) to `device`; va is only borrowed.
+ * nVertices <= 0 -> SHD_PE_EINVAL, no gfx950 device -> SHD_PE_ENODEV. */
+int shd_pe_attach_new(const ShdPeVertexAttrs* va, int32_t device, ShdPeAttach** out);
+void shd_pe_attach_free(ShdPeAttach* at);
+/* _topology_findAttachmentVertex for h->count hosts on the device (hosts are
+ * staged in chunks; one wave serves a small group of hosts and walks the
+ * vertex table in vertex order, so no result depends on scheduling).  A
+ * randomDouble outside [0,1] or NaN -> SHD_PE_EINVAL before any work. */
+int shd_pe_attach_hosts(ShdPeAttach* at, const ShdPeAttachHints* h, const ShdPeAttachResult* r);
+/* Hosts per staging chunk (default 65,536; tests and memory-tight callers). */
+int shd_pe_attach_set_chunk(ShdPeAttach* at, int64_t hostsPerChunk);
+/* Of the last shd_pe_attach_hosts call: ms[0] device time of its kernels
+ * (events), ms[1] wall time of the whole call, staging included. */
+int shd_pe_attach_timing(const ShdPeAttach* at, double* ms);
+/* The same rule for host i of h on the CPU, one serial pass over the
+ * vertices, no GPU (the late single attach, topology.c:2371-2430). */
+int shd_pe_attach_host(const ShdPeVertexAttrs* va, const ShdPeAttachHints* h, int64_t i,
+                       const ShdPeAttachResult* r);
 
 #ifdef __cplusplus
 }

@@ -5,6 +5,9 @@
 //   _topology_extractEdgeWeights topology.c:1212-1246 EANV("latency")
 //   edge / vertex 'packetloss'   topology.c:402-444, :1442-1462 (EAN / VAN)
 //   graph 'preferdirectpaths'    topology.c:769-790
+//   vertex 'ip', 'citycode', 'countrycode', 'geocode', 'type' (VAS) and
+//   'bandwidthup' / 'bandwidthdown' (VAN), the attributes topology_attach
+//   reads (_topology_findVertexAttributeString / Double, topology.c:308-347)
 // and produces exactly the ShdPeGraphDesc the engine takes: vertex ids in
 // <node> document order, edge ids in <edge> document order (igraph's GraphML
 // import order), endpoints as written (the engine normalises undirected
@@ -18,6 +21,8 @@
 // entities and numeric character references, comments, processing
 // instructions, DOCTYPE, CDATA.  Namespace prefixes are ignored (GraphML's
 // default namespace is the common case).
+#include <arpa/inet.h>
+
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -141,6 +146,34 @@ double parse_num(const std::string& s) { return parse_num_view(SV{s.data(), s.si
 
 }  // namespace
 
+// One string vertex attribute of topology_attach.  Raw strings are kept once
+// each (rawId per vertex, -1 = the vertex has none; an empty string is "not
+// found" to the reference, topology.c:316, and kept as none); code[] is the
+// interned value after folding ASCII A-Z, i.e. g_ascii_strcasecmp equality
+// (topology.c:2117-2120), -1 = none.
+struct StrAttr {
+    bool hasKey = false;
+    std::vector<int32_t> rawId, code;
+    std::vector<std::string> raws;
+    std::unordered_map<std::string, int32_t> rawIndex, codeIndex;
+    static std::string fold(const char* s, size_t n) {
+        std::string f(s, n);
+        for (char& c : f)
+            if (c >= 'A' && c <= 'Z') c = (char)(c - 'A' + 'a');
+        return f;
+    }
+    void push(const std::string* v) {
+        if (!v || v->empty()) { rawId.push_back(-1); code.push_back(-1); return; }
+        auto it = rawIndex.find(*v);
+        if (it == rawIndex.end()) {
+            it = rawIndex.emplace(*v, (int32_t)raws.size()).first;
+            raws.push_back(*v);
+        }
+        rawId.push_back(it->second);
+        code.push_back(codeIndex.emplace(fold(v->data(), v->size()), (int32_t)codeIndex.size()).first->second);
+    }
+};
+
 struct ShdGraphml {
     int32_t n = 0;
     int32_t directed = 1;
@@ -149,6 +182,10 @@ struct ShdGraphml {
     std::vector<int32_t> src, dst;
     std::vector<double> lat, loss, vloss;
     std::vector<std::string> ids;
+    StrAttr vstr[SHD_PE_VATTR_COUNT];       // indexed by SHD_PE_VATTR_*
+    std::vector<uint32_t> vip;              // address_stringToIP of vstr[IP]
+    bool hasBwDown = false, hasBwUp = false;
+    std::vector<double> bwDown, bwUp;
 };
 
 namespace {
@@ -262,7 +299,11 @@ int parse(const char* buf, size_t len, ShdGraphml& g) {
     SV textView;
     std::string text;
     bool inDefault = false;
-    double eLat = NAN, eLoss = NAN, vLoss = NAN;
+    double eLat = NAN, eLoss = NAN, vLoss = NAN, vBwDown = NAN, vBwUp = NAN;
+    static const char* const kStrAttr[SHD_PE_VATTR_COUNT] = {"ip", "citycode", "countrycode", "geocode",
+                                                             "type"};
+    std::string vStr[SHD_PE_VATTR_COUNT], defStr[SHD_PE_VATTR_COUNT];
+    bool vStrSet[SHD_PE_VATTR_COUNT] = {}, defStrSet[SHD_PE_VATTR_COUNT] = {};
     std::string gPdp;
     bool gPdpSet = false;
     SV eSrc, eDst;
@@ -305,6 +346,7 @@ int parse(const char* buf, size_t len, ShdGraphml& g) {
         return textMode == 1 ? parse_num_view(textView) : (textMode == 2 ? parse_num(text) : NAN);
     };
     double defLat = NAN, defLoss = NAN, defVLoss = NAN;   // fixed once <graph> opens
+    double defBwDown = NAN, defBwUp = NAN;
     auto finish_data = [&]() {
         if (!dataKey) return;
         const Key& k = *dataKey;
@@ -313,6 +355,11 @@ int parse(const char* buf, size_t len, ShdGraphml& g) {
             gPdpSet = true;
         } else if (ctx == 2) {
             if (k.name == "packetloss") vLoss = text_num();
+            else if (k.name == "bandwidthdown") vBwDown = text_num();
+            else if (k.name == "bandwidthup") vBwUp = text_num();
+            else
+                for (int a = 0; a < SHD_PE_VATTR_COUNT; ++a)
+                    if (k.name == kStrAttr[a]) { vStr[a] = text_str(); vStrSet[a] = true; }
         } else if (ctx == 3) {
             if (k.name == "latency") eLat = text_num();
             else if (k.name == "packetloss") eLoss = text_num();
@@ -348,6 +395,12 @@ int parse(const char* buf, size_t len, ShdGraphml& g) {
                 k.type = attr_str(tag, "attr.type");
                 const std::string id = attr_str(tag, "id");
                 if (k.forKind == "node" && k.name == "packetloss") keyNodeLoss = true;
+                if (k.forKind == "node") {
+                    if (k.name == "bandwidthdown") g.hasBwDown = true;
+                    if (k.name == "bandwidthup") g.hasBwUp = true;
+                    for (int a = 0; a < SHD_PE_VATTR_COUNT; ++a)
+                        if (k.name == kStrAttr[a]) g.vstr[a].hasKey = true;
+                }
                 const SV idv{id.data(), id.size()};
                 Key* ex = find_key(idv);
                 if (ex) *ex = k;
@@ -366,9 +419,19 @@ int parse(const char* buf, size_t len, ShdGraphml& g) {
                 deflt("edge", "latency", defLat, nullptr, nullptr);
                 deflt("edge", "packetloss", defLoss, nullptr, nullptr);
                 deflt("node", "packetloss", defVLoss, nullptr, nullptr);
+                deflt("node", "bandwidthdown", defBwDown, nullptr, nullptr);
+                deflt("node", "bandwidthup", defBwUp, nullptr, nullptr);
+                for (int a = 0; a < SHD_PE_VATTR_COUNT; ++a)
+                    deflt("node", kStrAttr[a], vLoss, &defStr[a], &defStrSet[a]);   // string: vLoss unused
             } else if (inGraph && nm.eq("node") && stack.size() == 2) {
                 ctx = 2;
                 vLoss = defVLoss;
+                vBwDown = defBwDown;
+                vBwUp = defBwUp;
+                for (int a = 0; a < SHD_PE_VATTR_COUNT; ++a) {
+                    vStrSet[a] = defStrSet[a];
+                    if (defStrSet[a]) vStr[a] = defStr[a];
+                }
                 const SV* raw = tag.raw("id");
                 std::string_view key;
                 if (!raw) {
@@ -434,6 +497,9 @@ int parse(const char* buf, size_t len, ShdGraphml& g) {
             curKey = nullptr;
         } else if (nm.eq("node") && ctx == 2 && stack.size() == 2) {
             g.vloss.push_back(vLoss);
+            g.bwDown.push_back(vBwDown);
+            g.bwUp.push_back(vBwUp);
+            for (int a = 0; a < SHD_PE_VATTR_COUNT; ++a) g.vstr[a].push(vStrSet[a] ? &vStr[a] : nullptr);
             ctx = 1;
         } else if (nm.eq("edge") && ctx == 3 && stack.size() == 2) {
             // endpoints may name nodes declared later in the document
@@ -461,6 +527,18 @@ int parse(const char* buf, size_t len, ShdGraphml& g) {
     }
     g.n = (int32_t)g.ids.size();
     g.hasVertexLoss = keyNodeLoss;
+    // address_stringToIP (address.c:145-152) once per distinct string
+    {
+        const StrAttr& ipa = g.vstr[SHD_PE_VATTR_IP];
+        std::vector<uint32_t> rawIp(ipa.raws.size());
+        for (size_t i = 0; i < ipa.raws.size(); ++i) {
+            struct in_addr in;
+            rawIp[i] = inet_pton(AF_INET, ipa.raws[i].c_str(), &in) == 1 ? (uint32_t)in.s_addr : 0xffffffffu;
+        }
+        g.vip.resize(ipa.rawId.size());
+        for (size_t v = 0; v < ipa.rawId.size(); ++v)
+            g.vip[v] = ipa.rawId[v] < 0 ? 0xffffffffu : rawIp[(size_t)ipa.rawId[v]];
+    }
     if (gPdpSet && !gPdp.empty()) {
         std::string low;
         for (char c : gPdp) low += (char)tolower((unsigned char)c);
@@ -506,6 +584,35 @@ extern "C" int shd_graphml_describe(const ShdGraphml* g, ShdPeGraphDesc* desc,
 extern "C" const char* shd_graphml_vertex_id(const ShdGraphml* g, int32_t v) {
     if (!g || v < 0 || v >= g->n) return nullptr;
     return g->ids[(size_t)v].c_str();
+}
+
+extern "C" int shd_graphml_vertex_attrs(const ShdGraphml* g, ShdPeVertexAttrs* out) {
+    if (!g || !out) return SHD_PE_EINVAL;
+    auto codes = [&](int a) { return g->vstr[a].hasKey ? g->vstr[a].code.data() : nullptr; };
+    out->nVertices = g->n;
+    out->ip = g->vstr[SHD_PE_VATTR_IP].hasKey ? g->vip.data() : nullptr;
+    out->citycode = codes(SHD_PE_VATTR_CITYCODE);
+    out->countrycode = codes(SHD_PE_VATTR_COUNTRYCODE);
+    out->geocode = codes(SHD_PE_VATTR_GEOCODE);
+    out->type = codes(SHD_PE_VATTR_TYPE);
+    out->bandwidthDown = g->hasBwDown ? g->bwDown.data() : nullptr;
+    out->bandwidthUp = g->hasBwUp ? g->bwUp.data() : nullptr;
+    return SHD_PE_OK;
+}
+
+extern "C" int32_t shd_graphml_attr_code(const ShdGraphml* g, int32_t attr, const char* value) {
+    if (!value) return -1;                               // no hint
+    if (!g || attr < 0 || attr >= SHD_PE_VATTR_COUNT || !value[0]) return -2;
+    const StrAttr& a = g->vstr[attr];
+    const auto it = a.codeIndex.find(StrAttr::fold(value, strlen(value)));
+    return it == a.codeIndex.end() ? -2 : it->second;
+}
+
+extern "C" const char* shd_graphml_vertex_attr_string(const ShdGraphml* g, int32_t v, int32_t attr) {
+    if (!g || v < 0 || v >= g->n || attr < 0 || attr >= SHD_PE_VATTR_COUNT) return nullptr;
+    const StrAttr& a = g->vstr[attr];
+    const int32_t r = a.rawId[(size_t)v];
+    return r < 0 ? nullptr : a.raws[(size_t)r].c_str();
 }
 
 extern "C" void shd_graphml_free(ShdGraphml* g) { delete g; }

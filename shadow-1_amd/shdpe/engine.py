@@ -45,7 +45,12 @@ EXPORTS = [
     "shd_rowstore_foreach", "shd_rowstore_store_rows", "shd_pe_put_rows", "shd_pe_row_checksums",
     "shd_rowstore_image_layout", "shd_rowstore_adopt_image", "shd_pe_fill_rowstore",
     "shd_pe_fill_rowstore_ex", "shd_topology_fill",
+    "shd_graphml_vertex_attrs", "shd_graphml_attr_code", "shd_graphml_vertex_attr_string",
+    "shd_pe_attach_new", "shd_pe_attach_free", "shd_pe_attach_hosts", "shd_pe_attach_host",
+    "shd_pe_attach_set_chunk", "shd_pe_attach_timing",
 ]
+VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
+VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
 
 
 class GraphDesc(C.Structure):
@@ -75,6 +80,26 @@ class Stats(C.Structure):
                 ("msGather", C.c_double), ("rowsTieEarly", C.c_int64), ("batchWaves", C.c_int32),
                 ("batchPostWaves", C.c_int32), ("rowsTieRepaired", C.c_int64),
                 ("batchCoop", C.c_int32), ("relaxCoopAborts", C.c_int64)]
+
+
+class VertexAttrsC(C.Structure):
+    """ShdPeVertexAttrs"""
+    _fields_ = [("nVertices", C.c_int32), ("ip", C.c_void_p), ("citycode", C.c_void_p),
+                ("countrycode", C.c_void_p), ("geocode", C.c_void_p), ("type", C.c_void_p),
+                ("bandwidthDown", C.c_void_p), ("bandwidthUp", C.c_void_p)]
+
+
+class AttachHintsC(C.Structure):
+    """ShdPeAttachHints"""
+    _fields_ = [("count", C.c_int64), ("ipHintGiven", C.c_void_p), ("ipHint", C.c_void_p),
+                ("citycode", C.c_void_p), ("countrycode", C.c_void_p), ("geocode", C.c_void_p),
+                ("type", C.c_void_p), ("randomDouble", C.c_void_p)]
+
+
+class AttachResultC(C.Structure):
+    """ShdPeAttachResult"""
+    _fields_ = [("vertex", C.c_void_p), ("candidateSet", C.c_void_p), ("numCandidates", C.c_void_p),
+                ("usedRandom", C.c_void_p), ("bwDown", C.c_void_p), ("bwUp", C.c_void_p)]
 
 
 class EngineError(RuntimeError):
@@ -168,11 +193,23 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_fill_rowstore": (C.c_int, [vp, vp, vp, vp]),
         "shd_pe_fill_rowstore_ex": (C.c_int, [vp, vp, i32, vp, vp]),
         "shd_topology_fill": (C.c_int, [vp, vp]),
+        "shd_graphml_vertex_attrs": (C.c_int, [vp, vp]),
+        "shd_graphml_attr_code": (i32, [vp, i32, C.c_char_p]),
+        "shd_graphml_vertex_attr_string": (C.c_char_p, [vp, i32, i32]),
+        "shd_pe_attach_new": (C.c_int, [vp, i32, vp]),
+        "shd_pe_attach_free": (None, [vp]),
+        "shd_pe_attach_hosts": (C.c_int, [vp, vp, vp]),
+        "shd_pe_attach_host": (C.c_int, [vp, vp, i64, vp]),
+        "shd_pe_attach_set_chunk": (C.c_int, [vp, i64]),
+        "shd_pe_attach_timing": (C.c_int, [vp, vp]),
     }
-    # ABI-3 / ABI-4 additions: an older build loaded through SHDPE_LIB (same-box
+    # ABI-3 / ABI-4 / ABI-5 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
     optional = {"shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_fill_rowstore_ex",
-                "shd_topology_fill"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_topology_fill", "shd_graphml_vertex_attrs", "shd_graphml_attr_code",
+                "shd_graphml_vertex_attr_string", "shd_pe_attach_new", "shd_pe_attach_free",
+                "shd_pe_attach_hosts", "shd_pe_attach_host", "shd_pe_attach_set_chunk",
+                "shd_pe_attach_timing"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -749,3 +786,185 @@ def parse_graphml(data, name: str = "topology", with_ids: bool = True):
                         vloss=vloss, ids=ids, prefers_direct=bool(pdp.value), name=name)
     finally:
         lib.shd_graphml_free(h)
+
+
+# ---- host attachment (topology_attach, topology.c:2094-2430) ----------------
+_HINT_FIELDS = (("ip_given", np.uint8), ("ip", np.uint32), ("citycode", np.int32),
+                ("countrycode", np.int32), ("geocode", np.int32), ("type", np.int32),
+                ("random", np.float64))
+_RESULT_FIELDS = (("vertex", np.int32), ("candidate_set", np.uint8), ("num_candidates", np.int32),
+                  ("used_random", np.uint8), ("bw_down", np.uint64), ("bw_up", np.uint64))
+
+
+class VertexAttrs:
+    """ShdPeVertexAttrs as numpy arrays: ip (uint32, raw s_addr, 0xffffffff =
+    none), citycode / countrycode / geocode / type (int32 codes, -1 = none),
+    bandwidth_down / bandwidth_up (float64, NaN = none); None = the graph has
+    no such key.  From parse_graphml_vertex_attrs it also maps hint strings
+    (attr_code) and returns the raw strings (attr_string) until close()."""
+
+    def __init__(self, n, ip=None, citycode=None, countrycode=None, geocode=None, type=None,
+                 bandwidth_down=None, bandwidth_up=None, handle=None):
+        def arr(a, dt):
+            if a is None:
+                return None
+            a = np.ascontiguousarray(a, dtype=dt)
+            if a.shape != (n,):
+                raise ValueError(f"vertex attribute of shape {a.shape}, want {(n,)}")
+            return a
+        self.n = int(n)
+        self.ip = arr(ip, np.uint32)
+        self.citycode, self.countrycode = arr(citycode, np.int32), arr(countrycode, np.int32)
+        self.geocode, self.type = arr(geocode, np.int32), arr(type, np.int32)
+        self.bandwidth_down, self.bandwidth_up = arr(bandwidth_down, np.float64), arr(bandwidth_up, np.float64)
+        self._h = handle
+
+    def c_struct(self) -> VertexAttrsC:
+        return VertexAttrsC(self.n, _p(self.ip), _p(self.citycode), _p(self.countrycode),
+                            _p(self.geocode), _p(self.type), _p(self.bandwidth_down),
+                            _p(self.bandwidth_up))
+
+    def attr_code(self, attr: int, value) -> int:
+        """shd_graphml_attr_code: None -> -1, matches nothing -> -2, else the code."""
+        if self._h is None:
+            raise ValueError("attr_code needs attributes parsed from GraphML")
+        if isinstance(value, str):
+            value = value.encode()
+        return int(load_library().shd_graphml_attr_code(self._h, int(attr), value))
+
+    def attr_string(self, v: int, attr: int):
+        """shd_graphml_vertex_attr_string: the raw bytes, or None."""
+        if self._h is None:
+            raise ValueError("attr_string needs attributes parsed from GraphML")
+        return load_library().shd_graphml_vertex_attr_string(self._h, int(v), int(attr))
+
+    def close(self):
+        if getattr(self, "_h", None):
+            load_library().shd_graphml_free(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def parse_graphml_vertex_attrs(data) -> VertexAttrs:
+    """shd_graphml_parse + shd_graphml_vertex_attrs: the vertex attributes
+    topology_attach reads, from GraphML text / bytes / a path (``.xz`` is
+    decompressed here).  Host only."""
+    import lzma
+    if isinstance(data, str) and not data.lstrip().startswith("<"):
+        with open(data, "rb") as f:
+            raw = f.read()
+        data = lzma.decompress(raw) if str(data).endswith(".xz") else raw
+    if isinstance(data, str):
+        data = data.encode()
+    lib = load_library()
+    h = C.c_void_p()
+    rc = lib.shd_graphml_parse(data, len(data), C.byref(h))
+    if rc:
+        raise EngineError(rc, "shd_graphml_parse")
+    va = VertexAttrsC()
+    rc = lib.shd_graphml_vertex_attrs(h, C.byref(va))
+    if rc:
+        lib.shd_graphml_free(h)
+        raise EngineError(rc, "shd_graphml_vertex_attrs")
+    n = int(va.nVertices)
+
+    def arr(ptr, ctype, dtype):
+        if not ptr:
+            return None
+        if n == 0:
+            return np.zeros(0, dtype)
+        return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(n,)).astype(dtype)
+
+    return VertexAttrs(n, arr(va.ip, C.c_uint32, np.uint32), arr(va.citycode, C.c_int32, np.int32),
+                       arr(va.countrycode, C.c_int32, np.int32), arr(va.geocode, C.c_int32, np.int32),
+                       arr(va.type, C.c_int32, np.int32), arr(va.bandwidthDown, C.c_double, np.float64),
+                       arr(va.bandwidthUp, C.c_double, np.float64), handle=h)
+
+
+def _hints_struct(hints: dict):
+    """hints: dict of equally long arrays ip_given (uint8), ip (uint32, raw
+    s_addr of the hint), citycode / countrycode / geocode / type (int32: -1
+    none, -2 matches nothing, else code), random (float64 in [0, 1]).  Returns
+    (ShdPeAttachHints, the arrays it points into)."""
+    keep = {}
+    count = None
+    for k, dt in _HINT_FIELDS:
+        a = np.ascontiguousarray(hints[k], dtype=dt)
+        if a.ndim != 1 or (count is not None and a.shape[0] != count):
+            raise ValueError(f"hints[{k!r}] has shape {a.shape}")
+        count = a.shape[0]
+        keep[k] = a
+    hs = AttachHintsC(count, *(_p(keep[k]) for k, _ in _HINT_FIELDS))
+    return hs, keep
+
+
+def _result_struct(count: int):
+    out = {k: np.zeros(count, dt) for k, dt in _RESULT_FIELDS}
+    return AttachResultC(*(_p(out[k]) for k, _ in _RESULT_FIELDS)), out
+
+
+def attach_host(va: VertexAttrs, hints: dict, i: int) -> dict:
+    """shd_pe_attach_host: _topology_findAttachmentVertex for host i of
+    `hints` on the CPU (no GPU); returns the six result fields as scalars."""
+    hs, keep = _hints_struct(hints)
+    rs, out = _result_struct(hs.count)
+    vs = va.c_struct()
+    rc = load_library().shd_pe_attach_host(C.byref(vs), C.byref(hs), int(i), C.byref(rs))
+    if rc:
+        raise EngineError(rc, "shd_pe_attach_host")
+    return {k: out[k][i].item() for k, _ in _RESULT_FIELDS}
+
+
+class Attacher:
+    """shd_pe_attach_new / shd_pe_attach_hosts: the vertex table on one gfx950
+    device, every host of a batch attached in one call (k_attach,
+    pe_attach.hip).  chunk: hosts per staging chunk (shd_pe_attach_set_chunk)."""
+
+    def __init__(self, va: VertexAttrs, device: int = 0, chunk: int | None = None):
+        self._lib = load_library()
+        vs = va.c_struct()
+        h = C.c_void_p()
+        rc = self._lib.shd_pe_attach_new(C.byref(vs), int(device), C.byref(h))
+        if rc:
+            raise EngineError(rc, "shd_pe_attach_new")
+        self.h = h
+        if chunk is not None:
+            rc = self._lib.shd_pe_attach_set_chunk(h, int(chunk))
+            if rc:
+                self.close()
+                raise EngineError(rc, "shd_pe_attach_set_chunk")
+
+    def attach(self, hints: dict) -> dict:
+        """-> dict of arrays vertex, candidate_set, num_candidates, used_random,
+        bw_down, bw_up, one entry per host."""
+        hs, keep = _hints_struct(hints)
+        rs, out = _result_struct(hs.count)
+        rc = self._lib.shd_pe_attach_hosts(self.h, C.byref(hs), C.byref(rs))
+        if rc:
+            raise EngineError(rc, "shd_pe_attach_hosts")
+        return out
+
+    def timing(self) -> dict:
+        """shd_pe_attach_timing of the last attach(): ms of the kernels
+        (device events) and of the whole call."""
+        ms = np.zeros(2)
+        rc = self._lib.shd_pe_attach_timing(self.h, _p(ms))
+        if rc:
+            raise EngineError(rc, "shd_pe_attach_timing")
+        return {"kernel_ms": float(ms[0]), "wall_ms": float(ms[1])}
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._lib.shd_pe_attach_free(self.h)
+            self.h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass

@@ -345,3 +345,83 @@ def make_config(name: str):
         top = power_law(250_000, m=2, seed=6, quantum=0.005 if name == "c5q" else 0.0)
         return top, sample_attached(top.n, 65_536, seed=7)
     raise KeyError(name)
+
+
+# ---- host attachment (topology_attach, topology.c:2094-2430) ----------------
+# Vertex addresses: the three the reference calls unusable or not as the host
+# reads them (0.0.0.0; 127.0.0.1 = raw 0x0100007f, usable on a little-endian
+# host; 1.0.0.127 = raw 0x7f000001 = INADDR_LOOPBACK unswapped, unusable), an
+# unparsable string, 254.253.252.251 (the bitwise complement of the hint
+# 1.2.3.4: match == 0) and ordinary ones.
+ATTACH_IP_POOL = ("0.0.0.0", "127.0.0.1", "1.0.0.127", "not-an-address", "254.253.252.251",
+                  "10.0.0.1", "10.0.0.2", "10.1.2.3", "192.168.0.9", "8.8.8.8")
+# hint-only addresses: usable, carried by no vertex (longest-prefix matching)
+ATTACH_HINT_ONLY_IPS = ("1.2.3.4", "10.0.0.77", "192.168.1.1")
+
+
+def ip_raw(s: str) -> int:
+    """address_stringToIP (address.c:145-152): inet_pton's s_addr as the host
+    reads it, INADDR_NONE for an unparsable string."""
+    import socket
+    import struct
+    try:
+        return struct.unpack("=I", socket.inet_pton(socket.AF_INET, s))[0]
+    except (OSError, ValueError):
+        return 0xFFFFFFFF
+
+
+def vertex_attrs(n: int, seed: int, n_city: int = 3, n_country: int = 3, n_geo: int = 3,
+                 n_type: int = 2, p_absent: float = 0.35, ip_pool=ATTACH_IP_POOL):
+    """Random vertex attributes for attach (engine.VertexAttrs): codes from
+    small pools so that every candidate set occurs, each attribute absent with
+    probability p_absent (-1; the address: INADDR_NONE), addresses from
+    ip_pool, integer bandwidths."""
+    from .engine import VertexAttrs
+    rng = np.random.default_rng(seed)
+
+    def codes(k):
+        c = rng.integers(0, max(1, k), n).astype(np.int32)
+        c[rng.random(n) < p_absent] = -1
+        return c
+
+    raw = np.array([ip_raw(s) for s in ip_pool], dtype=np.uint32)
+    ip = raw[rng.integers(0, len(raw), n)]
+    ip[rng.random(n) < p_absent] = 0xFFFFFFFF
+    va = VertexAttrs(n, ip, codes(n_city), codes(n_country), codes(n_geo), codes(n_type),
+                     rng.integers(1, 1 << 20, n).astype(np.float64),
+                     rng.integers(1, 1 << 20, n).astype(np.float64))
+    va.pools = (n_city, n_country, n_geo, n_type)
+    va.ip_pool = tuple(ip_pool)
+    return va
+
+
+def attach_hints(va, count: int, seed: int) -> dict:
+    """Random attach hints for `count` hosts against va (the dict
+    engine.Attacher.attach takes): each code hint is absent (-1), matches
+    nothing (-2) or a code of the pool; the address hint is absent, one of the
+    vertex pool (exact matches, unusable and unparsable ones included) or a
+    usable address no vertex has; random is 0.0 / 0.5 / 1.0 or uniform."""
+    rng = np.random.default_rng(seed)
+    pools = getattr(va, "pools", (3, 3, 3, 2))
+    ip_pool = tuple(getattr(va, "ip_pool", ATTACH_IP_POOL))
+
+    def codes(k, p_none):
+        u = rng.random(count)
+        c = rng.integers(0, max(1, k), count).astype(np.int32)
+        c[u < p_none] = -1
+        c[(u >= p_none) & (u < p_none + 0.1)] = -2
+        return c
+
+    hint_ips = np.array([ip_raw(s) for s in ip_pool + ATTACH_HINT_ONLY_IPS], dtype=np.uint32)
+    # half of the address hints come from the hint-only tail
+    pick = np.where(rng.random(count) < 0.5, rng.integers(0, len(ip_pool), count),
+                    len(ip_pool) + rng.integers(0, len(ATTACH_HINT_ONLY_IPS), count))
+    given = (rng.random(count) < 0.6).astype(np.uint8)
+    ip = np.where(given != 0, hint_ips[pick], np.uint32(0xFFFFFFFF)).astype(np.uint32)
+    r = rng.random(count)
+    special = rng.random(count)
+    r[special < 0.1] = 0.0
+    r[(special >= 0.1) & (special < 0.2)] = 1.0
+    r[(special >= 0.2) & (special < 0.3)] = 0.5
+    return dict(ip_given=given, ip=ip, citycode=codes(pools[0], 0.55), countrycode=codes(pools[1], 0.5),
+                geocode=codes(pools[2], 0.45), type=codes(pools[3], 0.4), random=r)
