@@ -172,7 +172,7 @@ struct BatchLaunch {
 // largest tied predecessor distance (the emulation stops past it).
 constexpr int32_t TIE_AMB = 1 << 30;
 struct TieBuf {
-    int32_t cap;             // slots (<= 254: rowAmbig holds 2 + slot)
+    int32_t cap;             // slots (<= 254: rowAmbig holds 2 + slot; mode 3: <= 4096)
     int32_t* count;          // device slot counter (reset per launch)
     double* D;               // [cap][n]
     int32_t* P;              // [cap][n]

@@ -73,7 +73,9 @@ struct Shard {
     BatchLaunch bcfgPost{};         // split kernels: post-kernel variant when the tune picked
                                     // another one than bcfg's (grid 0: bcfg)
     BatchLaunch bcfgCoop{};         // cooperative relax candidate (coop >= 2; grid 0: none)
-    int64_t coopAborts = 0;         // cooperative relax launches aborted (round rerun plain)
+    int64_t coopAborts = 0;         // cooperative relax launches refused by the runtime or aborted
+                                    // at a barrier, counted together (round rerun plain):
+                                    // relaxCoopAborts
     int32_t* dCoopAbort = nullptr;  // host-mapped copy target of the abort word
     bool tuned = false;
     bool timeParts = false;         // split kernels: time relax / post launches (tune)
@@ -872,9 +874,10 @@ static int ensure_table(ShdPe* pe, Shard* sh) {
     return SHD_PE_OK;
 }
 
-// Tie slots for the early-stop emulation (both sparse paths): D f64 + P i32
+// Tie slots for the early-stop emulation (all three relax paths): D f64 + P i32
 // + H i32 + R f64 per vertex, <= 2 GiB, <= 254 slots (rowAmbig stores
-// 2 + slot in a byte); arc indices carry TIE_AMB in bit 30.
+// 2 + slot in a byte; mode 3: <= 4096, see below); arc indices carry TIE_AMB
+// in bit 30.
 static int ensure_tie(ShdPe* pe, Shard* sh) {
     if (sh->dTie || sh->tieTried) return SHD_PE_OK;
     sh->tieTried = true;
@@ -1080,6 +1083,24 @@ static void print_batch_debug(ShdPe* pe, Shard* sh, const int32_t* d0, int32_t n
                  pr / nB / pe->hg.n, ambB, rep);
 }
 
+// SHDPE_DUMP_BATCHES=<file>: per batch its rows (table positions, -1 pads),
+// hub offsets and kernel counters, for offline batch-cost models
+// (tools/batch_cost.py)
+static void dump_batches(const ShdPe* pe, const std::vector<int32_t>& order,
+                         const std::vector<int32_t>& dbg, int32_t nB, int32_t LB) {
+    const char* f = std::getenv("SHDPE_DUMP_BATCHES");
+    FILE* fp = f ? std::fopen(f, "wb") : nullptr;
+    if (!fp) return;
+    const int32_t hdr[2] = {nB, LB};
+    std::fwrite(hdr, 4, 2, fp);
+    std::fwrite(order.data(), 4, order.size(), fp);
+    std::fwrite(dbg.data(), 4, dbg.size(), fp);
+    const int64_t nOff = (int64_t)pe->rowOff.size();
+    std::fwrite(&nOff, 8, 1, fp);
+    std::fwrite(pe->rowOff.data(), 8, pe->rowOff.size(), fp);
+    std::fclose(fp);
+}
+
 static void print_sparse_debug(ShdPe* pe, Shard* sh, const int32_t* dbg, int32_t cnt) {
     double ph = 0, cy[4] = {0, 0, 0, 0}, sub[4] = {0, 0, 0, 0};
     int phMax = 0, jMax = 0, mis = 0, am = 0;
@@ -1160,10 +1181,11 @@ static int relax_coop(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int3
     HIPCHK(hipMemsetAsync(sh->bsc.flags, 0, (size_t)rn * 4, sh->stream));
     BatchLaunch co = relax;
     co.grid = std::min(co.grid, sh->batchSlots);
-    bool rerun = launch_batch_relax_coop(sh->dg, sh->tab, sh->bsc, rows, rn, amb, co, dbg, sh->dTie,
-                                         sh->stream) != 0;
-    if (rerun) {
-        (void)hipGetLastError();                  // the refusal
+    const bool refused = launch_batch_relax_coop(sh->dg, sh->tab, sh->bsc, rows, rn, amb, co, dbg, sh->dTie,
+                                                 sh->stream) != 0;
+    bool rerun = refused;
+    if (refused) {
+        (void)hipGetLastError();                  // the refusal (the abort word was never copied)
     } else {
         HIPCHK(hipGetLastError());
         HIPCHK(hipMemcpyAsync(sh->dCoopAbort, sh->bsc.coCtl + 17, 4, hipMemcpyDeviceToHost, sh->stream));
@@ -1174,7 +1196,7 @@ static int relax_coop(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int3
         ++sh->coopAborts;
         if (pe->tu.debug || pe->tu.tuneLog)
             std::fprintf(stderr, "[shdpe] shard %d: cooperative relax %s; round recomputed by the plain relax\n",
-                         sh->gindex, *sh->dCoopAbort ? "aborted" : "refused");
+                         sh->gindex, refused ? "refused" : "aborted");
         BatchLaunch plain = relax;
         plain.coop = 0;
         plain.grid = std::min(plain.grid, sh->batchSlots);
@@ -1185,369 +1207,414 @@ static int relax_coop(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int3
     return SHD_PE_OK;
 }
 
-// Compute the given table positions (all owned by `sh`), chunked.
+// One chunk's rows for the exact stage, as the chunk's relax stage leaves them.
+struct ExactWork {
+    std::vector<int32_t> rows;       // table positions: early-stop tie rows first, then full-emulation rows
+    std::vector<int32_t> slots;      // per row its tie slot, -1 full emulation (empty: no early-stop row)
+    std::vector<int32_t> denseIdx;   // dense tie rows: their row of D / P (one dense chunk only)
+    void clear() { rows.clear(); slots.clear(); denseIdx.clear(); }
+};
+
+// Rows a sparse relax kernel flagged (amb[i] != 0; ids[i] < 0 pads a batch):
+// early-stop tie rows (amb = 2 + slot) first (k_tie_write takes that
+// prefix), then rows needing the full emulation (amb = 1)
+static void classify_rows(const int32_t* ids, size_t count, const uint8_t* amb, ExactWork& x) {
+    std::vector<int32_t> fullRows;
+    for (size_t i = 0; i < count; ++i) {
+        if (ids[i] < 0 || !amb[i]) continue;
+        if (amb[i] >= 2) {
+            x.rows.push_back(ids[i]);
+            x.slots.push_back(amb[i] - 2);
+        } else {
+            fullRows.push_back(ids[i]);
+        }
+    }
+    if (!x.slots.empty()) {
+        x.rows.insert(x.rows.end(), fullRows.begin(), fullRows.end());
+        x.slots.resize(x.rows.size(), -1);
+    } else {
+        x.rows.swap(fullRows);
+    }
+}
+
+// ---- relax stages: the rows at `pos` (cnt of them, already in dRows) ----------
+
+static int relax_direct(ShdPe*, Shard* sh, const int32_t*, int32_t cnt, ExactWork&) {
+    ShdPeStats& st = sh->stats;
+    HIPCHK(hipEventRecord(sh->evA, sh->stream));
+    launch_direct_rows(sh->dg, sh->tab, sh->dRows, cnt, sh->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sh->evB, sh->stream));
+    HIPCHK(hipEventSynchronize(sh->evB));
+    st.msDirectKernel += elapsed(sh->evA, sh->evB);
+    st.launchesDirect++;
+    return SHD_PE_OK;
+}
+
+static int relax_dense(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x) {
+    ShdPeStats& st = sh->stats;
+    int rc;
+    if ((rc = ensure_dense(pe, sh))) return rc;
+    std::vector<uint8_t> amb;
+    for (int32_t d0 = 0; d0 < cnt; d0 += sh->denseRows) {
+        const int32_t dc = std::min(sh->denseRows, cnt - d0);
+        HIPCHK(hipEventRecord(sh->evA, sh->stream));
+        int sweeps = 0;
+        double flops = 0.0;
+        if (launch_dense_rows(sh->dg, sh->tab, sh->dW, sh->dRl, sh->dD, sh->dP, sh->dRowA, sh->dRowB,
+                              sh->dRowAmbD, sh->dAny, sh->dChunkEpoch, sh->dRows + d0, dc, pe->hg.n,
+                              pe->tu, sh->stream, &sweeps, &flops))
+            return SHD_PE_EHIP;
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipEventRecord(sh->evB, sh->stream));
+        amb.resize(dc);
+        HIPCHK(hipMemcpyAsync(amb.data(), sh->dRowAmbD, dc, hipMemcpyDeviceToHost, sh->stream));
+        HIPCHK(hipStreamSynchronize(sh->stream));
+        st.msDenseKernel += elapsed(sh->evA, sh->evB);
+        st.launchesDense++;
+        st.denseSweeps += sweeps;
+        st.denseFlops += flops;
+        for (int32_t i = 0; i < dc; ++i)
+            if (amb[i]) {
+                x.rows.push_back(pos[d0 + i]);
+                if (dc == cnt) x.denseIdx.push_back(i);   // D / P still hold the row
+            }
+    }
+    return SHD_PE_OK;
+}
+
+// Batches of LB nearby sources (BFS rank order), -1 pads the last.  Host only.
+static std::vector<int32_t> batch_order(const ShdPe* pe, int LB, const int32_t* pos, int32_t cnt,
+                                        int32_t& nB) {
+    std::vector<int32_t> order(pos, pos + cnt);
+    std::stable_sort(order.begin(), order.end(),
+                     [&](int32_t a, int32_t b) { return pe->rank[a] < pe->rank[b]; });
+    nB = (cnt + LB - 1) / LB;
+    order.resize((size_t)nB * LB, -1);
+    if (!pe->rowOff.empty() && nB > 1) {
+        // longest batches first (workgroups take batches in order, so the last round is
+        // made of short ones): a batch's cost grows with its sources' mean distance to
+        // their hub (tools/sim/: correlation 0.53 with arc visits at C4)
+        std::vector<std::pair<double, int32_t>> key(nB);
+        for (int32_t b = 0; b < nB; ++b) {
+            double s = 0.0;
+            int c = 0;
+            for (int l = 0; l < LB; ++l) {
+                const int32_t p = order[(size_t)b * LB + l];
+                if (p >= 0) { s += pe->rowOff[p]; ++c; }
+            }
+            key[b] = {c ? -s / c : 0.0, b};
+        }
+        std::stable_sort(key.begin(), key.end());
+        std::vector<int32_t> re((size_t)nB * LB);
+        for (int32_t i = 0; i < nB; ++i)
+            std::copy(order.begin() + (size_t)key[i].second * LB,
+                      order.begin() + (size_t)(key[i].second + 1) * LB, re.begin() + (size_t)i * LB);
+        order.swap(re);
+    }
+    return order;
+}
+
+// Split kernels: rounds of batches: relax all of them, then the post kernel
+// over the same batches (their dist arrays persist in HBM)
+// (the post kernel may run another variant: bcfgPost)
+static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, int32_t nB) {
+    const int LB = sh->bcfg.lb;
+    int rc;
+    BatchLaunch post = sh->bcfgPost.grid > 0 ? sh->bcfgPost : sh->bcfg;
+    post.grid = std::min(post.grid, sh->batchSlots);
+    for (int32_t r0 = 0; r0 < nB; r0 += sh->batchRound) {
+        const int32_t rn = std::min(sh->batchRound, nB - r0);
+        const size_t ro = (size_t)r0 * LB;
+        if (sh->timeParts) HIPCHK(hipEventRecord(sh->evP[0], sh->stream));
+        for (int part = 1; part <= 2; ++part) {
+            int32_t* const dbgR = sh->dDbg ? sh->dDbg + 16 * r0 : nullptr;
+            if (part == 1 && relax.coop >= 2 && sh->bcfgCoop.grid > 0) {
+                if ((rc = relax_coop(pe, sh, relax, sh->dBatchRows + ro, rn, sh->dBatchAmb + ro, dbgR)))
+                    return rc;
+            } else {
+                HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
+                launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows + ro, rn, sh->dBatchAmb + ro,
+                                  part == 1 ? relax : post, dbgR, sh->dTie, sh->stream, part);
+            }
+            // tests only (SHDPE_TUNE_FAIL_WPE): the relax variant of that wave
+            // count flags every batch failed, as a miscompiled variant would
+            if (part == 1 && pe->tu.failWpe && relax.wpe == pe->tu.failWpe)
+                HIPCHK(hipMemsetAsync(sh->bsc.flags, 1, (size_t)rn * 4, sh->stream));
+            if (sh->timeParts) HIPCHK(hipEventRecord(sh->evP[part], sh->stream));
+            // the post kernel's deferred tie export of this round (the round's dist
+            // arrays persist until the next round's relax)
+            if (part == 1 && sh->tie.req)
+                HIPCHK(hipMemsetD32Async((hipDeviceptr_t)sh->tie.round, r0 / sh->batchRound, 1, sh->stream));
+            if (part == 2 && sh->tie.req)
+                launch_tie_export(sh->dg, sh->bsc, LB, sh->tie, r0 / sh->batchRound, sh->dBatchAmb + ro,
+                                  sh->numCUs * 4, pe->tu.tieCorrupt == 3 ? 0 : -1, sh->stream);
+        }
+        if (sh->timeParts) {
+            HIPCHK(hipEventSynchronize(sh->evP[2]));
+            sh->msPart[0] += elapsed(sh->evP[0], sh->evP[1]);
+            sh->msPart[1] += elapsed(sh->evP[1], sh->evP[2]);
+        }
+    }
+    return SHD_PE_OK;
+}
+
+static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x) {
+    ShdPeStats& st = sh->stats;
+    int rc;
+    if ((rc = ensure_batch(pe, sh))) return rc;
+    int32_t nB = 0;
+    const std::vector<int32_t> order = batch_order(pe, sh->bcfg.lb, pos, cnt, nB);
+    HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
+    if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
+    if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
+    HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
+    HIPCHK(hipEventRecord(sh->evA, sh->stream));
+    // a workgroup indexes its scratch slot by blockIdx: never launch
+    // more workgroups than ensure_batch allocated slots for
+    BatchLaunch relax = sh->bcfg;
+    relax.grid = std::min(relax.grid, sh->batchSlots);
+    if (!sh->bcfg.split)
+        launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows, nB, sh->dBatchAmb, relax,
+                          sh->dDbg, sh->dTie, sh->stream, 0);
+    else if ((rc = batch_rounds(pe, sh, relax, nB)))
+        return rc;
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sh->evB, sh->stream));
+    std::vector<uint8_t> amb(order.size());
+    HIPCHK(hipMemcpyAsync(amb.data(), sh->dBatchAmb, order.size(), hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    st.msSparseKernel += elapsed(sh->evA, sh->evB);
+    st.launchesSparse++;
+    classify_rows(order.data(), order.size(), amb.data(), x);
+    if (sh->dDbg) {
+        std::vector<int32_t> dbg((size_t)nB * 16);
+        HIPCHK(hipMemcpy(dbg.data(), sh->dDbg, dbg.size() * 4, hipMemcpyDeviceToHost));
+        print_batch_debug(pe, sh, dbg.data(), nB);
+        dump_batches(pe, order, dbg, nB, sh->bcfg.lb);
+    }
+    return SHD_PE_OK;
+}
+
+static int relax_sparse(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x) {
+    ShdPeStats& st = sh->stats;
+    int rc;
+    if ((rc = ensure_tie(pe, sh))) return rc;
+    if (sh->dTie) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
+    HIPCHK(hipEventRecord(sh->evA, sh->stream));
+    launch_sparse_rows(sh->dg, sh->tab, sh->sc, sh->dRows, cnt, sh->dRowAmbig, sh->cfg,
+                       sh->dDbg, sh->dTie, sh->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sh->evB, sh->stream));
+    std::vector<uint8_t> amb(cnt);
+    HIPCHK(hipMemcpyAsync(amb.data(), sh->dRowAmbig, cnt, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    st.msSparseKernel += elapsed(sh->evA, sh->evB);
+    st.launchesSparse++;
+    classify_rows(pos, (size_t)cnt, amb.data(), x);
+    if (sh->dDbg) {
+        std::vector<int32_t> dbg((size_t)cnt * 16);
+        HIPCHK(hipMemcpy(dbg.data(), sh->dDbg, dbg.size() * 4, hipMemcpyDeviceToHost));
+        print_sparse_debug(pe, sh, dbg.data(), cnt);
+    }
+    return SHD_PE_OK;
+}
+
+// One chunk's relax stage, by the shard's mode.
+static int relax_stage(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x) {
+    if (pe->mode == 2) return relax_direct(pe, sh, pos, cnt, x);
+    if (pe->opt.forceMode == 3 || pe->hg.latFold) {
+        // (latFold multigraphs: the reported latency is a fold of other
+        // edges' latencies than the distance's -- the exact emulation
+        // carries it as a label, so every row takes that path)
+        x.rows.assign(pos, pos + cnt);
+        return SHD_PE_OK;
+    }
+    if (pe->mode == 3) return relax_dense(pe, sh, pos, cnt, x);
+    if (pe->batched) return relax_batched(pe, sh, pos, cnt, x);
+    return relax_sparse(pe, sh, pos, cnt, x);
+}
+
+// ---- exact stage: the igraph emulation of the rows a relax stage left ---------
+
+// The shard's exact emulation is k_exact_dense (~n arcs per pop: the
+// workgroup-wide scan) rather than k_exact_rows.  (Rows with tie slots in
+// dSlots take k_exact_rows all the same: exact_general.)
+static bool dense_emulation(const ShdPe* pe) {
+    return pe->mode == 3 && pe->opt.forceMode != 3 && !pe->hg.latFold;
+}
+
+// k_exact_dense's per-slot lists, allocated at its first use.
+static int ensure_xlist(Shard* sh) {
+    if (sh->dXList) return SHD_PE_OK;
+    return dev_alloc(sh, &sh->dXList, (size_t)sh->exactGrid * (size_t)sh->sc.stride *
+                                          (size_t)exact_dense_list_bytes());
+}
+
+// The emulation of the first n rows in dRows: in full, but for those of them
+// with a slot in dSl (k_exact_rows only; null: none), which stop early.
+static void launch_emulation(ShdPe* pe, Shard* sh, int32_t n, bool dense, const int32_t* dSl,
+                             long long* dbg) {
+    if (dense)
+        launch_exact_dense(sh->dg, sh->tab, sh->sc, sh->dRows, n, sh->exactGrid, sh->exactHc,
+                           sh->dXList, nullptr, sh->tie, nullptr, sh->stream);
+    else
+        launch_exact_rows(sh->dg, sh->tab, sh->sc, sh->dRows, n, sh->exactGrid, sh->exactHc,
+                          pe->tu.exactHc > 0, dSl, sh->tie, dbg, sh->stream);
+}
+
+// The relevance scan of the first nTie rows in dRows (their slots in dSlots;
+// `slots`: the host's copy), and the test hook right after it.
+static void scan_tie_slots(ShdPe* pe, Shard* sh, const std::vector<int32_t>& slots, int32_t nTie) {
+    launch_tie_scan(sh->dg, sh->dRows, sh->dSlots, nTie, sh->tie, sh->stream);
+    if (pe->tu.tieCorrupt == 1 || pe->tu.tieCorrupt == 2) corrupt_tie_slot(pe, sh, slots, nTie);
+}
+
+// Early-stop rows whose slot failed the exact kernel's consistency check
+// (thr = NaN: the exported distances are not this row's): k_tie_write
+// skipped them.  Reads thr[0, nThr) back and appends those of rows[0, nTie)
+// to `redo`; repair_tie_rows recomputes them by the full emulation.
+static int failed_tie_rows(Shard* sh, const int32_t* rows, const int32_t* slots, int32_t nTie,
+                           int32_t nThr, std::vector<int32_t>& redo) {
+    std::vector<double> thr((size_t)nThr);
+    HIPCHK(hipMemcpyAsync(thr.data(), sh->tie.thr, thr.size() * 8, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    for (int32_t i = 0; i < nTie; ++i)
+        if (std::isnan(thr[(size_t)slots[i]])) redo.push_back(rows[i]);
+    return SHD_PE_OK;
+}
+
+static int repair_tie_rows(ShdPe* pe, Shard* sh, const std::vector<int32_t>& redo, bool dense) {
+    if (redo.empty()) return SHD_PE_OK;
+    std::fprintf(stderr, "[shdpe] shard %d: %zu %searly-stop tie row(s) failed the slot "
+                 "consistency check; recomputed by the full emulation\n",
+                 sh->gindex, redo.size(), dense ? "dense " : "");
+    HIPCHK(hipMemcpyAsync(sh->dRows, redo.data(), redo.size() * 4, hipMemcpyHostToDevice, sh->stream));
+    launch_emulation(pe, sh, (int32_t)redo.size(), dense, nullptr, nullptr);
+    HIPCHK(hipGetLastError());
+    sh->stats.rowsTieRepaired += (int64_t)redo.size();
+    return SHD_PE_OK;
+}
+
+// Dense tie rows with early stop (round 6; undirected graphs whose rows
+// fit one dense chunk, so D / P still hold them): in groups of the
+// tie slots, each row's slot filled from D / P (k_dense_tie_export),
+// the relevance scan, the emulation only until the row's tied
+// predecessors are popped (k_exact_dense) and k_tie_write.  A slot
+// failing the emulation's consistency check is redone in full.
+static int exact_dense_early(ShdPe* pe, Shard* sh, const ExactWork& x) {
+    ShdPeStats& st = sh->stats;
+    int rc;
+    if (!sh->dDenseIdx) {
+        void* di;
+        if ((rc = dev_alloc(sh, &di, (size_t)sh->rowsCap * 4))) return rc;
+        sh->dDenseIdx = (int32_t*)di;
+    }
+    if ((rc = ensure_xlist(sh))) return rc;
+    const int32_t cap = sh->tie.cap;
+    std::vector<int32_t> slots(cap), redo;
+    for (int32_t k = 0; k < cap; ++k) slots[k] = k;
+    HIPCHK(hipMemcpyAsync(sh->dSlots, slots.data(), (size_t)cap * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipEventRecord(sh->evA, sh->stream));
+    for (size_t g0 = 0; g0 < x.rows.size(); g0 += (size_t)cap) {
+        const int32_t k = (int32_t)std::min<size_t>(cap, x.rows.size() - g0);
+        HIPCHK(hipMemcpyAsync(sh->dRows, x.rows.data() + g0, (size_t)k * 4, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipMemcpyAsync(sh->dDenseIdx, x.denseIdx.data() + g0, (size_t)k * 4, hipMemcpyHostToDevice,
+                              sh->stream));
+        HIPCHK(hipMemsetAsync(sh->tie.thr, 0, (size_t)k * 8, sh->stream));
+        launch_dense_tie_export(sh->dg, sh->dD, sh->dP, pe->hg.n, sh->dDenseIdx, sh->dRows, sh->tie,
+                                k, sh->stream);
+        scan_tie_slots(pe, sh, slots, k);
+        // rows of unequal early-stop cost: taken from a counter
+        HIPCHK(hipMemsetAsync(sh->tie.count + 2, 0, 4, sh->stream));
+        launch_exact_dense(sh->dg, sh->tab, sh->sc, sh->dRows, k, sh->exactGrid, sh->exactHc,
+                           sh->dXList, sh->dSlots, sh->tie, sh->tie.count + 2, sh->stream);
+        launch_tie_write(sh->dg, sh->tab, sh->dRows, sh->dSlots, k, sh->tie, sh->stream);
+        HIPCHK(hipGetLastError());
+        if ((rc = failed_tie_rows(sh, x.rows.data() + g0, slots.data(), k, k, redo))) return rc;
+        st.rowsTieEarly += k;
+    }
+    if ((rc = repair_tie_rows(pe, sh, redo, true))) return rc;
+    HIPCHK(hipEventRecord(sh->evB, sh->stream));
+    HIPCHK(hipEventSynchronize(sh->evB));
+    st.msExactKernel += elapsed(sh->evA, sh->evB);
+    st.launchesExact++;
+    st.rowsExact += (int64_t)x.rows.size();
+    return SHD_PE_OK;
+}
+
+// The general form: one emulation launch over the early-stop rows (slots
+// from the sparse kernels' tie export) and the full rows together, then
+// k_tie_write over the early-stop prefix; the cross-check's repairs after
+// the timed window.
+static int exact_general(ShdPe* pe, Shard* sh, const ExactWork& x) {
+    ShdPeStats& st = sh->stats;
+    int rc;
+    HIPCHK(hipMemcpyAsync(sh->dRows, x.rows.data(), x.rows.size() * 4, hipMemcpyHostToDevice, sh->stream));
+    const int32_t* dSl = nullptr;
+    int32_t nTie = 0;
+    if (!x.slots.empty()) {
+        HIPCHK(hipMemcpyAsync(sh->dSlots, x.slots.data(), x.slots.size() * 4, hipMemcpyHostToDevice, sh->stream));
+        dSl = sh->dSlots;
+        while (nTie < (int32_t)x.slots.size() && x.slots[nTie] >= 0) ++nTie;
+    }
+    const bool dense = dense_emulation(pe) && !dSl;
+    if (dense && (rc = ensure_xlist(sh))) return rc;
+    HIPCHK(hipEventRecord(sh->evA, sh->stream));
+    if (nTie > 0) scan_tie_slots(pe, sh, x.slots, nTie);
+    launch_emulation(pe, sh, (int32_t)x.rows.size(), dense, dSl, sh->dXdbg);
+    HIPCHK(hipGetLastError());
+    if (nTie > 0) {
+        launch_tie_write(sh->dg, sh->tab, sh->dRows, sh->dSlots, nTie, sh->tie, sh->stream);
+        HIPCHK(hipGetLastError());
+        st.rowsTieEarly += nTie;
+    }
+    HIPCHK(hipEventRecord(sh->evB, sh->stream));
+    HIPCHK(hipEventSynchronize(sh->evB));
+    st.msExactKernel += elapsed(sh->evA, sh->evB);
+    st.launchesExact++;
+    if (nTie > 0) {
+        std::vector<int32_t> redo;
+        if ((rc = failed_tie_rows(sh, x.rows.data(), x.slots.data(), nTie, sh->tie.cap, redo)) ||
+            (rc = repair_tie_rows(pe, sh, redo, dense)))
+            return rc;
+        if (!redo.empty()) HIPCHK(hipStreamSynchronize(sh->stream));
+    }
+    if (sh->dXdbg && pe->hg.n > 10240) print_exact_debug(sh, x.rows, nTie);
+    st.rowsExact += (int64_t)x.rows.size();
+    return SHD_PE_OK;
+}
+
+// One chunk's exact stage.  (dRows: the dense early-stop form overwrites it
+// with the exact rows only now, the relax stage's ambiguity bytes being on
+// the host.)
+static int exact_stage(ShdPe* pe, Shard* sh, const ExactWork& x) {
+    if (x.rows.empty()) return SHD_PE_OK;
+    if (dense_emulation(pe) && !pe->hg.directed && x.denseIdx.size() == x.rows.size()) {
+        const int rc = ensure_tie(pe, sh);
+        if (rc) return rc;
+        if (sh->tie.cap > 0) return exact_dense_early(pe, sh, x);
+    }
+    return exact_general(pe, sh, x);
+}
+
+// Compute the given table positions (all owned by `sh`), chunked: per chunk
+// one relax stage and one exact stage.
 static int compute_shard(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t count) {
     if (count <= 0) return SHD_PE_OK;
     sh->pathSrc = -1;               // the exact kernels reuse slot 0
     if (hipSetDevice(sh->device) != hipSuccess) return SHD_PE_EHIP;
     int rc = ensure_table(pe, sh);
     if (rc) return rc;
-    std::vector<uint8_t> amb;
-    std::vector<int32_t> exactRows, exactSlots, fullRows;
-    std::vector<int32_t> denseIdx;   // dense tie rows: their row of D / P (one dense chunk only)
+    ExactWork x;
     ShdPeStats& st = sh->stats;
     HIPCHK(hipEventRecord(sh->ev0, sh->stream));
     for (int32_t c0 = 0; c0 < count; c0 += sh->rowsCap) {
         const int32_t cnt = std::min(sh->rowsCap, count - c0);
         HIPCHK(hipMemcpyAsync(sh->dRows, pos + c0, (size_t)cnt * 4, hipMemcpyHostToDevice,
                               sh->stream));
-        exactRows.clear();
-        exactSlots.clear();
-        denseIdx.clear();
-        if (pe->mode == 2) {
-            HIPCHK(hipEventRecord(sh->evA, sh->stream));
-            launch_direct_rows(sh->dg, sh->tab, sh->dRows, cnt, sh->stream);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(sh->evB, sh->stream));
-            HIPCHK(hipEventSynchronize(sh->evB));
-            st.msDirectKernel += elapsed(sh->evA, sh->evB);
-            st.launchesDirect++;
-        } else if (pe->opt.forceMode == 3 || pe->hg.latFold) {
-            // (latFold multigraphs: the reported latency is a fold of other
-            // edges' latencies than the distance's -- the exact emulation
-            // carries it as a label, so every row takes that path)
-            exactRows.assign(pos + c0, pos + c0 + cnt);
-        } else if (pe->mode == 3) {
-            if ((rc = ensure_dense(pe, sh))) return rc;
-            for (int32_t d0 = 0; d0 < cnt; d0 += sh->denseRows) {
-                const int32_t dc = std::min(sh->denseRows, cnt - d0);
-                HIPCHK(hipEventRecord(sh->evA, sh->stream));
-                int sweeps = 0;
-                double flops = 0.0;
-                if (launch_dense_rows(sh->dg, sh->tab, sh->dW, sh->dRl, sh->dD, sh->dP, sh->dRowA,
-                                      sh->dRowB, sh->dRowAmbD, sh->dAny, sh->dChunkEpoch,
-                                      sh->dRows + d0, dc, pe->hg.n, pe->tu, sh->stream, &sweeps,
-                                      &flops))
-                    return SHD_PE_EHIP;
-                HIPCHK(hipGetLastError());
-                HIPCHK(hipEventRecord(sh->evB, sh->stream));
-                amb.resize(dc);
-                HIPCHK(hipMemcpyAsync(amb.data(), sh->dRowAmbD, dc, hipMemcpyDeviceToHost,
-                                      sh->stream));
-                HIPCHK(hipStreamSynchronize(sh->stream));
-                st.msDenseKernel += elapsed(sh->evA, sh->evB);
-                st.launchesDense++;
-                st.denseSweeps += sweeps;
-                st.denseFlops += flops;
-                for (int32_t i = 0; i < dc; ++i)
-                    if (amb[i]) {
-                        exactRows.push_back(pos[c0 + d0 + i]);
-                        if (dc == cnt) denseIdx.push_back(i);   // D / P still hold the row
-                    }
-            }
-        } else if (pe->batched) {
-            if ((rc = ensure_batch(pe, sh))) return rc;
-            // batches of LB nearby sources (BFS rank order), -1 pads the last
-            const int LB = sh->bcfg.lb;
-            std::vector<int32_t> order(pos + c0, pos + c0 + cnt);
-            std::stable_sort(order.begin(), order.end(),
-                             [&](int32_t a, int32_t b) { return pe->rank[a] < pe->rank[b]; });
-            const int32_t nB = (cnt + LB - 1) / LB;
-            order.resize((size_t)nB * LB, -1);
-            if (!pe->rowOff.empty() && nB > 1) {
-                // longest batches first (workgroups take batches in order, so
-                // the last round is made of short ones): a batch's cost grows
-                // with its sources' mean distance to their hub (tools/sim/:
-                // correlation 0.53 with arc visits at C4)
-                std::vector<std::pair<double, int32_t>> key(nB);
-                for (int32_t b = 0; b < nB; ++b) {
-                    double s = 0.0;
-                    int c = 0;
-                    for (int l = 0; l < LB; ++l) {
-                        const int32_t p = order[(size_t)b * LB + l];
-                        if (p >= 0) { s += pe->rowOff[p]; ++c; }
-                    }
-                    key[b] = {c ? -s / c : 0.0, b};
-                }
-                std::stable_sort(key.begin(), key.end());
-                std::vector<int32_t> re((size_t)nB * LB);
-                for (int32_t i = 0; i < nB; ++i)
-                    std::copy(order.begin() + (size_t)key[i].second * LB,
-                              order.begin() + (size_t)(key[i].second + 1) * LB, re.begin() + (size_t)i * LB);
-                order.swap(re);
-            }
-            HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4,
-                                  hipMemcpyHostToDevice, sh->stream));
-            if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
-            if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
-            HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
-            HIPCHK(hipEventRecord(sh->evA, sh->stream));
-            // a workgroup indexes its scratch slot by blockIdx: never launch
-            // more workgroups than ensure_batch allocated slots for
-            BatchLaunch relax = sh->bcfg;
-            relax.grid = std::min(relax.grid, sh->batchSlots);
-            if (!sh->bcfg.split) {
-                launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows, nB, sh->dBatchAmb, relax,
-                                  sh->dDbg, sh->dTie, sh->stream, 0);
-            } else {
-                // rounds of batches: relax all of them, then the post kernel
-                // over the same batches (their dist arrays persist in HBM)
-                // (the post kernel may run another variant: bcfgPost)
-                BatchLaunch post = sh->bcfgPost.grid > 0 ? sh->bcfgPost : sh->bcfg;
-                post.grid = std::min(post.grid, sh->batchSlots);
-                for (int32_t r0 = 0; r0 < nB; r0 += sh->batchRound) {
-                    const int32_t rn = std::min(sh->batchRound, nB - r0);
-                    const size_t ro = (size_t)r0 * LB;
-                    if (sh->timeParts) HIPCHK(hipEventRecord(sh->evP[0], sh->stream));
-                    for (int part = 1; part <= 2; ++part) {
-                        int32_t* const dbgR = sh->dDbg ? sh->dDbg + 16 * r0 : nullptr;
-                        if (part == 1 && relax.coop >= 2 && sh->bcfgCoop.grid > 0) {
-                            if ((rc = relax_coop(pe, sh, relax, sh->dBatchRows + ro, rn, sh->dBatchAmb + ro,
-                                                 dbgR)))
-                                return rc;
-                        } else {
-                            HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
-                            launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows + ro, rn,
-                                              sh->dBatchAmb + ro, part == 1 ? relax : post, dbgR, sh->dTie,
-                                              sh->stream, part);
-                        }
-                        // tests only (SHDPE_TUNE_FAIL_WPE): the relax variant of that wave
-                        // count flags every batch failed, as a miscompiled variant would
-                        if (part == 1 && pe->tu.failWpe && relax.wpe == pe->tu.failWpe)
-                            HIPCHK(hipMemsetAsync(sh->bsc.flags, 1, (size_t)rn * 4, sh->stream));
-                        if (sh->timeParts) HIPCHK(hipEventRecord(sh->evP[part], sh->stream));
-                        // the post kernel's deferred tie export of this round
-                        // (the round's dist arrays persist until the next
-                        // round's relax)
-                        if (part == 1 && sh->tie.req)
-                            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)sh->tie.round, r0 / sh->batchRound, 1,
-                                                     sh->stream));
-                        if (part == 2 && sh->tie.req)
-                            launch_tie_export(sh->dg, sh->bsc, LB, sh->tie, r0 / sh->batchRound,
-                                              sh->dBatchAmb + ro, sh->numCUs * 4,
-                                              pe->tu.tieCorrupt == 3 ? 0 : -1, sh->stream);
-                    }
-                    if (sh->timeParts) {
-                        HIPCHK(hipEventSynchronize(sh->evP[2]));
-                        sh->msPart[0] += elapsed(sh->evP[0], sh->evP[1]);
-                        sh->msPart[1] += elapsed(sh->evP[1], sh->evP[2]);
-                    }
-                }
-            }
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(sh->evB, sh->stream));
-            amb.resize(order.size());
-            HIPCHK(hipMemcpyAsync(amb.data(), sh->dBatchAmb, order.size(), hipMemcpyDeviceToHost,
-                                  sh->stream));
-            HIPCHK(hipStreamSynchronize(sh->stream));
-            st.msSparseKernel += elapsed(sh->evA, sh->evB);
-            st.launchesSparse++;
-            // early-stop tie rows first (k_tie_write takes that prefix),
-            // then rows needing the full emulation
-            fullRows.clear();
-            for (size_t i = 0; i < order.size(); ++i) {
-                if (order[i] < 0 || !amb[i]) continue;
-                if (amb[i] >= 2) {
-                    exactRows.push_back(order[i]);
-                    exactSlots.push_back(amb[i] - 2);
-                } else {
-                    fullRows.push_back(order[i]);
-                }
-            }
-            if (!exactSlots.empty()) {
-                exactRows.insert(exactRows.end(), fullRows.begin(), fullRows.end());
-                exactSlots.resize(exactRows.size(), -1);
-            } else {
-                exactRows.swap(fullRows);
-            }
-            if (sh->dDbg) {
-                std::vector<int32_t> dbg((size_t)nB * 16);
-                HIPCHK(hipMemcpy(dbg.data(), sh->dDbg, dbg.size() * 4, hipMemcpyDeviceToHost));
-                print_batch_debug(pe, sh, dbg.data(), nB);
-                // SHDPE_DUMP_BATCHES=<file>: per batch its rows (table
-                // positions, -1 pads), hub offsets and kernel counters, for
-                // offline batch-cost models (tools/batch_cost.py)
-                if (const char* f = std::getenv("SHDPE_DUMP_BATCHES")) {
-                    if (FILE* fp = std::fopen(f, "wb")) {
-                        const int32_t hdr[2] = {nB, LB};
-                        std::fwrite(hdr, 4, 2, fp);
-                        std::fwrite(order.data(), 4, order.size(), fp);
-                        std::fwrite(dbg.data(), 4, dbg.size(), fp);
-                        const int64_t nOff = (int64_t)pe->rowOff.size();
-                        std::fwrite(&nOff, 8, 1, fp);
-                        std::fwrite(pe->rowOff.data(), 8, pe->rowOff.size(), fp);
-                        std::fclose(fp);
-                    }
-                }
-            }
-        } else {
-            if ((rc = ensure_tie(pe, sh))) return rc;
-            if (sh->dTie) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
-            HIPCHK(hipEventRecord(sh->evA, sh->stream));
-            launch_sparse_rows(sh->dg, sh->tab, sh->sc, sh->dRows, cnt, sh->dRowAmbig, sh->cfg,
-                               sh->dDbg, sh->dTie, sh->stream);
-            HIPCHK(hipGetLastError());
-            HIPCHK(hipEventRecord(sh->evB, sh->stream));
-            amb.resize(cnt);
-            HIPCHK(hipMemcpyAsync(amb.data(), sh->dRowAmbig, cnt, hipMemcpyDeviceToHost,
-                                  sh->stream));
-            HIPCHK(hipStreamSynchronize(sh->stream));
-            st.msSparseKernel += elapsed(sh->evA, sh->evB);
-            st.launchesSparse++;
-            fullRows.clear();
-            for (int32_t i = 0; i < cnt; ++i) {
-                if (!amb[i]) continue;
-                if (amb[i] >= 2) {
-                    exactRows.push_back(pos[c0 + i]);
-                    exactSlots.push_back(amb[i] - 2);
-                } else {
-                    fullRows.push_back(pos[c0 + i]);
-                }
-            }
-            if (!exactSlots.empty()) {
-                exactRows.insert(exactRows.end(), fullRows.begin(), fullRows.end());
-                exactSlots.resize(exactRows.size(), -1);
-            } else {
-                exactRows.swap(fullRows);
-            }
-            if (sh->dDbg) {
-                std::vector<int32_t> dbg((size_t)cnt * 16);
-                HIPCHK(hipMemcpy(dbg.data(), sh->dDbg, dbg.size() * 4, hipMemcpyDeviceToHost));
-                print_sparse_debug(pe, sh, dbg.data(), cnt);
-            }
-        }
-        // Dense tie rows with early stop (round 6; undirected graphs whose rows
-        // fit one dense chunk, so D / P still hold them): in groups of the
-        // tie slots, each row's slot filled from D / P (k_dense_tie_export),
-        // the relevance scan, the emulation only until the row's tied
-        // predecessors are popped (k_exact_dense) and k_tie_write.  A slot
-        // failing the emulation's consistency check is redone in full.
-        if (!exactRows.empty() && pe->mode == 3 && pe->opt.forceMode != 3 && !pe->hg.latFold &&
-            !pe->hg.directed && denseIdx.size() == exactRows.size()) {
-            if ((rc = ensure_tie(pe, sh))) return rc;
-            if (sh->tie.cap > 0 && !sh->dDenseIdx) {
-                void* di;
-                if ((rc = dev_alloc(sh, &di, (size_t)sh->rowsCap * 4))) return rc;
-                sh->dDenseIdx = (int32_t*)di;
-            }
-            if (sh->tie.cap > 0) {
-                if (!sh->dXList &&
-                    (rc = dev_alloc(sh, &sh->dXList, (size_t)sh->exactGrid * (size_t)sh->sc.stride *
-                                                         (size_t)exact_dense_list_bytes())))
-                    return rc;
-                const int32_t cap = sh->tie.cap;
-                std::vector<int32_t> slots(cap), redo;
-                for (int32_t k = 0; k < cap; ++k) slots[k] = k;
-                HIPCHK(hipMemcpyAsync(sh->dSlots, slots.data(), (size_t)cap * 4, hipMemcpyHostToDevice,
-                                      sh->stream));
-                HIPCHK(hipEventRecord(sh->evA, sh->stream));
-                for (size_t g0 = 0; g0 < exactRows.size(); g0 += (size_t)cap) {
-                    const int32_t k = (int32_t)std::min<size_t>(cap, exactRows.size() - g0);
-                    HIPCHK(hipMemcpyAsync(sh->dRows, exactRows.data() + g0, (size_t)k * 4,
-                                          hipMemcpyHostToDevice, sh->stream));
-                    HIPCHK(hipMemcpyAsync(sh->dDenseIdx, denseIdx.data() + g0, (size_t)k * 4,
-                                          hipMemcpyHostToDevice, sh->stream));
-                    HIPCHK(hipMemsetAsync(sh->tie.thr, 0, (size_t)k * 8, sh->stream));
-                    launch_dense_tie_export(sh->dg, sh->dD, sh->dP, pe->hg.n, sh->dDenseIdx, sh->dRows, sh->tie,
-                                            k, sh->stream);
-                    launch_tie_scan(sh->dg, sh->dRows, sh->dSlots, k, sh->tie, sh->stream);
-                    // rows of unequal early-stop cost: taken from a counter
-                    HIPCHK(hipMemsetAsync(sh->tie.count + 2, 0, 4, sh->stream));
-                    launch_exact_dense(sh->dg, sh->tab, sh->sc, sh->dRows, k, sh->exactGrid, sh->exactHc,
-                                       sh->dXList, sh->dSlots, sh->tie, sh->tie.count + 2, sh->stream);
-                    launch_tie_write(sh->dg, sh->tab, sh->dRows, sh->dSlots, k, sh->tie, sh->stream);
-                    HIPCHK(hipGetLastError());
-                    std::vector<double> thr((size_t)k);
-                    HIPCHK(hipMemcpyAsync(thr.data(), sh->tie.thr, (size_t)k * 8, hipMemcpyDeviceToHost,
-                                          sh->stream));
-                    HIPCHK(hipStreamSynchronize(sh->stream));
-                    for (int32_t i = 0; i < k; ++i)
-                        if (std::isnan(thr[(size_t)i])) redo.push_back(exactRows[g0 + (size_t)i]);
-                    st.rowsTieEarly += k;
-                }
-                if (!redo.empty()) {
-                    std::fprintf(stderr, "[shdpe] shard %d: %zu dense early-stop tie row(s) failed the slot "
-                                 "consistency check; recomputed by the full emulation\n",
-                                 sh->gindex, redo.size());
-                    HIPCHK(hipMemcpyAsync(sh->dRows, redo.data(), redo.size() * 4, hipMemcpyHostToDevice,
-                                          sh->stream));
-                    launch_exact_dense(sh->dg, sh->tab, sh->sc, sh->dRows, (int32_t)redo.size(),
-                                       sh->exactGrid, sh->exactHc, sh->dXList, nullptr, sh->tie, nullptr,
-                                       sh->stream);
-                    HIPCHK(hipGetLastError());
-                    st.rowsTieRepaired += (int64_t)redo.size();
-                }
-                HIPCHK(hipEventRecord(sh->evB, sh->stream));
-                HIPCHK(hipEventSynchronize(sh->evB));
-                st.msExactKernel += elapsed(sh->evA, sh->evB);
-                st.launchesExact++;
-                st.rowsExact += (int64_t)exactRows.size();
-                exactRows.clear();
-            }
-        }
-        if (!exactRows.empty()) {
-            HIPCHK(hipMemcpyAsync(sh->dRows, exactRows.data(), exactRows.size() * 4,
-                                  hipMemcpyHostToDevice, sh->stream));
-            const int32_t* dSl = nullptr;
-            int32_t nTie = 0;
-            if (!exactSlots.empty()) {
-                HIPCHK(hipMemcpyAsync(sh->dSlots, exactSlots.data(), exactSlots.size() * 4,
-                                      hipMemcpyHostToDevice, sh->stream));
-                dSl = sh->dSlots;
-                while (nTie < (int32_t)exactSlots.size() && exactSlots[nTie] >= 0) ++nTie;
-            }
-            const bool dense = pe->mode == 3 && pe->opt.forceMode != 3 && !pe->hg.latFold && !dSl;
-            if (dense && !sh->dXList &&
-                (rc = dev_alloc(sh, &sh->dXList, (size_t)sh->exactGrid * (size_t)sh->sc.stride *
-                                                     (size_t)exact_dense_list_bytes())))
-                return rc;
-            HIPCHK(hipEventRecord(sh->evA, sh->stream));
-            if (nTie > 0) launch_tie_scan(sh->dg, sh->dRows, sh->dSlots, nTie, sh->tie, sh->stream);
-            if (nTie > 0 && (pe->tu.tieCorrupt == 1 || pe->tu.tieCorrupt == 2))
-                corrupt_tie_slot(pe, sh, exactSlots, nTie);
-            if (dense)      // ~n arcs per pop: the workgroup-wide scan
-                launch_exact_dense(sh->dg, sh->tab, sh->sc, sh->dRows, (int32_t)exactRows.size(),
-                                   sh->exactGrid, sh->exactHc, sh->dXList, nullptr, sh->tie, nullptr,
-                                   sh->stream);
-            else
-                launch_exact_rows(sh->dg, sh->tab, sh->sc, sh->dRows, (int32_t)exactRows.size(),
-                                  sh->exactGrid, sh->exactHc, pe->tu.exactHc > 0, dSl, sh->tie,
-                                  sh->dXdbg, sh->stream);
-            HIPCHK(hipGetLastError());
-            if (nTie > 0) {
-                launch_tie_write(sh->dg, sh->tab, sh->dRows, sh->dSlots, nTie, sh->tie, sh->stream);
-                HIPCHK(hipGetLastError());
-                st.rowsTieEarly += nTie;
-            }
-            HIPCHK(hipEventRecord(sh->evB, sh->stream));
-            HIPCHK(hipEventSynchronize(sh->evB));
-            st.msExactKernel += elapsed(sh->evA, sh->evB);
-            st.launchesExact++;
-            // early-stop rows whose slot failed the exact kernel's consistency
-            // check (thr = NaN: the exported distances are not this row's):
-            // k_tie_write skipped them; the full emulation recomputes them
-            if (nTie > 0) {
-                std::vector<double> thr((size_t)sh->tie.cap);
-                HIPCHK(hipMemcpy(thr.data(), sh->tie.thr, thr.size() * 8, hipMemcpyDeviceToHost));
-                std::vector<int32_t> redo;
-                for (int32_t i = 0; i < nTie; ++i)
-                    if (std::isnan(thr[(size_t)exactSlots[i]])) redo.push_back(exactRows[i]);
-                if (!redo.empty()) {
-                    std::fprintf(stderr, "[shdpe] shard %d: %zu early-stop tie row(s) failed the slot "
-                                 "consistency check; recomputed by the full emulation\n",
-                                 sh->gindex, redo.size());
-                    HIPCHK(hipMemcpyAsync(sh->dRows, redo.data(), redo.size() * 4, hipMemcpyHostToDevice,
-                                          sh->stream));
-                    launch_exact_rows(sh->dg, sh->tab, sh->sc, sh->dRows, (int32_t)redo.size(), sh->exactGrid,
-                                      sh->exactHc, pe->tu.exactHc > 0, nullptr, sh->tie, nullptr, sh->stream);
-                    HIPCHK(hipGetLastError());
-                    HIPCHK(hipStreamSynchronize(sh->stream));
-                    st.rowsTieRepaired += (int64_t)redo.size();
-                }
-            }
-            if (sh->dXdbg && pe->hg.n > 10240) print_exact_debug(sh, exactRows, nTie);
-            st.rowsExact += (int64_t)exactRows.size();
-        }
+        x.clear();
+        if ((rc = relax_stage(pe, sh, pos + c0, cnt, x)) || (rc = exact_stage(pe, sh, x))) return rc;
     }
     HIPCHK(hipEventRecord(sh->ev1, sh->stream));
     HIPCHK(hipEventSynchronize(sh->ev1));
@@ -1638,6 +1705,13 @@ extern "C" int shd_pe_tune(ShdPe* pe) {
         int64_t ex[4] = {0, 0, 0, 0};   // rows each candidate sent to the exact path
         BatchLaunch cand[4] = {sh->bcfg, sh->bcfgAlt, sh->bcfgAlt2, sh->bcfgCoop};
         const BatchLaunch orig[3] = {sh->bcfg, sh->bcfgAlt, sh->bcfgAlt2};
+        // a failed compute: the shard as it was before the tune
+        auto fail = [&](int rc) {
+            sh->bcfg = orig[0]; sh->bcfgAlt = orig[1]; sh->bcfgAlt2 = orig[2];
+            sh->bcfgPost = BatchLaunch{};
+            sh->stats = keep;
+            return rc;
+        };
         int nc = 1;
         if (sh->bcfgAlt.grid > 0) cand[nc++] = sh->bcfgAlt;
         if (sh->bcfgAlt2.grid > 0) cand[nc++] = sh->bcfgAlt2;
@@ -1657,11 +1731,7 @@ extern "C" int shd_pe_tune(ShdPe* pe) {
                 sh->timeParts = rep == 1 && sh->bcfg.split;
                 int rc = compute_shard(pe, sh, pos.data(), sh->rowCount);
                 sh->timeParts = false;
-                if (rc) {
-                    sh->bcfg = orig[0]; sh->bcfgAlt = orig[1]; sh->bcfgAlt2 = orig[2];
-                    sh->stats = keep;
-                    return rc;
-                }
+                if (rc) return fail(rc);
                 ms[k] = sh->stats.msSparseKernel - m0;
                 part[k][0] = sh->msPart[0];
                 part[k][1] = sh->msPart[1];
@@ -1714,12 +1784,7 @@ extern "C" int shd_pe_tune(ShdPe* pe) {
                 sh->timeParts = true;
                 const int rc = compute_shard(pe, sh, pos.data(), sh->rowCount);
                 sh->timeParts = false;
-                if (rc) {
-                    sh->bcfg = orig[0]; sh->bcfgAlt = orig[1]; sh->bcfgAlt2 = orig[2];
-                    sh->bcfgPost = BatchLaunch{};
-                    sh->stats = keep;
-                    return rc;
-                }
+                if (rc) return fail(rc);
                 double& b = best[rep & 1];
                 if (sh->msPart[0] > 0.0 && (b == 0.0 || sh->msPart[0] < b)) b = sh->msPart[0];
             }

@@ -463,6 +463,7 @@ def test_dense_minplus_shipped_minus_one(E, oracle_mod):
     st = _check_engine(E, oracle_mod, m1, np.arange(top.n))
     assert st["mode"] == 3 and st["launchesDense"] >= 1
     assert st["rowsExact"] > 0
+    assert st["rowsTieEarly"] == st["rowsExact"], st    # one dense chunk: every tie row stops early
 
 
 @pytest.mark.parametrize("n,seed", [(700, 3), (1200, 5)])
@@ -470,6 +471,18 @@ def test_dense_minplus_random(E, oracle_mod, n, seed):
     top = G.dense(n, seed=seed, drop_edge=True)
     st = _check_engine(E, oracle_mod, top, np.arange(n), sources=np.arange(0, n, 9))
     assert st["mode"] == 3 and st["denseSweeps"] >= 2
+
+
+def test_dense_early_stop_tie_rows(E, oracle_mod):
+    """Integer latencies on a dense graph: most rows have a vertex whose tight
+    predecessors tie.  The rows fit one dense chunk and one group of tie
+    slots, so every tie row takes the early-stop emulation and none of them
+    fails the slot cross-check."""
+    top = G.dense(300, seed=3, drop_edge=True, quantum=1.0)
+    st = _check_engine(E, oracle_mod, top, np.arange(300))
+    assert st["mode"] == 3, st
+    assert st["rowsTieEarly"] == st["rowsExact"] > 0, st
+    assert st["rowsTieRepaired"] == 0, st
 
 
 def test_dense_forced_on_sparse_graph(E, oracle_mod):
@@ -813,7 +826,7 @@ def test_cooperative_relax_abort_recomputes(E, oracle_mod, monkeypatch):
 
 
 @pytest.mark.parametrize("mode", ["1", "2"])
-@pytest.mark.parametrize("case", ["batched", "sparse"])
+@pytest.mark.parametrize("case", ["batched", "sparse", "dense"])
 def test_tie_slot_cross_check_repairs(E, oracle_mod, monkeypatch, case, mode):
     """Early-stop tie rows: the exact kernel checks every vertex it popped
     against the exported distance of the same row (a slot holding another
@@ -827,6 +840,9 @@ def test_tie_slot_cross_check_repairs(E, oracle_mod, monkeypatch, case, mode):
     monkeypatch.setenv("SHDPE_TIE_CORRUPT", mode)
     if case == "batched":
         top, att, force = G.random_sparse(600, 6, seed=216, quantum=1.0), np.arange(599), 5
+    elif case == "dense":
+        # mode 3 by density; the rows fit one dense chunk: the dense early-stop form
+        top, att, force = G.dense(300, seed=3, drop_edge=True, quantum=1.0), np.arange(300), 0
     else:
         top, att, force = G.rgg(2000, seed=9, quantum=0.05), None, 1
         att = np.arange(top.n, dtype=np.int32)

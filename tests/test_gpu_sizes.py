@@ -321,7 +321,8 @@ def test_dense_quantized_tie_rows(E, oracle_mod, quantum):
     eng.compute_all()
     st = eng.stats()
     assert st["mode"] == 3
-    assert st["rowsTieRepaired"] == 0, st          # dense tie rows take the full emulation
+    assert st["rowsTieRepaired"] == 0, st          # dense tie rows take the early-stop emulation
+    assert st["rowsTieEarly"] == st["rowsExact"], st
     ties = tie_positions(eng, E)
     if quantum >= 1.0:
         assert ties.shape[0] > 0 and st["rowsExact"] >= ties.shape[0]
