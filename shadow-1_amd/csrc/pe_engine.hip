@@ -44,6 +44,30 @@ namespace {
 
 constexpr int LDS_BYTES = 160 * 1024;
 
+// A shard's choice of k_batch_rows variant.  configure_batch fills it,
+// ensure_batch lowers every grid in it to the scratch slots (the one place: a
+// workgroup indexes its slot by blockIdx), shd_pe_tune times cand[] and
+// writes the picks.  Every launch of the batched path takes its BatchLaunch
+// from relax / post or from a BatchTrial of the tune.
+struct BatchPlan {
+    BatchLaunch cand[4];            // what shd_pe_tune times, in its order: the untuned relax
+                                    // pick, the other of 4 / 8 waves, 6 waves, the cooperative
+    int nc = 0;
+    int coop = -1;                  // cand[coop] is the cooperative relax (coop >= 2); -1: none
+    BatchLaunch relax{};            // picks in use: the relax launch (with the delta chosen) ...
+    BatchLaunch post{};             // ... and, split kernels, the post launch
+    bool tunable() const { return nc > 1 || coop >= 0; }
+};
+
+// One timed run of shd_pe_tune: the launches to use instead of the plan's
+// picks, and what the split kernels' relax / post parts took (summed over
+// the rounds; 0 when not split).
+struct BatchTrial {
+    BatchLaunch relax{}, post{};
+    bool timed = false;
+    double msRelax = 0.0, msPost = 0.0;
+};
+
 struct Shard {
     int gindex = 0;                 // global shard index
     int device = 0;
@@ -67,23 +91,16 @@ struct Shard {
     int32_t rowsCap = 0;
     SparseLaunch cfg{};
     int exactGrid = 0, exactHc = 1;
-    BatchLaunch bcfg{};
-    BatchLaunch bcfgAlt{};          // the other kernel variant (grid 0: none), shd_pe_tune
-    BatchLaunch bcfgAlt2{};         // a third variant (6 waves), shd_pe_tune
-    BatchLaunch bcfgPost{};         // split kernels: post-kernel variant when the tune picked
-                                    // another one than bcfg's (grid 0: bcfg)
-    BatchLaunch bcfgCoop{};         // cooperative relax candidate (coop >= 2; grid 0: none)
+    BatchPlan plan{};
     int64_t coopAborts = 0;         // cooperative relax launches refused by the runtime or aborted
                                     // at a barrier, counted together (round rerun plain):
                                     // relaxCoopAborts
     int32_t* dCoopAbort = nullptr;  // host-mapped copy target of the abort word
     bool tuned = false;
-    bool timeParts = false;         // split kernels: time relax / post launches (tune)
-    double msPart[2] = {0.0, 0.0};
     BatchScratch bsc{};
     bool batchReady = false;
     int32_t batchRound = 0;         // split kernels: batches per round (persisted dist arrays)
-    int32_t batchSlots = 0;         // scratch slots allocated (no launch may exceed it)
+    int32_t batchSlots = 0;         // scratch slots allocated (ensure_batch: no grid of the plan exceeds it)
     int32_t* dBatchRows = nullptr;
     uint8_t* dBatchAmb = nullptr;
     TieBuf tie{};                   // early-stop tie rows (batched path)
@@ -232,9 +249,9 @@ extern "C" const char* shd_pe_strerror(int code) {
 
 static inline int a16(long x) { return (int)((x + 15) & ~15L); }
 
-// Kernel configuration for one shard's device.  Returns SHD_PE_ETOOBIG when
-// no kernel layout can hold the graph's per-row LDS state.
-static int configure(ShdPe* pe, Shard* sh) {
+// The sparse kernel's LDS layout and grid.  False when no layout can hold the
+// graph's per-row LDS state.
+static bool configure_sparse(ShdPe* pe, Shard* sh) {
     const HostGraph& g = pe->hg;
     const Tuning& tu = pe->tu;
     const long n = g.n;
@@ -282,6 +299,14 @@ static int configure(ShdPe* pe, Shard* sh) {
     if (!(c.delta > 0)) c.delta = 1.0;
     c.kflags = tu.kflags;
     sh->cfg = c;
+    return !(layout == 0 && need0 > LDS);
+}
+
+// The exact kernels' heap split and grid.
+static void configure_exact(ShdPe* pe, Shard* sh) {
+    const Tuning& tu = pe->tu;
+    const long n = pe->hg.n;
+    const int LDS = LDS_BYTES;
     // exact kernels: n <= exact_soa_max_n() keeps heap + index2 wholly in
     // LDS (16 B per vertex, several rows per CU); larger graphs keep the top
     // of the heap in LDS (12 B per entry, up to the whole 160 KB) and the
@@ -297,10 +322,63 @@ static int configure(ShdPe* pe, Shard* sh) {
     if (tu.exactHc > 0) sh->exactHc = std::min(sh->exactHc, tu.exactHc);   // tests: global heap tail
     const int exPerCU = (int)std::max<long>(1, std::min<long>(8, LDS / perWG));
     sh->exactGrid = sh->numCUs * (tu.exactPerCU > 0 ? tu.exactPerCU : exPerCU);
-    // Batched multi-source kernel: the layout for graphs whose per-row state
-    // does not fit LDS (LAYOUT 0), or on request (forceMode 5).
-    pe->batched = pe->mode == 1 &&
-                  (tu.batch == 1 || (tu.batch != 0 && layout == 0) || pe->opt.forceMode == 5);
+}
+
+// configure_batch's cooperative candidate, added to the plan after the plain
+// picks (`b`: the plain relax pick; v4 / v6 / v8: the variants).
+// Cooperative relax (PART 3, K workgroups of one XCD per batch): for a
+// shard with fewer batches than the plain relax has workgroup slots --
+// the C4 8-GPU shard's 256 LB-8 batches leave one of the two 8-wave
+// slots of every CU idle -- the batch's listing rounds are shared by K
+// workgroups.  SHDPE_BATCH_COOP=K forces it, =1 makes it a candidate of
+// shd_pe_tune (off by default: slower than the plain relax wherever it
+// was measured).
+static void configure_batch_coop(ShdPe* pe, Shard* sh, const BatchLaunch& b, const BatchLaunch& v4,
+                                 const BatchLaunch& v6, const BatchLaunch& v8, bool ok6, bool ok8) {
+    const Tuning& tu = pe->tu;
+    const int LDS = LDS_BYTES;
+    BatchPlan& p = sh->plan;
+    if (!(pe->batched && b.split && !b.gbits && (b.lb == 8 || b.lb == 16) && tu.batchCoop >= 1)) return;
+    const int K = tu.batchCoop >= 2 ? std::min(tu.batchCoop, 8) : 2;
+    const int wpeC = tu.batchCoopWpe == 4 || tu.batchCoopWpe == 6 || tu.batchCoopWpe == 8
+                         ? tu.batchCoopWpe
+                         : ok8 ? 8 : ok6 ? 6 : 4;
+    BatchLaunch c2 = wpeC == 8 ? v8 : wpeC == 6 ? v6 : v4;
+    c2.split = 1;
+    const void* fn = batch_coop_kernel_ptr(b.lb, wpeC);
+    int per = 0;
+    if (!(c2.ldsBytes <= LDS &&
+          hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, c2.ldsBytes) == hipSuccess &&
+          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, c2.threads, c2.ldsBytes) == hipSuccess &&
+          per >= 1))
+        return;
+    c2.grid = sh->numCUs * per;
+    c2.coop = K;
+    const int64_t nB = ((int64_t)sh->rowCount + b.lb - 1) / b.lb;
+    if (tu.batchCoop >= 2) {
+        // forced: the relax variant in use and the only candidate; the post
+        // kernel stays the plain pick's
+        p = BatchPlan{};
+        p.cand[p.nc++] = c2;
+        p.coop = 0;
+        p.relax = c2;
+        p.post = b;
+    } else if (nB * K <= c2.grid && nB < b.grid) {
+        // a tune candidate only on request (SHDPE_BATCH_COOP=1): measured
+        // slower than the plain relax at every shard size (round 6, C4
+        // N=8: 17.1-22.6 vs 16.8 ms; profiles/r06_shard_times.txt)
+        p.coop = p.nc;
+        p.cand[p.nc++] = c2;
+    }
+}
+
+// The batched kernel's variants and the shard's plan of them.  False when
+// neither the 4- nor the 8-wave variant fits the LDS.
+static bool configure_batch(ShdPe* pe, Shard* sh) {
+    const HostGraph& g = pe->hg;
+    const Tuning& tu = pe->tu;
+    const long n = g.n;
+    const int LDS = LDS_BYTES;
     BatchLaunch b{};
     // LB = 16 sources per batch; 8 when a shard has too few rows to give
     // every CU a batch of 16.  C4 per-rank shard times, same box: round 5
@@ -354,61 +432,47 @@ static int configure(ShdPe* pe, Shard* sh) {
     const int forced = tu.batchWpe == 4 || tu.batchWpe == 6 || tu.batchWpe == 8 ? tu.batchWpe : 0;
     auto v8 = make(8), v4 = make(4), v6 = make(6);
     const bool ok8 = v8.second >= 1, ok4 = v4.second >= 1, ok6 = v6.second >= 2 && b.threads == 1024;
-    if (pe->batched && !ok8 && !ok4) return SHD_PE_ETOOBIG;
-    if (!pe->batched && layout == 0 && need0 > LDS) return SHD_PE_ETOOBIG;
     const int first = forced == 6 && ok6 ? 6 : forced == 8 && ok8 ? 8 : ok4 ? 4 : 8;
     v8.first.split = v4.first.split = v6.first.split = tu.batchSplit ? 1 : 0;
     b = first == 8 ? v8.first : first == 6 ? v6.first : v4.first;
-    sh->bcfgAlt = sh->bcfgAlt2 = BatchLaunch{};
-    if (!forced && ok8 && ok4) sh->bcfgAlt = first == 8 ? v4.first : v8.first;
+    BatchPlan& p = sh->plan;
+    p = BatchPlan{};
+    p.cand[p.nc++] = b;
+    if (!forced && ok8 && ok4) p.cand[p.nc++] = first == 8 ? v4.first : v8.first;
     // the 6-wave variant (768 threads: 80 VGPRs, fewer spills than 8 waves'
     // 64) joins the tune when two of its workgroups fit a CU
-    if (!forced && ok6 && tu.batchSplit) sh->bcfgAlt2 = v6.first;
-    (void)need0;
-    sh->bcfg = b;
-    sh->bcfgPost = BatchLaunch{};
-    if (!forced && first == 4 && ok6 && b.split && b.lb >= 16) sh->bcfgPost = v6.first;
-    // Cooperative relax (PART 3, K workgroups of one XCD per batch): for a
-    // shard with fewer batches than the plain relax has workgroup slots --
-    // the C4 8-GPU shard's 256 LB-8 batches leave one of the two 8-wave
-    // slots of every CU idle -- the batch's listing rounds are shared by K
-    // workgroups.  SHDPE_BATCH_COOP=K forces it, =1 makes it a candidate of
-    // shd_pe_tune (off by default: slower than the plain relax wherever it
-    // was measured).
-    sh->bcfgCoop = BatchLaunch{};
-    if (pe->batched && b.split && !b.gbits && (b.lb == 8 || b.lb == 16) && tu.batchCoop >= 1) {
-        const int K = tu.batchCoop >= 2 ? std::min(tu.batchCoop, 8) : 2;
-        const int wpeC = tu.batchCoopWpe == 4 || tu.batchCoopWpe == 6 || tu.batchCoopWpe == 8
-                             ? tu.batchCoopWpe
-                             : ok8 ? 8 : ok6 ? 6 : 4;
-        BatchLaunch c2 = wpeC == 8 ? v8.first : wpeC == 6 ? v6.first : v4.first;
-        c2.split = 1;
-        const void* fn = batch_coop_kernel_ptr(b.lb, wpeC);
-        int per = 0;
-        if (c2.ldsBytes <= LDS &&
-            hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, c2.ldsBytes) == hipSuccess &&
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, c2.threads, c2.ldsBytes) == hipSuccess &&
-            per >= 1) {
-            c2.grid = sh->numCUs * per;
-            c2.coop = K;
-            const int64_t nB = ((int64_t)sh->rowCount + b.lb - 1) / b.lb;
-            // a tune candidate only on request (SHDPE_BATCH_COOP=1): measured
-            // slower than the plain relax at every shard size (round 6, C4
-            // N=8: 17.1-22.6 vs 16.8 ms; profiles/r06_shard_times.txt)
-            if (tu.batchCoop >= 2 || (tu.batchCoop == 1 && nB * K <= c2.grid && nB < b.grid))
-                sh->bcfgCoop = c2;
-        }
-        if (tu.batchCoop >= 2 && sh->bcfgCoop.grid > 0) {
-            sh->bcfg = sh->bcfgCoop;        // forced: the relax variant in use
-            sh->bcfgPost = b;
-            sh->bcfgAlt = sh->bcfgAlt2 = BatchLaunch{};
-        }
-    }
-    sh->stats.deltaUsed = pe->batched ? b.delta : c.delta;
+    if (!forced && ok6 && tu.batchSplit) p.cand[p.nc++] = v6.first;
+    p.relax = p.post = b;
+    if (!forced && first == 4 && ok6 && b.split && b.lb >= 16) p.post = v6.first;
+    configure_batch_coop(pe, sh, b, v4.first, v6.first, v8.first, ok6, ok8);
+    return ok8 || ok4;
+}
+
+// The stats that name the plan's picks (configure, and shd_pe_tune after it
+// changed them).
+static void plan_stats(const ShdPe* pe, Shard* sh) {
+    const BatchPlan& p = sh->plan;
+    sh->stats.deltaUsed = pe->batched ? p.relax.delta : sh->cfg.delta;
     sh->stats.batched = pe->batched ? 1 : 0;
-    sh->stats.batchLanes = pe->batched ? b.lb : 0;
-    sh->stats.batchWaves = pe->batched ? b.wpe : 0;
-    sh->stats.batchPostWaves = pe->batched && b.split ? (sh->bcfgPost.grid > 0 ? sh->bcfgPost.wpe : b.wpe) : 0;
+    sh->stats.batchLanes = pe->batched ? p.relax.lb : 0;
+    sh->stats.batchWaves = pe->batched ? p.relax.wpe : 0;
+    sh->stats.batchPostWaves = pe->batched && p.relax.split ? p.post.wpe : 0;
+}
+
+// Kernel configuration for one shard's device.  Returns SHD_PE_ETOOBIG when
+// no kernel layout can hold the graph's per-row LDS state.
+static int configure(ShdPe* pe, Shard* sh) {
+    const Tuning& tu = pe->tu;
+    const bool sparseFits = configure_sparse(pe, sh);
+    configure_exact(pe, sh);
+    // Batched multi-source kernel: the layout for graphs whose per-row state
+    // does not fit LDS (LAYOUT 0), or on request (forceMode 5).
+    pe->batched = pe->mode == 1 &&
+                  (tu.batch == 1 || (tu.batch != 0 && sh->cfg.layout == 0) || pe->opt.forceMode == 5);
+    const bool batchFits = configure_batch(pe, sh);
+    if (pe->batched && !batchFits) return SHD_PE_ETOOBIG;
+    if (!pe->batched && !sparseFits) return SHD_PE_ETOOBIG;
+    plan_stats(pe, sh);
     return SHD_PE_OK;
 }
 
@@ -912,26 +976,36 @@ static int ensure_tie(ShdPe* pe, Shard* sh) {
 static int ensure_batch(ShdPe* pe, Shard* sh) {
     if (sh->batchReady) return SHD_PE_OK;
     const size_t NS = ((size_t)pe->hg.n + 63) & ~(size_t)63;
-    const size_t LB = (size_t)sh->bcfg.lb;
-    const size_t bitBytes = sh->bcfg.gbits ? (size_t)batch_bits_words(pe->hg.n) * 4 : 0;
+    BatchPlan& plan = sh->plan;
+    const size_t LB = (size_t)plan.relax.lb;
+    const size_t bitBytes = plan.relax.gbits ? (size_t)batch_bits_words(pe->hg.n) * 4 : 0;
     const size_t perSlot = NS * LB * (8 + 16) + NS * 4 + bitBytes;   // D, L
     // scratch budget (default 64 GiB): fewer resident batches on huge graphs
     const double budget = pe->tu.batchScratchGB * (double)(1ull << 30);
     const size_t maxSlots = std::max<size_t>(1, (size_t)(budget / (double)perSlot));
     const size_t nBatchesAll = ((size_t)sh->rowCount + LB - 1) / LB;
-    const size_t grid = (size_t)std::max({sh->bcfg.grid, sh->bcfgAlt.grid, sh->bcfgAlt2.grid});
+    size_t grid = 0;                               // the candidates' largest
+    for (int k = 0; k < plan.nc; ++k) grid = std::max(grid, (size_t)plan.cand[k].grid);
     // (a cooperative launch needs one slot per resident workgroup: its grid
     // is the whole resident set, more workgroups than batches)
-    const size_t coGrid = sh->bcfgCoop.grid > 0 ? (size_t)sh->bcfgCoop.grid : 0;
-    const size_t slots = std::min<size_t>({std::max(grid, coGrid), maxSlots,
-                                          std::max<size_t>({(size_t)1, nBatchesAll, coGrid})});
+    const size_t coGrid = plan.coop >= 0 ? (size_t)plan.cand[plan.coop].grid : 0;
+    const size_t slots = std::min<size_t>({grid, maxSlots, std::max<size_t>({(size_t)1, nBatchesAll, coGrid})});
     if (coGrid > slots) {                          // scratch budget: no cooperative relax
-        if (sh->bcfg.coop >= 2) { sh->bcfg = sh->bcfgPost.grid > 0 ? sh->bcfgPost : sh->bcfg; sh->bcfg.coop = 0; }
-        sh->bcfgCoop = BatchLaunch{};
+        plan.nc = plan.coop;                       // (the cooperative candidate is the last)
+        plan.coop = -1;
+        if (plan.relax.coop >= 2) {                // a forced one: the plain kernel of its post variant
+            plan.relax = plan.post;
+            plan.relax.coop = 0;
+            plan.cand[plan.nc++] = plan.relax;
+            plan_stats(pe, sh);
+        }
     }
-    sh->bcfg.grid = (int32_t)std::min<size_t>(slots, (size_t)sh->bcfg.grid);
-    if (sh->bcfgAlt.grid > 0) sh->bcfgAlt.grid = (int32_t)std::min<size_t>(slots, (size_t)sh->bcfgAlt.grid);
-    if (sh->bcfgAlt2.grid > 0) sh->bcfgAlt2.grid = (int32_t)std::min<size_t>(slots, (size_t)sh->bcfgAlt2.grid);
+    // a workgroup indexes its scratch slot by blockIdx: no launch may have
+    // more workgroups than slots, so every grid of the plan is lowered here
+    sh->batchSlots = (int32_t)slots;
+    for (int k = 0; k < plan.nc; ++k) plan.cand[k].grid = std::min(plan.cand[k].grid, sh->batchSlots);
+    plan.relax.grid = std::min(plan.relax.grid, sh->batchSlots);
+    plan.post.grid = std::min(plan.post.grid, sh->batchSlots);
     int rc;
     // split kernels: one persisted dist array per batch of a round (relax ->
     // post), the rest per resident workgroup; rounds sized by free memory
@@ -939,7 +1013,7 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     // of 131 GB beside its 107 GB table -- 2 rounds under a 96 GiB cap were
     // 5% slower, profiles/r04_ab_notes.txt r04i)
     size_t roundB = slots;
-    if (sh->bcfg.split) {
+    if (plan.relax.split) {
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) freeB = (size_t)16 << 30;
         const size_t perD = NS * LB * 8;
@@ -949,7 +1023,6 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
         roundB = std::max<size_t>(slots, std::min<size_t>(nBatchesAll, dBudget / perD));
     }
     sh->batchRound = (int32_t)roundB;
-    sh->batchSlots = (int32_t)slots;
     void *D, *L, *q, *rows, *amb, *fl;
     if ((rc = dev_alloc(sh, &D, roundB * NS * LB * 8)) || (rc = dev_alloc(sh, &L, slots * NS * LB * 16)) ||
         (rc = dev_alloc(sh, &q, slots * NS * 4 + 64)) ||
@@ -976,11 +1049,11 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     }
     sh->dBatchRows = (int32_t*)rows;
     sh->dBatchAmb = (uint8_t*)amb;
-    if (sh->bcfgCoop.grid > 0) {
+    if (plan.coop >= 0) {
         // cooperative relax state: control words, one barrier line per group,
         // two publication buffers of near bits + scalars per member per group
-        const size_t maxGroups = (size_t)sh->bcfgCoop.grid;
-        const size_t K = (size_t)sh->bcfgCoop.coop;
+        const size_t maxGroups = (size_t)plan.cand[plan.coop].grid;
+        const size_t K = (size_t)plan.cand[plan.coop].coop;
         const size_t nwp = (size_t)batch_bits_words(pe->hg.n) / 2;
         void *cc, *pub, *pubS;
         if ((rc = dev_alloc(sh, &cc, 128 + maxGroups * 128)) ||
@@ -1036,7 +1109,7 @@ static float elapsed(hipEvent_t a, hipEvent_t b) {
 
 // Kernel counters of k_batch_rows (SHD_PE_DEBUG_COUNTERS): phase cycles,
 // re-visits, jump rounds, per-batch cost spread.
-static void print_batch_debug(ShdPe* pe, Shard* sh, const int32_t* d0, int32_t nB) {
+static void print_batch_debug(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int32_t* d0, int32_t nB) {
     double ph = 0, pr = 0, kc[5] = {0, 0, 0, 0, 0}, arcsP = 0, lanesP = 0, bmax = 0, bmean = 0, cand = 0,
            walks = 0;
     long ambB = 0, rep = 0;
@@ -1079,7 +1152,7 @@ static void print_batch_debug(ShdPe* pe, Shard* sh, const int32_t* d0, int32_t n
                      why[3], why[4], why[5], why[6], why[7]);
     std::fprintf(stderr, "[shdpe] batch LB=%d batches=%d grid=%d delta=%.3f | phases/batch=%.1f "
                  "vertex-procs/batch=%.0f (%.2f per vertex) | tie batches=%ld repairs=%ld\n",
-                 sh->bcfg.lb, nB, sh->bcfg.grid, sh->bcfg.delta, ph / nB, pr / nB,
+                 relax.lb, nB, relax.grid, relax.delta, ph / nB, pr / nB,
                  pr / nB / pe->hg.n, ambB, rep);
 }
 
@@ -1176,12 +1249,10 @@ static std::mutex g_coopMu[64];
 static int relax_coop(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int32_t* rows, int32_t rn,
                       uint8_t* amb, int32_t* dbg) {
     std::lock_guard<std::mutex> devLock(g_coopMu[sh->device & 63]);
-    const size_t maxGroups = (size_t)sh->bcfgCoop.grid;
+    const size_t maxGroups = (size_t)sh->plan.cand[sh->plan.coop].grid;
     HIPCHK(hipMemsetAsync(sh->bsc.coCtl, 0, 128 + maxGroups * 128, sh->stream));
     HIPCHK(hipMemsetAsync(sh->bsc.flags, 0, (size_t)rn * 4, sh->stream));
-    BatchLaunch co = relax;
-    co.grid = std::min(co.grid, sh->batchSlots);
-    const bool refused = launch_batch_relax_coop(sh->dg, sh->tab, sh->bsc, rows, rn, amb, co, dbg, sh->dTie,
+    const bool refused = launch_batch_relax_coop(sh->dg, sh->tab, sh->bsc, rows, rn, amb, relax, dbg, sh->dTie,
                                                  sh->stream) != 0;
     bool rerun = refused;
     if (refused) {
@@ -1199,7 +1270,6 @@ static int relax_coop(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int3
                          sh->gindex, refused ? "refused" : "aborted");
         BatchLaunch plain = relax;
         plain.coop = 0;
-        plain.grid = std::min(plain.grid, sh->batchSlots);
         HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
         launch_batch_rows(sh->dg, sh->tab, sh->bsc, rows, rn, amb, plain, dbg, sh->dTie, sh->stream, 1);
         HIPCHK(hipGetLastError());
@@ -1317,19 +1387,20 @@ static std::vector<int32_t> batch_order(const ShdPe* pe, int LB, const int32_t* 
 
 // Split kernels: rounds of batches: relax all of them, then the post kernel
 // over the same batches (their dist arrays persist in HBM)
-// (the post kernel may run another variant: bcfgPost)
-static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, int32_t nB) {
-    const int LB = sh->bcfg.lb;
+// (the post kernel may run another variant than the relax).  A timed trial
+// gets the parts' times.
+static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const BatchLaunch& post, int32_t nB,
+                        BatchTrial* trial) {
+    const int LB = relax.lb;
+    const bool timed = trial && trial->timed;
     int rc;
-    BatchLaunch post = sh->bcfgPost.grid > 0 ? sh->bcfgPost : sh->bcfg;
-    post.grid = std::min(post.grid, sh->batchSlots);
     for (int32_t r0 = 0; r0 < nB; r0 += sh->batchRound) {
         const int32_t rn = std::min(sh->batchRound, nB - r0);
         const size_t ro = (size_t)r0 * LB;
-        if (sh->timeParts) HIPCHK(hipEventRecord(sh->evP[0], sh->stream));
+        if (timed) HIPCHK(hipEventRecord(sh->evP[0], sh->stream));
         for (int part = 1; part <= 2; ++part) {
             int32_t* const dbgR = sh->dDbg ? sh->dDbg + 16 * r0 : nullptr;
-            if (part == 1 && relax.coop >= 2 && sh->bcfgCoop.grid > 0) {
+            if (part == 1 && relax.coop >= 2 && sh->plan.coop >= 0) {
                 if ((rc = relax_coop(pe, sh, relax, sh->dBatchRows + ro, rn, sh->dBatchAmb + ro, dbgR)))
                     return rc;
             } else {
@@ -1341,7 +1412,7 @@ static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, int32_t 
             // count flags every batch failed, as a miscompiled variant would
             if (part == 1 && pe->tu.failWpe && relax.wpe == pe->tu.failWpe)
                 HIPCHK(hipMemsetAsync(sh->bsc.flags, 1, (size_t)rn * 4, sh->stream));
-            if (sh->timeParts) HIPCHK(hipEventRecord(sh->evP[part], sh->stream));
+            if (timed) HIPCHK(hipEventRecord(sh->evP[part], sh->stream));
             // the post kernel's deferred tie export of this round (the round's dist
             // arrays persist until the next round's relax)
             if (part == 1 && sh->tie.req)
@@ -1350,34 +1421,40 @@ static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, int32_t 
                 launch_tie_export(sh->dg, sh->bsc, LB, sh->tie, r0 / sh->batchRound, sh->dBatchAmb + ro,
                                   sh->numCUs * 4, pe->tu.tieCorrupt == 3 ? 0 : -1, sh->stream);
         }
-        if (sh->timeParts) {
+        if (timed) {
             HIPCHK(hipEventSynchronize(sh->evP[2]));
-            sh->msPart[0] += elapsed(sh->evP[0], sh->evP[1]);
-            sh->msPart[1] += elapsed(sh->evP[1], sh->evP[2]);
+            trial->msRelax += elapsed(sh->evP[0], sh->evP[1]);
+            trial->msPost += elapsed(sh->evP[1], sh->evP[2]);
         }
     }
     return SHD_PE_OK;
 }
 
-static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x) {
+// The launches to use now: the plan's picks, or those of the tune's trial.
+static const BatchLaunch& relax_launch(const Shard* sh, const BatchTrial* trial) {
+    return trial ? trial->relax : sh->plan.relax;
+}
+static const BatchLaunch& post_launch(const Shard* sh, const BatchTrial* trial) {
+    return trial ? trial->post : sh->plan.post;
+}
+
+static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x,
+                         BatchTrial* trial) {
     ShdPeStats& st = sh->stats;
     int rc;
     if ((rc = ensure_batch(pe, sh))) return rc;
+    const BatchLaunch& relax = relax_launch(sh, trial);
     int32_t nB = 0;
-    const std::vector<int32_t> order = batch_order(pe, sh->bcfg.lb, pos, cnt, nB);
+    const std::vector<int32_t> order = batch_order(pe, relax.lb, pos, cnt, nB);
     HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
     if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
     if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
     HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
     HIPCHK(hipEventRecord(sh->evA, sh->stream));
-    // a workgroup indexes its scratch slot by blockIdx: never launch
-    // more workgroups than ensure_batch allocated slots for
-    BatchLaunch relax = sh->bcfg;
-    relax.grid = std::min(relax.grid, sh->batchSlots);
-    if (!sh->bcfg.split)
+    if (!relax.split)
         launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows, nB, sh->dBatchAmb, relax,
                           sh->dDbg, sh->dTie, sh->stream, 0);
-    else if ((rc = batch_rounds(pe, sh, relax, nB)))
+    else if ((rc = batch_rounds(pe, sh, relax, post_launch(sh, trial), nB, trial)))
         return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sh->evB, sh->stream));
@@ -1390,8 +1467,8 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     if (sh->dDbg) {
         std::vector<int32_t> dbg((size_t)nB * 16);
         HIPCHK(hipMemcpy(dbg.data(), sh->dDbg, dbg.size() * 4, hipMemcpyDeviceToHost));
-        print_batch_debug(pe, sh, dbg.data(), nB);
-        dump_batches(pe, order, dbg, nB, sh->bcfg.lb);
+        print_batch_debug(pe, sh, relax, dbg.data(), nB);
+        dump_batches(pe, order, dbg, nB, relax.lb);
     }
     return SHD_PE_OK;
 }
@@ -1420,8 +1497,10 @@ static int relax_sparse(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, E
     return SHD_PE_OK;
 }
 
-// One chunk's relax stage, by the shard's mode.
-static int relax_stage(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x) {
+// One chunk's relax stage, by the shard's mode.  (trial: shd_pe_tune's
+// launches for the batched kernel, null otherwise.)
+static int relax_stage(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x,
+                       BatchTrial* trial) {
     if (pe->mode == 2) return relax_direct(pe, sh, pos, cnt, x);
     if (pe->opt.forceMode == 3 || pe->hg.latFold) {
         // (latFold multigraphs: the reported latency is a fold of other
@@ -1431,7 +1510,7 @@ static int relax_stage(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, Ex
         return SHD_PE_OK;
     }
     if (pe->mode == 3) return relax_dense(pe, sh, pos, cnt, x);
-    if (pe->batched) return relax_batched(pe, sh, pos, cnt, x);
+    if (pe->batched) return relax_batched(pe, sh, pos, cnt, x, trial);
     return relax_sparse(pe, sh, pos, cnt, x);
 }
 
@@ -1600,7 +1679,8 @@ static int exact_stage(ShdPe* pe, Shard* sh, const ExactWork& x) {
 
 // Compute the given table positions (all owned by `sh`), chunked: per chunk
 // one relax stage and one exact stage.
-static int compute_shard(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t count) {
+static int compute_shard(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t count,
+                         BatchTrial* trial = nullptr) {
     if (count <= 0) return SHD_PE_OK;
     sh->pathSrc = -1;               // the exact kernels reuse slot 0
     if (hipSetDevice(sh->device) != hipSuccess) return SHD_PE_EHIP;
@@ -1614,7 +1694,7 @@ static int compute_shard(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t count
         HIPCHK(hipMemcpyAsync(sh->dRows, pos + c0, (size_t)cnt * 4, hipMemcpyHostToDevice,
                               sh->stream));
         x.clear();
-        if ((rc = relax_stage(pe, sh, pos + c0, cnt, x)) || (rc = exact_stage(pe, sh, x))) return rc;
+        if ((rc = relax_stage(pe, sh, pos + c0, cnt, x, trial)) || (rc = exact_stage(pe, sh, x))) return rc;
     }
     HIPCHK(hipEventRecord(sh->ev1, sh->stream));
     HIPCHK(hipEventSynchronize(sh->ev1));
@@ -1682,133 +1762,159 @@ extern "C" int shd_pe_compute_all(ShdPe* pe) {
     return shd_pe_compute_positions(pe, pe->ownStart, pe->ownEnd - pe->ownStart);
 }
 
+// ---- shd_pe_tune: time the plan's candidates, pick, try a narrower delta ------
+
+// What one candidate's timed compute gave.
+struct TuneSample {
+    double ms = 0.0;                 // batch kernels in all
+    double msRelax = 0.0, msPost = 0.0;   // split kernels: their parts
+    int64_t exact = 0;               // rows it sent to the exact path
+};
+
+// The tune's choice among the samples.
+struct TunePick {
+    int relax = 0, post = 0;         // candidate indices
+    bool perPart = false;            // picked per part (else one pick for both)
+    bool ok[4] = {false, false, false, false};   // candidates that competed
+};
+
+// One compute of the shard's rows with the trial's launches.
+static int tune_run(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, BatchTrial& t, TuneSample& s) {
+    const double m0 = sh->stats.msSparseKernel;
+    const int64_t x0 = sh->stats.rowsExact;
+    t.msRelax = t.msPost = 0.0;
+    const int rc = compute_shard(pe, sh, pos.data(), (int32_t)pos.size(), &t);
+    s = TuneSample{sh->stats.msSparseKernel - m0, t.msRelax, t.msPost, sh->stats.rowsExact - x0};
+    return rc;
+}
+
+// Times one candidate as both kernels' variant: a first launch maps its code
+// and scratch; the second is timed (split kernels: relax and post separately)
+static int tune_time(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, const BatchLaunch& c,
+                     TuneSample& s) {
+    BatchTrial t;
+    t.relax = t.post = c;
+    int rc = tune_run(pe, sh, pos, t, s);
+    if (rc) return rc;
+    t.timed = c.split != 0;
+    return tune_run(pe, sh, pos, t, s);
+}
+
+// The picks, from the candidates' samples alone.
+static TunePick tune_pick(const BatchLaunch* cand, const TuneSample* s, int nc) {
+    TunePick p;
+    // Every variant computes the same rows, so they all send the same
+    // rows to the exact path -- except one whose batches fail their
+    // checks (a miscompiled instantiation: round 6 found one whose post
+    // kernel failed every batch's Bellman check under one register
+    // allocation).  Such a variant looks FASTER here (its
+    // skipped phases are not in the batch-kernel time, the exact kernel
+    // is), so it is never picked: only candidates at the fewest exact
+    // rows compete.
+    int64_t exMin = s[0].exact;
+    for (int k = 1; k < nc; ++k) exMin = std::min(exMin, s[k].exact);
+    for (int k = 0; k < nc; ++k) p.ok[k] = s[k].exact == exMin;
+    // whole launches, or per part when every variant ran split: the
+    // relax kernel and the post kernel each take their fastest variant
+    p.perPart = true;
+    for (int k = 0; k < nc; ++k) p.perPart = p.perPart && cand[k].split && s[k].msRelax > 0.0;
+    int rk = 0;
+    while (!p.ok[rk]) ++rk;
+    int pk = rk;
+    for (int k = rk + 1; k < nc; ++k) {
+        if (!p.ok[k]) continue;
+        if (p.perPart ? s[k].msRelax < s[rk].msRelax : s[k].ms < s[rk].ms) rk = k;
+        if (p.perPart ? s[k].msPost < s[pk].msPost : s[k].ms < s[pk].ms) pk = k;
+    }
+    if (!p.perPart) pk = rk;
+    p.relax = rk;
+    p.post = pk;
+    return p;
+}
+
+// bucket width: the chosen relax variant at delta and at 0.8 x delta,
+// timed alternately (A B A B, each width's best run: best[0] at delta,
+// best[1] at 0.8 x), the narrower width kept only if its relax kernel is
+// faster by more than 1% on this shard -- the gain is 1-2% where it exists
+// (C4 same box: N=1 -1.2%, the N=8 shard's LB-8 batches -2%; C5 +1.2%, so
+// not a fixed default; profiles/r05_ab_notes.txt r05bg-bi), and a single run
+// against a measurement from another pass let noise pick the width.
+// The post kernel does not use delta.
+static int tune_delta(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, BatchLaunch& relax,
+                      const BatchLaunch& post, double best[2]) {
+    BatchLaunch alt = relax;
+    alt.delta = relax.delta * 0.8;
+    best[0] = best[1] = 0.0;
+    for (int rep = 0; rep < 4; ++rep) {
+        BatchTrial t;
+        t.relax = (rep & 1) ? alt : relax;
+        t.post = post;
+        t.timed = true;
+        TuneSample s;
+        const int rc = tune_run(pe, sh, pos, t, s);
+        if (rc) return rc;
+        double& b = best[rep & 1];
+        if (s.msRelax > 0.0 && (b == 0.0 || s.msRelax < b)) b = s.msRelax;
+    }
+    if (best[1] > 0.0 && best[0] > 0.0 && best[1] < 0.99 * best[0]) relax = alt;
+    return SHD_PE_OK;
+}
+
+static void tune_log(const Shard* sh, const TuneSample* s, const TunePick& p, const double best[2]) {
+    const BatchPlan& plan = sh->plan;
+    for (int k = 0; k < plan.nc; ++k)
+        std::fprintf(stderr, "[shdpe] shard %d tune: %d waves%s %.2f ms (relax %.2f post %.2f) exact rows %ld%s%s%s\n",
+                     sh->gindex, plan.cand[k].wpe, plan.cand[k].coop >= 2 ? " cooperative" : "", s[k].ms,
+                     s[k].msRelax, s[k].msPost, (long)s[k].exact, p.ok[k] ? "" : " (excluded)",
+                     k == p.relax ? " <relax" : "", k == p.post ? " <post" : "");
+    if (best[1] > 0.0)
+        std::fprintf(stderr, "[shdpe] shard %d tune: relax at 0.8 x delta %.2f ms vs %.2f -> delta %.3f\n",
+                     sh->gindex, best[1], best[0], plan.relax.delta);
+}
+
+// One shard's tune.  Its computes take their launches from trials, so the
+// plan changes only when all of them succeeded: a failing compute leaves the
+// shard as it was, the untuned picks included.
+static int tune_shard(ShdPe* pe, Shard* sh) {
+    // scratch first: ensure_batch sizes the slots and lowers the plan's
+    // grids to them, and the trials below are copies of those launches
+    if (hipSetDevice(sh->device) != hipSuccess) return SHD_PE_EHIP;
+    int rc = ensure_table(pe, sh);
+    if (!rc) rc = ensure_batch(pe, sh);
+    if (rc) return rc;
+    BatchPlan& plan = sh->plan;
+    std::vector<int32_t> pos(sh->rowCount);
+    for (int32_t i = 0; i < sh->rowCount; ++i) pos[i] = sh->rowStart + i;
+    const ShdPeStats keep = sh->stats;
+    TuneSample s[4];
+    for (int k = 0; k < plan.nc && !rc; ++k) rc = tune_time(pe, sh, pos, plan.cand[k], s[k]);
+    TunePick p;
+    BatchLaunch relax{};
+    double best[2] = {0.0, 0.0};
+    if (!rc) {
+        p = tune_pick(plan.cand, s, plan.nc);
+        relax = plan.cand[p.relax];
+        if (p.perPart) rc = tune_delta(pe, sh, pos, relax, plan.cand[p.post], best);
+    }
+    sh->stats = keep;               // the tune's computes are not the caller's
+    if (rc) return rc;
+    plan.relax = relax;
+    plan.post = p.post != p.relax ? plan.cand[p.post] : relax;
+    sh->tuned = true;
+    plan_stats(pe, sh);
+    if (pe->tu.debug || pe->tu.tuneLog) tune_log(sh, s, p, best);
+    return SHD_PE_OK;
+}
+
 extern "C" int shd_pe_tune(ShdPe* pe) {
     if (!pe) return SHD_PE_EINVAL;
     if (!pe->batched) return SHD_PE_OK;
     std::lock_guard<std::mutex> lk(pe->mu);
     for (auto& sp : pe->shards) {
         Shard* sh = sp.get();
-        if (sh->tuned || (sh->bcfgAlt.grid <= 0 && sh->bcfgAlt2.grid <= 0 && sh->bcfgCoop.grid <= 0) ||
-            sh->rowCount <= 0)
-            continue;
-        // scratch first: ensure_batch sizes the slots and lowers the live
-        // grids to them, and the candidates below are copies of those grids
-        if (hipSetDevice(sh->device) != hipSuccess) return SHD_PE_EHIP;
-        int rc0 = ensure_table(pe, sh);
-        if (!rc0) rc0 = ensure_batch(pe, sh);
-        if (rc0) return rc0;
-        std::vector<int32_t> pos(sh->rowCount);
-        for (int32_t i = 0; i < sh->rowCount; ++i) pos[i] = sh->rowStart + i;
-        const ShdPeStats keep = sh->stats;
-        double ms[4] = {0.0, 0.0, 0.0, 0.0}, part[4][2] = {{0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}, {0.0, 0.0}};
-        int w[4] = {0, 0, 0, 0};
-        int64_t ex[4] = {0, 0, 0, 0};   // rows each candidate sent to the exact path
-        BatchLaunch cand[4] = {sh->bcfg, sh->bcfgAlt, sh->bcfgAlt2, sh->bcfgCoop};
-        const BatchLaunch orig[3] = {sh->bcfg, sh->bcfgAlt, sh->bcfgAlt2};
-        // a failed compute: the shard as it was before the tune
-        auto fail = [&](int rc) {
-            sh->bcfg = orig[0]; sh->bcfgAlt = orig[1]; sh->bcfgAlt2 = orig[2];
-            sh->bcfgPost = BatchLaunch{};
-            sh->stats = keep;
-            return rc;
-        };
-        int nc = 1;
-        if (sh->bcfgAlt.grid > 0) cand[nc++] = sh->bcfgAlt;
-        if (sh->bcfgAlt2.grid > 0) cand[nc++] = sh->bcfgAlt2;
-        // the cooperative relax (its post part runs the plain kernel of the
-        // same variant, so it is timed as that variant's post)
-        if (sh->bcfgCoop.grid > 0 && sh->bcfg.coop < 2 && sh->bcfg.split) cand[nc++] = sh->bcfgCoop;
-        sh->bcfgPost = BatchLaunch{};
-        for (int k = 0; k < nc; ++k) {
-            sh->bcfg = cand[k];
-            w[k] = sh->bcfg.wpe;
-            // a first launch of each variant maps its code and scratch; the
-            // second is timed (split kernels: relax and post separately)
-            for (int rep = 0; rep < 2; ++rep) {
-                const double m0 = sh->stats.msSparseKernel;
-                const int64_t x0 = sh->stats.rowsExact;
-                sh->msPart[0] = sh->msPart[1] = 0.0;
-                sh->timeParts = rep == 1 && sh->bcfg.split;
-                int rc = compute_shard(pe, sh, pos.data(), sh->rowCount);
-                sh->timeParts = false;
-                if (rc) return fail(rc);
-                ms[k] = sh->stats.msSparseKernel - m0;
-                part[k][0] = sh->msPart[0];
-                part[k][1] = sh->msPart[1];
-                ex[k] = sh->stats.rowsExact - x0;
-            }
-        }
-        // Every variant computes the same rows, so they all send the same
-        // rows to the exact path -- except one whose batches fail their
-        // checks (a miscompiled instantiation: round 6 found one whose post
-        // kernel failed every batch's Bellman check under one register
-        // allocation).  Such a variant looks FASTER here (its
-        // skipped phases are not in the batch-kernel time, the exact kernel
-        // is), so it is never picked: only candidates at the fewest exact
-        // rows compete.
-        int64_t exMin = ex[0];
-        for (int k = 1; k < nc; ++k) exMin = std::min(exMin, ex[k]);
-        bool ok[4] = {false, false, false, false};
-        for (int k = 0; k < nc; ++k) ok[k] = ex[k] == exMin;
-        // whole launches, or per part when every variant ran split: the
-        // relax kernel and the post kernel each take their fastest variant
-        bool perPart = true;
-        for (int k = 0; k < nc; ++k) perPart = perPart && cand[k].split && part[k][0] > 0.0;
-        int rk = 0;
-        while (!ok[rk]) ++rk;
-        int pk = rk;
-        for (int k = rk + 1; k < nc; ++k) {
-            if (!ok[k]) continue;
-            if (perPart ? part[k][0] < part[rk][0] : ms[k] < ms[rk]) rk = k;
-            if (perPart ? part[k][1] < part[pk][1] : ms[k] < ms[pk]) pk = k;
-        }
-        if (!perPart) pk = rk;
-        // bucket width: the chosen relax variant at delta and at 0.8 x delta,
-        // timed alternately (A B A B, each width's best run), the narrower
-        // width kept only if its relax kernel is faster by more than 1% on
-        // this shard -- the gain is 1-2% where it exists (C4 same box: N=1
-        // -1.2%, the N=8 shard's LB-8 batches -2%; C5 +1.2%, so not a fixed
-        // default; profiles/r05_ab_notes.txt r05bg-bi), and a single run
-        // against a measurement from another pass let noise pick the width.
-        // The post kernel does not use delta.
-        BatchLaunch relaxPick = cand[rk];
-        double relaxAlt = 0.0, relaxBase = 0.0;
-        if (perPart) {
-            BatchLaunch alt = cand[rk];
-            alt.delta = cand[rk].delta * 0.8;
-            sh->bcfgPost = cand[pk];
-            double best[2] = {0.0, 0.0};
-            for (int rep = 0; rep < 4; ++rep) {
-                sh->bcfg = (rep & 1) ? alt : cand[rk];
-                sh->msPart[0] = sh->msPart[1] = 0.0;
-                sh->timeParts = true;
-                const int rc = compute_shard(pe, sh, pos.data(), sh->rowCount);
-                sh->timeParts = false;
-                if (rc) return fail(rc);
-                double& b = best[rep & 1];
-                if (sh->msPart[0] > 0.0 && (b == 0.0 || sh->msPart[0] < b)) b = sh->msPart[0];
-            }
-            relaxBase = best[0];
-            relaxAlt = best[1];
-            if (relaxAlt > 0.0 && relaxBase > 0.0 && relaxAlt < 0.99 * relaxBase) relaxPick = alt;
-            sh->bcfgPost = BatchLaunch{};
-        }
-        sh->bcfg = relaxPick;
-        if (pk != rk) sh->bcfgPost = cand[pk];
-        sh->tuned = true;
-        sh->stats = keep;
-        sh->stats.deltaUsed = relaxPick.delta;
-        sh->stats.batchWaves = sh->bcfg.wpe;
-        sh->stats.batchPostWaves = sh->bcfg.split ? cand[pk].wpe : 0;
-        if (pe->tu.debug || pe->tu.tuneLog)
-            for (int k = 0; k < nc; ++k)
-                std::fprintf(stderr, "[shdpe] shard %d tune: %d waves%s %.2f ms (relax %.2f post %.2f) exact rows %ld%s%s%s\n",
-                             sh->gindex, w[k], cand[k].coop >= 2 ? " cooperative" : "", ms[k], part[k][0],
-                             part[k][1], (long)ex[k], ok[k] ? "" : " (excluded)", k == rk ? " <relax" : "",
-                             k == pk ? " <post" : "");
-        if ((pe->tu.debug || pe->tu.tuneLog) && relaxAlt > 0.0)
-            std::fprintf(stderr, "[shdpe] shard %d tune: relax at 0.8 x delta %.2f ms vs %.2f -> delta %.3f\n",
-                         sh->gindex, relaxAlt, relaxBase, relaxPick.delta);
+        if (sh->tuned || !sh->plan.tunable() || sh->rowCount <= 0) continue;
+        const int rc = tune_shard(pe, sh);
+        if (rc) return rc;
     }
     return SHD_PE_OK;
 }
@@ -2720,7 +2826,7 @@ extern "C" int shd_pe_get_stats(const ShdPe* pe, ShdPeStats* out) {
     std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
     for (auto& sp : pe->shards) {                // live per-shard counters into the stats
         sp->stats.relaxCoopAborts = sp->coopAborts;
-        sp->stats.batchCoop = sp->bcfg.coop >= 2 ? sp->bcfg.coop : 0;
+        sp->stats.batchCoop = sp->plan.relax.coop >= 2 ? sp->plan.relax.coop : 0;
     }
     ShdPeStats t = pe->shards[0]->stats;
     for (size_t i = 1; i < pe->shards.size(); ++i) {

@@ -737,6 +737,37 @@ def test_tune_never_picks_a_failing_variant(E, oracle_mod, monkeypatch, wpe):
     eng.close()
 
 
+def test_untuned_variant_picks(E, oracle_mod, monkeypatch):
+    """The picks an engine starts with before any tune (the drop-in computes
+    once): the 4-wave relax, and for the post kernel 6 waves with batches of
+    16, 4 with batches of 8.  1,200 rows are 75 batches of 16, fewer than the
+    device's CUs, so the engine takes LB 8 by itself; SHDPE_BATCH_LB=16 shows
+    the other pick.  Rows computed with those picks are bit-exact."""
+    top = G.power_law(8000, m=3, seed=14)
+    att = G.sample_attached(top.n, 1200, seed=3)
+    og = oracle_mod.OracleGraph(top)
+    exp = pos = None
+    for lb, waves, post in ((8, 4, 4), (16, 4, 6)):
+        if lb == 16:
+            monkeypatch.setenv("SHDPE_BATCH_LB", "16")
+        eng = E.Engine(top, att, force_mode=5, debug_flags=E.DEBUG_ENV)
+        st = eng.stats()
+        print(f"LB {st['batchLanes']}: relax {st['batchWaves']} waves, post {st['batchPostWaves']}")
+        assert st["batched"] == 1 and st["batchLanes"] == lb, st
+        assert st["batchWaves"] == waves and st["batchPostWaves"] == post, st
+        eng.compute_all()
+        st = eng.stats()
+        assert st["rowsExact"] == 0, st
+        assert st["batchWaves"] == waves and st["batchPostWaves"] == post, st
+        if exp is None:
+            pos = np.arange(0, eng.T, 37)
+            exp = og.rows(eng.attached[pos], eng.attached, threads=8)
+        for i, p in enumerate(pos):
+            got = {k: (v[0] if v is not None else None) for k, v in eng.get_rows(int(p), 1).items()}
+            _assert_rows_equal(got, {k: v[i] for k, v in exp.items()}, f"LB {lb} row {p}")
+        eng.close()
+
+
 @pytest.mark.parametrize("wpe", [4, 6, 8])
 @pytest.mark.parametrize("case", ["power_law", "quantized"])
 def test_batched_kernel_each_variant(E, oracle_mod, monkeypatch, wpe, case):
