@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 5   /* 5: batched host attachment (shd_pe_attach_*) */
+#define SHD_PE_ABI_VERSION 6   /* 6: batched path extraction (shd_pe_get_paths) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -229,6 +229,76 @@ int shd_pe_get_rows(ShdPe* pe, int32_t start, int32_t count, double* lat, double
  * the path needs more than cap entries. */
 int shd_pe_get_path(ShdPe* pe, int32_t srcVertex, int32_t dstVertex, int32_t* verts,
                     int32_t cap, int32_t* len);
+
+/* shd_pe_get_path for `count` (src[i], dst[i]) pairs in one call: what
+ * topology.c:1831-1841 logs on every first miss of a source, collected per
+ * row.  Path i is exactly what shd_pe_get_path(src[i], dst[i]) returns
+ * (src == dst -> [src]; complete graph -> [src, dst]; else igraph's path, ties
+ * decided by its heap) and occupies entries [offsets[i], offsets[i+1]) of
+ * verts / hopLat / hopRel.  Entry k > 0 of a path carries the latency and
+ * 1 - packetloss of the edge verts[k-1] -> verts[k] as _topology_getEdgeHelper
+ * returns them for igraph_get_eid's edge (the newest of parallel edges, the one
+ * the row's fold used); entry 0 carries 0.0.
+ *
+ * A request that shd_pe_get_path would refuse does not fail the call: its
+ * code goes to status[i] (SHD_PE_EINVAL for an id out of range,
+ * SHD_PE_ENOTATTACHED, SHD_PE_ENOEDGE, SHD_PE_ENOTOWNED, SHD_PE_EUNREACHABLE)
+ * and its path is empty.  The codes are tested in shd_pe_get_path's order:
+ * range, attachment, then src == dst, which is [src] with status 0 whoever
+ * owns the row (it needs none; so a sharded, ungathered engine answers
+ * SHD_PE_ENOTOWNED for a foreign source only where src != dst), then the
+ * complete graph's edge, the owner, and the table's flags.
+ * Lengths come from the table alone (hops + 1 for a
+ * reachable src != dst); rows not yet computed are computed first, as in
+ * shd_pe_get_rows.
+ *
+ * offsets (count + 1 entries, required) is always filled completely.
+ * verts == NULL is the sizing call: nothing else is written, no Dijkstra is
+ * re-run, the call returns 0.  offsets[count] > cap: SHD_PE_EINVAL with
+ * offsets (and status) still valid.  Otherwise every non-NULL array is filled,
+ * per owning shard in three tiers:
+ *  - batch tier (the batched multi-source path with split kernels, the large
+ *    sparse graphs' default): one relax + post pass over the unique requested
+ *    sources, which stores no table row; after each round the requests whose
+ *    source sits in it are walked over the round's persisted distance arrays,
+ *    parent by parent as the post kernel derives them (the tight in-arc of
+ *    minimum distance).  A request whose walk meets equal minima is handed on;
+ *  - tie tier: the rows that pass gives a tie slot (early-stop tie rows) run
+ *    the exact stage's relevance scan and early-stop emulation, which leave
+ *    the row's final parents in its slot, and their requests are walked over
+ *    those.  A slot that fails the emulation's consistency check, and a walk
+ *    that does not arrive at its source, are handed on;
+ *  - grouped emulation (every mode; what shd_pe_get_path does, wide): igraph's
+ *    Dijkstra on the device (the exact heap emulation) for the remaining
+ *    unique sources -- rows the pass sends to the full emulation, sources of
+ *    requests handed on, and every source where the first two tiers do not
+ *    apply -- in groups of one row per resident workgroup, one walk launch
+ *    per group over all its requests.
+ * Only the grouped emulation stores table rows: the values they hold already,
+ * with SHD_PE_F_EXACT on every entry until the row's saved flag bytes are put
+ * back right after the group's launch.  That flag bit of such a row is the
+ * one thing a concurrent shd_pe_get_row(s) can see differ during the call; no
+ * other table byte, no computed-row flag and no ShdPeStats field changes.
+ * Takes the compute lock. */
+typedef struct ShdPePathsOut {      /* any pointer but offsets may be NULL */
+    int64_t* offsets;   /* count + 1: path i occupies [offsets[i], offsets[i+1]) */
+    int32_t* verts;     /* [src, ..., dst] in the caller's vertex ids          */
+    double*  hopLat;    /* same indexing; entry k > 0 of a path = the edge verts[k-1] -> verts[k]; */
+    double*  hopRel;    /*   entry 0 of every path = 0.0                        */
+    int32_t* status;    /* count: 0 or the SHD_PE_E* code of request i          */
+    int64_t  cap;       /* entries available in verts / hopLat / hopRel         */
+} ShdPePathsOut;
+int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* dst, int64_t count,
+                     const ShdPePathsOut* out);
+/* Of the last shd_pe_get_paths call (ShdPeStats is not touched), the first
+ * min(n, 6) of: info[0] unique sources served wholly by the batch tier,
+ * info[1] unique sources served wholly from early-stop tie parents (the tie
+ * tier), info[2] unique sources served by the grouped full emulation (each
+ * unique source with a walk counts in exactly one of the three), info[3]
+ * requests that left the batch or the tie tier after its check and were
+ * finished by the emulation, info[4] emulation groups launched, info[5]
+ * device time of the call from events, in integer microseconds. */
+int shd_pe_paths_info(const ShdPe* pe, int64_t* info, int32_t n);
 
 /* Page-locked host memory for shd_pe_get_rows destinations (DMA target, no
  * staging copy).  No reference counterpart: Shadow's row buffers are plain

@@ -488,3 +488,211 @@ void launch_rows_all_success(const DevTable& tab, int32_t* dOut, void* stream) {
 }
 
 }  // namespace shdpe
+
+namespace shdpe {
+
+// ---------------------------------------------------------------------------
+// Batched path extraction (shd_pe_get_paths): the igraph paths behind many
+// table entries in one call, topology.c:1449 / :1502-1503 / :1831-1841 for
+// every (src, dst) of a batch instead of one shd_pe_get_path each.
+//
+//   k_paths_size   per request: validity, attachment, owner and the table's
+//                  flags / hops -> path length and SHD_PE_E* status
+//   k_paths_scan   exclusive scan of the lengths -> output offsets
+//   k_paths_flags  saves / restores the flag bytes of the rows an emulation
+//                  group rewrites (the emulation marks every entry F_EXACT)
+//   k_paths_walk   per request: len - 1 parent steps from dst, each vertex
+//                  written straight to its final place; arrival at src checked
+//   k_paths_hops   per output entry: the hop's edge (igraph_get_eid: the
+//                  newest parallel edge) -> latency and 1 - packetloss
+//
+// The walk is a chain of dependent 4-B loads (parent arc, then its tail), so
+// one thread serves one request and the parallelism is across requests; the
+// host orders a launch's requests by source, so neighbouring lanes read the
+// same parent array.  The hop attributes have no such chain: one thread per
+// output entry, coalesced stores.
+// ---------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void k_paths_size(DevGraph g0, DevTable tab0, PathsSizeArgs p) {
+    const DevGraph g = global_view(g0);
+    const DevTable tab = global_view(tab0);
+    const int32_t* __restrict__ posOf = as_global(p.posOf);
+    const int32_t i = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (i >= p.count) return;
+    int32_t* __restrict__ len = as_global(p.len);
+    int32_t* __restrict__ stat = as_global(p.stat);
+    const int s = as_global(p.src)[i], t = as_global(p.dst)[i];
+    // outcomes that need no table row: decided by the primary shard
+    int st = SHD_PE_OK, L = 0;
+    bool table = false;
+    int ps = -1, pt = -1;
+    if (s < 0 || s >= g.n || t < 0 || t >= g.n) {
+        st = SHD_PE_EINVAL;
+    } else if ((ps = posOf[s]) < 0 || (pt = posOf[t]) < 0) {
+        st = SHD_PE_ENOTATTACHED;
+    } else if (s == t) {
+        L = 1;                                   // the 1-vertex igraph path [s]
+    } else if (p.complete) {                     // _topology_lookupDirectPath: the edge itself
+        int a = -1;
+        if (find_arc(g, s, t, &a)) L = 2;
+        else st = SHD_PE_ENOEDGE;
+    } else if (ps < p.ownLo || ps >= p.ownHi) {
+        st = SHD_PE_ENOTOWNED;
+    } else {
+        table = true;
+    }
+    if (!table) {
+        if (p.primary) { len[i] = L; stat[i] = st; }
+        return;
+    }
+    if (ps < p.rowLo || ps >= p.rowHi) return;   // another shard's row: that shard answers
+    const size_t cell = (size_t)(ps - tab.rowStart) * (size_t)tab.T + (size_t)pt;
+    const uint8_t f = tab.flags[cell];
+    if (f & F_UNREACHABLE) st = SHD_PE_EUNREACHABLE;
+    else if (f & F_NOEDGE) st = SHD_PE_ENOEDGE;
+    else {
+        const int h = tab.hops[cell];
+        if (h >= 1 && h < g.n) L = h + 1;
+        else st = SHD_PE_EHIP;                   // (not a table this engine wrote)
+    }
+    len[i] = L;
+    stat[i] = st;
+}
+
+// One workgroup: off[i] = sum of len[0 .. i), off[count] = the total.
+__global__ __launch_bounds__(1024) void k_paths_scan(const int32_t* __restrict__ len, int32_t count,
+                                                     int64_t* __restrict__ off) {
+    __shared__ long long wsum[16];
+    __shared__ long long carry;
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+    if (tid == 0) carry = 0;
+    __syncthreads();
+    for (int32_t base = 0; base < count; base += 1024) {
+        const int32_t i = base + tid;
+        const long long v = i < count ? (long long)len[i] : 0;
+        long long x = v;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const long long y = __shfl_up(x, o, 64);
+            if (lane >= o) x += y;
+        }
+        if (lane == 63) wsum[w] = x;
+        __syncthreads();
+        long long pre = carry;
+        for (int k = 0; k < w; ++k) pre += wsum[k];
+        if (i < count) off[i] = pre + x - v;
+        __syncthreads();
+        if (tid == 1023) carry = pre + x;
+        __syncthreads();
+    }
+    if (tid == 0) off[count] = carry;
+}
+
+// One workgroup per row: the row's T flag bytes to buf (restore == 0) or back.
+__global__ __launch_bounds__(256) void k_paths_flags(DevTable tab0, const int32_t* __restrict__ rows,
+                                                     uint8_t* __restrict__ buf, int restore) {
+    const DevTable tab = global_view(tab0);
+    const int64_t T = tab.T;
+    uint8_t* row = tab.flags + (size_t)(rows[blockIdx.x] - tab.rowStart) * (size_t)T;
+    uint8_t* sav = buf + (size_t)blockIdx.x * (size_t)T;
+    for (int64_t j = threadIdx.x; j < T; j += 256) {
+        if (restore) row[j] = sav[j];
+        else sav[j] = row[j];
+    }
+}
+
+__global__ __launch_bounds__(256) void k_paths_walk(DevGraph g0, PathsWalkArgs p) {
+    const DevGraph g = global_view(g0);
+    const int32_t j = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (j >= p.nReqs) return;
+    const PathReq q = as_global(p.reqs)[j];
+    const int32_t L = as_global(p.len)[q.req];
+    int32_t* __restrict__ out = as_global(p.verts) + as_global(p.off)[q.req];
+    if (L <= 0) return;
+    if (q.slot < 0) {                            // [s] or, complete graph, [s, t]: caller's ids
+        out[0] = q.s;
+        if (L > 1) out[1] = q.t;
+        return;
+    }
+    const int32_t* __restrict__ P = as_global(p.parents) + (size_t)q.slot * (size_t)p.stride;
+    int v = q.t;
+    bool ok = true;
+    for (int32_t k = L - 1; k >= 1; --k) {
+        out[k] = g.oldId ? g.oldId[v] : v;
+        const int a = P[v];
+        if (a < 0 || (a & ~TIE_AMB) >= p.nInArcs) { ok = false; break; }
+        v = g.inCol[a & ~TIE_AMB];
+        if (v < 0 || v >= g.n) { ok = false; break; }
+    }
+    if (ok && v == q.s) {
+        out[0] = g.oldId ? g.oldId[v] : v;
+    } else {                                     // not this source's parents: never reported as a path
+        as_global(p.failed)[q.req] = 1;
+        atomicAdd(as_global(p.nFailed), 1);
+    }
+}
+
+__global__ __launch_bounds__(256) void k_paths_hops(DevGraph g0, const int64_t* __restrict__ off,
+                                                    int32_t count, const int32_t* __restrict__ verts,
+                                                    double* __restrict__ hopLat,
+                                                    double* __restrict__ hopRel,
+                                                    int32_t* __restrict__ nFailed) {
+    const DevGraph g = global_view(g0);
+    const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= off[count]) return;
+    // the request whose path holds entry e: the last i with off[i] <= e
+    // (empty paths share their successor's offset and are never chosen)
+    int32_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= e) lo = mid;
+        else hi = mid;
+    }
+    double L = 0.0, R = 0.0;
+    if (e > off[lo]) {
+        const int u = verts[e - 1], v = verts[e];
+        int a = -1;
+        if (u >= 0 && u < g.n && v >= 0 && v < g.n && u != v && find_arc(g, u, v, &a)) {
+            L = g.flat ? g.flat[a] : g.lat[a];   // igraph_get_eid: the newest parallel edge
+            R = g.rel[a];
+        } else {
+            atomicAdd(nFailed, 1);
+        }
+    }
+    if (hopLat) hopLat[e] = L;
+    if (hopRel) hopRel[e] = R;
+}
+
+void launch_paths_size(const DevGraph& gAux, const DevTable& tab, const PathsSizeArgs& a, void* stream) {
+    if (a.count <= 0) return;
+    hipLaunchKernelGGL(k_paths_size, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), gAux, tab, a);
+}
+
+void launch_paths_scan(const int32_t* dLen, int32_t count, int64_t* dOff, void* stream) {
+    hipLaunchKernelGGL(k_paths_scan, dim3(1), dim3(1024), 0, reinterpret_cast<hipStream_t>(stream), dLen,
+                       count, dOff);
+}
+
+void launch_paths_flags(const DevTable& tab, const int32_t* dRows, int32_t nRows, uint8_t* dBuf,
+                        bool restore, void* stream) {
+    if (nRows <= 0) return;
+    hipLaunchKernelGGL(k_paths_flags, dim3(nRows), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       tab, dRows, dBuf, restore ? 1 : 0);
+}
+
+void launch_paths_walk(const DevGraph& g, const PathsWalkArgs& a, void* stream) {
+    if (a.nReqs <= 0) return;
+    hipLaunchKernelGGL(k_paths_walk, dim3((unsigned)((a.nReqs + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), g, a);
+}
+
+void launch_paths_hops(const DevGraph& gAux, const int64_t* dOff, int32_t count, int64_t entries,
+                       const int32_t* dVerts, double* dHopLat, double* dHopRel, int32_t* dNFailed,
+                       void* stream) {
+    if (entries <= 0) return;
+    hipLaunchKernelGGL(k_paths_hops, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), gAux, dOff, count, dVerts, dHopLat, dHopRel,
+                       dNFailed);
+}
+
+}  // namespace shdpe

@@ -358,7 +358,10 @@ __device__ __noinline__ double fold_rel_batch(const double* __restrict__ vrel,
 // them (slot = batch index): PART 1 relaxes, PART 2 derives predecessors ON
 // DEMAND (only vertices on some target's path in some lane; the full pass only
 // for tie rows and trees too deep for the walks), labels, rows and the tie
-// export -- each with its own register budget.
+// export -- each with its own register budget.  PART 4: PART 2 without the row
+// writer's stores (the pass of shd_pe_get_paths, which wants the round's
+// distances, ambiguity bytes and tie export only): its own instantiation, so
+// the post kernel keeps its code.
 template <int LB, int WPE, bool GB, int PART>
 __global__ __launch_bounds__(BT_THREADS) __attribute__((amdgpu_waves_per_eu(WPE)))
 void k_batch_rows(DevGraph g0, DevTable tab0,
@@ -370,7 +373,8 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
     // PART 3: the relax (PART 1) shared by K workgroups per batch -- its own
     // instantiation, so the plain relax keeps its code and register budget
     constexpr bool CO = PART == 3;
-    constexpr int PT = CO ? 1 : PART;
+    constexpr bool NOTAB = PART == 4;
+    constexpr int PT = CO ? 1 : NOTAB ? 2 : PART;
     constexpr int BV = BCfg<WPE>::BV;
     constexpr int SMAX = BCfg<WPE>::SMAX;
     // the light-vertex relax loop and the predecessor pass are software-
@@ -1421,7 +1425,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
             int32_t* const tPred = tHop + 2 * NT;
             uint8_t* const tFlg = reinterpret_cast<uint8_t*>(tPred + 2 * NT);
             const int wl = tid / NG, wc = tid % NG;     // writer: lane (row), column in block
-            const int wrow = laneRow[wl];
+            const int wrow = NOTAB ? -1 : laneRow[wl];
             const size_t wbase = (size_t)(wrow >= 0 ? wrow - tab.rowStart : 0) * (size_t)tab.T;
             __syncthreads();                            // walks done: stacks free
             // WQ targets per group per block, their loads issued branch-free
@@ -1731,6 +1735,67 @@ void launch_tie_export(const DevGraph& g, const BatchScratch& bs, int lb, const 
         hipLaunchKernelGGL(k_tie_export<16>, dim3(grid), dim3(256), 0, st, g, bs, tie, round, dRowAmbig, violSlot);
 }
 
+// k_paths_walk_dist (shd_pe_get_paths, launch_paths_walk_dist): the paths of
+// requests whose source sits in a round of the split kernels, walked over the
+// round's persisted distance arrays after its post kernel (the labels L are
+// per workgroup and reused by the workgroup's next batch; the distances are
+// per batch).  One thread per request, len - 1 steps from the destination: at
+// each vertex the parent exactly as the post kernel's predecessor pass and
+// k_tie_export derive it -- the tight in-arc with minimum dist[u] -- and
+// nothing else: equal minima, a zero-increment arc, a Bellman violation at the
+// vertex, a lane the post kernel flagged (rowAmbig: a tie row, a failed batch)
+// or a walk that does not end on the source at distance 0 hands the request on
+// (failed[req] = 1; the grouped emulation serves it).
+__global__ __launch_bounds__(256) void k_paths_walk_dist(DevGraph g0, BatchScratch bs, PathsDistArgs p) {
+    const DevGraph g = global_view(g0);
+    const int32_t j = (int32_t)(blockIdx.x * 256 + threadIdx.x);
+    if (j >= p.nReqs) return;
+    const PathReq q = as_global(p.reqs)[j];
+    const int32_t L = as_global(p.len)[q.req];
+    if (L <= 0) return;
+    uint8_t* failed = as_global(p.failed);
+    const int slot = q.slot - p.slotBase;
+    if (as_global(p.rowAmbig)[slot] != 0) { failed[q.req] = 1; return; }
+    const int LB = p.lb;
+    const int b = slot / LB, l = slot % LB;
+    const unsigned long long* __restrict__ D = as_global(bs.D) + (size_t)b * ((size_t)bs.nStride * LB);
+    int32_t* __restrict__ out = as_global(p.verts) + as_global(p.off)[q.req];
+    const bool undirected = g.inCol == g.col;
+    int v = q.t;
+    unsigned long long dv = dec(D[(size_t)v * LB + l]);
+    bool ok = dv != INF_BITS;
+    for (int32_t k = L - 1; k >= 1 && ok; --k) {
+        out[k] = g.oldId ? g.oldId[v] : v;
+        const int a0 = undirected ? g.rowPtr[v] : g.inPtr[v];
+        const int a1 = undirected ? g.rowPtr[v + 1] : g.inPtr[v + 1];
+        unsigned long long best = INF_BITS, mn = INF_BITS;
+        int cnt = 0, bu = -1;
+        for (int a = a0; a < a1; ++a) {
+            const int u = undirected ? g.col[a] : g.inCol[a];
+            const double w = undirected ? g.lat[a] : g.inLat[a];
+            const unsigned long long du = dec(D[(size_t)u * LB + l]);
+            const double cand = b2d(du) + w;
+            const unsigned long long cb = d2b(cand);
+            mn = cb < mn ? cb : mn;
+            if (du <= dv && cand == b2d(dv)) {
+                if (du < best) { best = du; cnt = 1; bu = u; }
+                else if (du == best) ++cnt;
+            }
+        }
+        if (mn < dv || cnt != 1 || best == dv) { ok = false; break; }
+        v = bu;
+        dv = best;
+    }
+    if (ok && v == q.s && dv == 0ull) out[0] = g.oldId ? g.oldId[v] : v;
+    else failed[q.req] = 1;
+}
+
+void launch_paths_walk_dist(const DevGraph& g, const BatchScratch& bs, const PathsDistArgs& a, void* stream) {
+    if (a.nReqs <= 0) return;
+    hipLaunchKernelGGL(k_paths_walk_dist, dim3((unsigned)((a.nReqs + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), g, bs, a);
+}
+
 template <int LB, int WPE, bool GB, int PART>
 static void launch_lb(const DevGraph& g, const DevTable& tab, const BatchScratch& bs,
                       const int32_t* dBatchRows, int32_t nBatches, uint8_t* dRowAmbig,
@@ -1856,6 +1921,7 @@ static void launch_wp(const DevGraph& g, const DevTable& tab, const BatchScratch
                       int part) {
     if (part == 1) launch_w<WPE, 1>(g, tab, bs, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid);
     else if (part == 2) launch_w<WPE, 2>(g, tab, bs, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid);
+    else if (part == 4) launch_w<WPE, 4>(g, tab, bs, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid);
     else launch_w<WPE, 0>(g, tab, bs, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid);
 }
 

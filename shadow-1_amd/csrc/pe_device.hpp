@@ -99,6 +99,9 @@ struct Tuning {
     int batchCoopWpe = 0;      // its variant (8 / 6 / 4 waves; 0 = the one with two
                                // workgroups per CU)
     int coopSpin = 1 << 22;    // its barrier poll limit (tests shrink it to force aborts)
+    int pathsGroup = 0;        // shd_pe_get_paths: sources per emulation group (0: exactGrid)
+    int pathsChunk = 0;        // ... requests per staging chunk (0: 65,536)
+    int pathsFast = 1;         // ... 0: no batch / tie tier, every source by the grouped emulation
     int failWpe = 0;           // tests only: the relax variant of this wave count flags
                                // every batch failed (a miscompiled variant; shd_pe_tune
                                // must not pick it)
@@ -262,7 +265,7 @@ void launch_path_walk(const DevGraph& g, const int32_t* dP, int32_t s, int32_t t
 void launch_batch_rows(const DevGraph& g, const DevTable& tab, const BatchScratch& bs,
                        const int32_t* dBatchRows, int32_t nBatches, uint8_t* dRowAmbig,
                        const BatchLaunch& cfg, int32_t* dDbg, const TieBuf* dTie, void* stream,
-                       int part = 0);
+                       int part = 0);   // (part 4: the post kernel, part 2, storing no table row)
 const void* batch_kernel_ptr(int lb, int wpe, bool gbits, int part = 0);
 // cooperative relax (PART 3; LB 8 / 16, LDS bitmaps): 0 launched, -1 refused
 // (grid not resident / unsupported shape: run launch_batch_rows part 1)
@@ -307,6 +310,63 @@ void launch_rows_all_success(const DevTable& tab, int32_t* dOut, void* stream);
 // 64-bit fingerprint per table row (local rows firstLocal .. + rows), pe_aux.hip
 void launch_row_checksums(const DevTable& tab, int64_t firstLocal, int32_t rows, uint64_t* dOut,
                           void* stream);
+// batched path extraction (pe_aux.hip, shd_pe_get_paths); requests are staged
+// in chunks of `count`, every array below indexed by the request's place in
+// its chunk
+struct PathsSizeArgs {
+    const int32_t* src;      // [count] caller's vertex ids
+    const int32_t* dst;
+    int32_t count;
+    const int32_t* posOf;    // [n] caller's vertex id -> table position or -1
+    int32_t ownLo, ownHi;    // table positions this engine owns (else SHD_PE_ENOTOWNED)
+    int32_t rowLo, rowHi;    // ... and this shard: it answers the requests that need one of its rows
+    int32_t primary;         // 1: this shard also answers the requests that need no table row
+    int32_t complete;        // mode 2: a path is the direct edge
+    int32_t* len;            // [count] vertices of the path, 0 with a status (written where this
+    int32_t* stat;           // [count]   shard answers; the host presets len 0, stat INT32_MIN)
+};
+struct PathReq {
+    int32_t req;             // request (place in its chunk)
+    int32_t slot;            // parent array of its source; -1: [s] or [s, t] as given
+    int32_t s, t;            // slot >= 0: DEVICE ids of source and destination; else the caller's
+};
+struct PathsWalkArgs {
+    const PathReq* reqs;
+    int32_t nReqs;
+    const int32_t* parents;  // [slot][stride] IN-arc of the chosen parent (TIE_AMB masked off)
+    int64_t stride;
+    int32_t nInArcs;
+    const int32_t* len;      // [count]
+    const int64_t* off;      // [count + 1] from launch_paths_scan
+    int32_t* verts;          // [off[count]] caller's ids, path i at off[i]: [src, ..., dst]
+    uint8_t* failed;         // [count] 1: the walk did not arrive at src (nothing of it is a path)
+    int32_t* nFailed;
+};
+// the same walk over one round's persisted distance arrays of the split batch
+// kernels (pe_batch.hip): PathReq::slot - slotBase = batch within the round * lb + lane
+struct PathsDistArgs {
+    const PathReq* reqs;
+    int32_t nReqs;
+    int32_t lb;
+    int32_t slotBase;        // the round's first batch * lb
+    const uint8_t* rowAmbig; // the round's [batches * lb] ambiguity bytes (non-zero: handed on)
+    const int32_t* len;
+    const int64_t* off;
+    int32_t* verts;
+    uint8_t* failed;         // [count] 1: handed on to the emulation
+};
+void launch_paths_walk_dist(const DevGraph& g, const BatchScratch& bs, const PathsDistArgs& a, void* stream);
+void launch_paths_size(const DevGraph& gAux, const DevTable& tab, const PathsSizeArgs& a, void* stream);
+void launch_paths_scan(const int32_t* dLen, int32_t count, int64_t* dOff, void* stream);
+// the flag bytes of table rows dRows[0, nRows) to dBuf (nRows x T) or back
+void launch_paths_flags(const DevTable& tab, const int32_t* dRows, int32_t nRows, uint8_t* dBuf,
+                        bool restore, void* stream);
+void launch_paths_walk(const DevGraph& g, const PathsWalkArgs& a, void* stream);
+// per output entry the latency and 1 - packetloss of the edge into it (entry
+// 0 of a path: 0.0); gAux / dVerts in the caller's ids; either output may be null
+void launch_paths_hops(const DevGraph& gAux, const int64_t* dOff, int32_t count, int64_t entries,
+                       const int32_t* dVerts, double* dHopLat, double* dHopRel, int32_t* dNFailed,
+                       void* stream);
 // dense path (pe_dense.hip)
 void launch_dense_build(const DevGraph& g, double* W, double* Rl, int64_t n, int64_t nArcs,
                         void* stream);

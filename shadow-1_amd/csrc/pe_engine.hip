@@ -26,6 +26,7 @@
 #include <cstdlib>
 #include <cstdio>
 #include <cstring>
+#include <functional>
 #include <memory>
 #include <mutex>
 #include <new>
@@ -62,9 +63,13 @@ struct BatchPlan {
 // One timed run of shd_pe_tune: the launches to use instead of the plan's
 // picks, and what the split kernels' relax / post parts took (summed over
 // the rounds; 0 when not split).
+// Serves two callers: shd_pe_tune's timed trials (timed, msRelax / msPost) and
+// the batch tier of shd_pe_get_paths (noTable), both through relax_batched /
+// batch_rounds; a plain compute passes no trial.
 struct BatchTrial {
     BatchLaunch relax{}, post{};
     bool timed = false;
+    bool noTable = false;           // shd_pe_get_paths: the post kernel stores no table row
     double msRelax = 0.0, msPost = 0.0;
 };
 
@@ -153,6 +158,7 @@ struct ShdPe {
     std::mutex mu;                   // compute / gather
     std::mutex copyMu;               // staging buffers
     double msGather = 0.0;
+    int64_t pathsInfo[6] = {0, 0, 0, 0, 0, 0};   // shd_pe_paths_info of the last shd_pe_get_paths
 };
 
 #define HIPCHK(x)                                   \
@@ -212,6 +218,9 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_BATCH_COOP", t.batchCoop);
     gi("SHDPE_BATCH_COOP_WPE", t.batchCoopWpe);
     gi("SHDPE_COOP_SPIN", t.coopSpin);
+    gi("SHDPE_PATHS_GROUP", t.pathsGroup);
+    gi("SHDPE_PATHS_CHUNK", t.pathsChunk);
+    gi("SHDPE_PATHS_FAST", t.pathsFast);
 }
 
 extern "C" void shd_pe_default_options(ShdPeOptions* opt) {
@@ -1389,10 +1398,16 @@ static std::vector<int32_t> batch_order(const ShdPe* pe, int LB, const int32_t* 
 // over the same batches (their dist arrays persist in HBM)
 // (the post kernel may run another variant than the relax).  A timed trial
 // gets the parts' times.
+// roundHook (shd_pe_get_paths; null otherwise): called after each round's
+// post kernel and tie export, while the round's dist arrays and ambiguity
+// bytes are still in place, with the round's first batch and batch count.
+using RoundHook = std::function<int(int32_t r0, int32_t rn)>;
+
 static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const BatchLaunch& post, int32_t nB,
-                        BatchTrial* trial) {
+                        BatchTrial* trial, const RoundHook* roundHook = nullptr) {
     const int LB = relax.lb;
     const bool timed = trial && trial->timed;
+    const int postPart = trial && trial->noTable ? 4 : 2;   // (4: the post kernel without its row stores)
     int rc;
     for (int32_t r0 = 0; r0 < nB; r0 += sh->batchRound) {
         const int32_t rn = std::min(sh->batchRound, nB - r0);
@@ -1406,7 +1421,8 @@ static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const Ba
             } else {
                 HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
                 launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows + ro, rn, sh->dBatchAmb + ro,
-                                  part == 1 ? relax : post, dbgR, sh->dTie, sh->stream, part);
+                                  part == 1 ? relax : post, dbgR, sh->dTie, sh->stream,
+                                  part == 1 ? 1 : postPart);
             }
             // tests only (SHDPE_TUNE_FAIL_WPE): the relax variant of that wave
             // count flags every batch failed, as a miscompiled variant would
@@ -1421,6 +1437,7 @@ static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const Ba
                 launch_tie_export(sh->dg, sh->bsc, LB, sh->tie, r0 / sh->batchRound, sh->dBatchAmb + ro,
                                   sh->numCUs * 4, pe->tu.tieCorrupt == 3 ? 0 : -1, sh->stream);
         }
+        if (roundHook && (rc = (*roundHook)(r0, rn))) return rc;
         if (timed) {
             HIPCHK(hipEventSynchronize(sh->evP[2]));
             trial->msRelax += elapsed(sh->evP[0], sh->evP[1]);
@@ -1438,14 +1455,19 @@ static const BatchLaunch& post_launch(const Shard* sh, const BatchTrial* trial) 
     return trial ? trial->post : sh->plan.post;
 }
 
+// (orderOut / roundHook: shd_pe_get_paths -- the batch order the rounds run
+// in, handed out before the first launch, and the per-round hook of
+// batch_rounds; split kernels only)
 static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x,
-                         BatchTrial* trial) {
+                         BatchTrial* trial, std::vector<int32_t>* orderOut = nullptr,
+                         const RoundHook* roundHook = nullptr) {
     ShdPeStats& st = sh->stats;
     int rc;
     if ((rc = ensure_batch(pe, sh))) return rc;
     const BatchLaunch& relax = relax_launch(sh, trial);
     int32_t nB = 0;
     const std::vector<int32_t> order = batch_order(pe, relax.lb, pos, cnt, nB);
+    if (orderOut) *orderOut = order;
     HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
     if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
     if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
@@ -1454,7 +1476,7 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     if (!relax.split)
         launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows, nB, sh->dBatchAmb, relax,
                           sh->dDbg, sh->dTie, sh->stream, 0);
-    else if ((rc = batch_rounds(pe, sh, relax, post_launch(sh, trial), nB, trial)))
+    else if ((rc = batch_rounds(pe, sh, relax, post_launch(sh, trial), nB, trial, roundHook)))
         return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sh->evB, sh->stream));
@@ -2188,6 +2210,475 @@ extern "C" int shd_pe_get_path(ShdPe* pe, int32_t srcVertex, int32_t dstVertex, 
     HIPCHK(hipMemcpy(rev.data(), sh->dPath, (size_t)n * 4, hipMemcpyDeviceToHost));
     for (int32_t k = 0; k < n; ++k) verts[k] = rev[n - 1 - k];
     *len = n;
+    return SHD_PE_OK;
+}
+
+// ---- shd_pe_get_paths: batched path extraction --------------------
+namespace {
+
+constexpr int32_t PATHS_CHUNK = 65536;            // requests per staging chunk
+constexpr int64_t PATHS_ENTRIES = (int64_t)1 << 22;   // output entries per chunk (one path may exceed it)
+constexpr int32_t PATHS_NOT_MINE = INT32_MIN;     // status preset: another shard answers the request
+
+// Device staging of one shard for one shd_pe_get_paths call (freed with it).
+struct PathsStage {
+    int device = 0;
+    std::vector<void*> mem;
+    int32_t *src = nullptr, *dst = nullptr, *posOf = nullptr, *len = nullptr, *stat = nullptr;
+    int32_t *verts = nullptr, *nFailed = nullptr;
+    int32_t* rows = nullptr;                        // a chunk's unique sources that take the emulation
+    int64_t* off = nullptr;
+    PathReq *reqs = nullptr, *reqsB = nullptr;      // requests of the emulation tier / of the batch tier
+    uint8_t *failed = nullptr, *flags = nullptr;
+    double *hopLat = nullptr, *hopRel = nullptr;
+    int64_t entries = 0;             // capacity of verts / hopLat / hopRel
+    std::vector<int32_t> hLen, hStat;
+    ~PathsStage() {
+        if (mem.empty()) return;
+        (void)hipSetDevice(device);
+        for (void* p : mem) (void)hipFree(p);
+    }
+    template <class T>
+    int get(T** p, size_t count) {
+        void* q = nullptr;
+        if (hipMalloc(&q, std::max<size_t>(16, count * sizeof(T))) != hipSuccess) return SHD_PE_ENOMEM;
+        mem.push_back(q);
+        *p = (T*)q;
+        return SHD_PE_OK;
+    }
+};
+
+struct PathsCall {
+    const int32_t *src, *dst;
+    const ShdPePathsOut* out;
+    int32_t chunk;                   // requests per chunk
+    int32_t group;                   // sources per emulation group (<= every shard's exactGrid)
+    int64_t entries;                 // output entries per chunk
+    bool hops;
+    std::vector<PathsStage> st;      // per local shard
+    std::vector<int32_t> slotOf;     // table position -> its place among a chunk's unique sources, -1
+    double ms = 0.0;
+};
+
+}  // namespace
+
+static int paths_stage_init(ShdPe* pe, PathsCall& c, size_t k) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    if (s.src) return SHD_PE_OK;
+    s.device = sh->device;
+    int rc;
+    const size_t C = (size_t)c.chunk;
+    if ((rc = s.get(&s.src, C)) || (rc = s.get(&s.dst, C)) || (rc = s.get(&s.len, C)) ||
+        (rc = s.get(&s.stat, C)) || (rc = s.get(&s.off, C + 1)) || (rc = s.get(&s.posOf, (size_t)pe->hg.n)))
+        return rc;
+    HIPCHK(hipMemcpyAsync(s.posOf, pe->posOf.data(), (size_t)pe->hg.n * 4, hipMemcpyHostToDevice, sh->stream));
+    return SHD_PE_OK;
+}
+
+// The extraction's part of the staging (not needed by a sizing call).
+static int paths_stage_extract(ShdPe* pe, PathsCall& c, size_t k) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    if (s.verts) return SHD_PE_OK;
+    int rc;
+    const size_t C = (size_t)c.chunk, E = (size_t)c.entries;
+    if ((rc = s.get(&s.verts, E)) || (rc = s.get(&s.reqs, C)) || (rc = s.get(&s.reqsB, C)) ||
+        (rc = s.get(&s.failed, C)) || (rc = s.get(&s.nFailed, 4)) || (rc = s.get(&s.rows, C)) ||
+        (rc = s.get(&s.flags, (size_t)std::min(c.group, sh->rowCount) * pe->attached.size())))
+        return rc;
+    if (c.hops && ((rc = s.get(&s.hopLat, E)) || (rc = s.get(&s.hopRel, E)))) return rc;
+    s.entries = (int64_t)E;
+    return SHD_PE_OK;
+}
+
+// Lengths and statuses of requests [c0, c0 + cnt) as shard k answers them
+// (hLen / hStat; statuses another shard answers stay PATHS_NOT_MINE), and the
+// exclusive scan of its lengths on the device (s.off) for the walk.
+static int paths_size_chunk(ShdPe* pe, PathsCall& c, size_t k, int64_t c0, int32_t cnt) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    HIPCHK(hipSetDevice(sh->device));
+    int rc = pe->mode == 2 ? SHD_PE_OK : ensure_table(pe, sh);   // (a complete graph's paths need no table)
+    if (rc || (rc = paths_stage_init(pe, c, k))) return rc;
+    HIPCHK(hipMemcpyAsync(s.src, c.src + c0, (size_t)cnt * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemcpyAsync(s.dst, c.dst + c0, (size_t)cnt * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipEventRecord(sh->ev0, sh->stream));
+    HIPCHK(hipMemsetAsync(s.len, 0, (size_t)cnt * 4, sh->stream));
+    HIPCHK(hipMemsetD32Async((hipDeviceptr_t)s.stat, PATHS_NOT_MINE, (size_t)cnt, sh->stream));
+    const PathsSizeArgs a{s.src, s.dst, cnt, s.posOf, pe->ownStart, pe->ownEnd, sh->rowStart,
+                          sh->rowStart + sh->rowCount, k == 0 ? 1 : 0, pe->mode == 2 ? 1 : 0, s.len, s.stat};
+    launch_paths_size(sh->dgAux, sh->tab, a, sh->stream);
+    launch_paths_scan(s.len, cnt, s.off, sh->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sh->ev1, sh->stream));
+    s.hLen.resize((size_t)cnt);
+    s.hStat.resize((size_t)cnt);
+    HIPCHK(hipMemcpyAsync(s.hLen.data(), s.len, (size_t)cnt * 4, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipMemcpyAsync(s.hStat.data(), s.stat, (size_t)cnt * 4, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    c.ms += elapsed(sh->ev0, sh->ev1);
+    return SHD_PE_OK;
+}
+
+// The batch tier serves shards on the split batch kernels (the C4 / C5
+// default); every other path (non-split, sparse, dense, forceMode 3, latFold
+// multigraphs) goes to the grouped emulation alone.  SHDPE_PATHS_FAST=0: off.
+static bool paths_batch_tier_applies(const ShdPe* pe, const Shard* sh) {
+    return pe->tu.pathsFast != 0 && pe->mode == 1 && pe->batched && pe->opt.forceMode != 3 &&
+           !pe->hg.latFold && sh->plan.relax.split != 0;
+}
+
+// Batch tier: one relax + post pass of the split batch kernels over the
+// chunk's unique sources (`uniq`, table positions), and after each round's post
+// kernel and tie export one k_paths_walk_dist over the requests (`walk`:
+// place of the source in uniq, request) whose source sits in that round, on
+// the round's persisted distance arrays.  The pass stores no table row
+// (BatchTrial::noTable): the table is not touched here at all.
+// Tie tier: the rows the pass gave a tie slot (early-stop tie rows) then run
+// what the exact stage runs for them -- relevance scan and the emulation up to
+// the row's tie threshold, which leaves the final parents in tie.P of the
+// slot -- without k_tie_write (the table holds the row already), and one
+// k_paths_walk over their requests on tie.P.  A slot that failed the
+// emulation's consistency check, and a walk that did not arrive, hand on.
+// On return uniq / walk hold what goes to the grouped emulation only (places
+// renumbered): rows the pass sent to the full emulation, and every request
+// handed on.  ShdPeStats is put back as it was.
+static int paths_batch_tier(ShdPe* pe, PathsCall& c, size_t k, int32_t cnt, std::vector<int32_t>& uniq,
+                            std::vector<std::pair<int32_t, PathReq>>& walk) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    int rc;
+    if ((rc = ensure_batch(pe, sh))) return rc;
+    if (!sh->plan.relax.split) return SHD_PE_OK;
+    const ShdPeStats savedStats = sh->stats;
+    BatchTrial trial;                                    // the plan's picks; for a cooperative relax the
+    trial.relax = sh->plan.relax;                        // plain kernel of the post variant (as ensure_batch)
+    if (trial.relax.coop >= 2) trial.relax = sh->plan.post;
+    trial.relax.coop = 0;
+    trial.post = sh->plan.post;
+    trial.noTable = true;
+    const int32_t LB = trial.relax.lb;
+    std::vector<int32_t> order;                          // batch order of the pass: table positions, -1 pads
+    std::vector<std::pair<int32_t, PathReq>> byOrd;      // (index of the source in order, request)
+    std::vector<PathReq> breqs;
+    const RoundHook hook = [&](int32_t r0, int32_t rn) -> int {
+        if (byOrd.empty()) {
+            for (size_t i = 0; i < order.size(); ++i)
+                if (order[i] >= 0) c.slotOf[(size_t)order[i]] = (int32_t)i;
+            byOrd.reserve(walk.size());
+            for (const auto& w : walk) {
+                PathReq q = w.second;
+                q.slot = c.slotOf[(size_t)uniq[(size_t)w.first]];
+                byOrd.push_back({q.slot, q});
+            }
+            for (int32_t p : uniq) c.slotOf[(size_t)p] = -1;
+            std::stable_sort(byOrd.begin(), byOrd.end(),
+                             [](const auto& a, const auto& b) { return a.first < b.first; });
+            breqs.resize(byOrd.size());
+            for (size_t i = 0; i < byOrd.size(); ++i) breqs[i] = byOrd[i].second;
+            HIPCHK(hipMemcpyAsync(s.reqsB, breqs.data(), breqs.size() * sizeof(PathReq), hipMemcpyHostToDevice,
+                                  sh->stream));
+        }
+        const auto cmp = [](const std::pair<int32_t, PathReq>& a, int32_t v) { return a.first < v; };
+        const size_t lo = std::lower_bound(byOrd.begin(), byOrd.end(), r0 * LB, cmp) - byOrd.begin();
+        const size_t hi = std::lower_bound(byOrd.begin(), byOrd.end(), (r0 + rn) * LB, cmp) - byOrd.begin();
+        const PathsDistArgs a{s.reqsB + lo, (int32_t)(hi - lo), LB, r0 * LB, sh->dBatchAmb + (size_t)r0 * LB,
+                              s.len, s.off, s.verts, s.failed};
+        launch_paths_walk_dist(sh->dg, sh->bsc, a, sh->stream);
+        HIPCHK(hipGetLastError());
+        return SHD_PE_OK;
+    };
+    ExactWork x;
+    rc = relax_batched(pe, sh, uniq.data(), (int32_t)uniq.size(), x, &trial, &order, &hook);
+    sh->stats = savedStats;
+    if (rc) return rc;
+    std::vector<uint8_t> failed((size_t)cnt), failedTie;
+    HIPCHK(hipMemcpyAsync(failed.data(), s.failed, (size_t)cnt, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    HIPCHK(hipMemsetAsync(s.failed, 0, (size_t)cnt, sh->stream));
+    // per unique source (place in uniq) what the pass made of it: 0 resolved,
+    // 1 + i: early-stop tie row i of x (its slot x.slots[i]), -1: full emulation
+    int32_t nTie = 0;
+    while (nTie < (int32_t)x.slots.size() && x.slots[(size_t)nTie] >= 0) ++nTie;
+    std::vector<int32_t> cls(uniq.size(), 0);
+    for (size_t i = 0; i < uniq.size(); ++i) c.slotOf[(size_t)uniq[i]] = (int32_t)i;
+    for (size_t j = 0; j < x.rows.size(); ++j)
+        cls[(size_t)c.slotOf[(size_t)x.rows[j]]] = (int32_t)j < nTie ? 1 + (int32_t)j : -1;
+    for (int32_t p : uniq) c.slotOf[(size_t)p] = -1;
+    // tie tier: the early-stop part of the exact stage on those rows (no table
+    // write), then their requests walked on tie.P
+    std::vector<uint8_t> slotBad((size_t)nTie, 0);
+    if (nTie > 0) {
+        std::vector<PathReq> treqs;
+        for (const auto& w : walk) {
+            const int32_t ci = cls[(size_t)w.first];
+            if (ci <= 0) continue;
+            PathReq q = w.second;
+            q.slot = x.slots[(size_t)ci - 1];
+            treqs.push_back(q);
+        }
+        sh->pathSrc = -1;                                // the exact kernel reuses scratch slot 0
+        HIPCHK(hipMemcpyAsync(sh->dRows, x.rows.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipMemcpyAsync(sh->dSlots, x.slots.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipMemcpyAsync(s.reqsB, treqs.data(), treqs.size() * sizeof(PathReq), hipMemcpyHostToDevice,
+                              sh->stream));
+        scan_tie_slots(pe, sh, x.slots, nTie);
+        launch_exact_rows(sh->dg, sh->tab, sh->sc, sh->dRows, nTie, sh->exactGrid, sh->exactHc,
+                          pe->tu.exactHc > 0, sh->dSlots, sh->tie, nullptr, sh->stream);
+        HIPCHK(hipGetLastError());
+        const PathsWalkArgs wt{s.reqsB, (int32_t)treqs.size(), sh->tie.P, sh->tie.n, (int32_t)pe->hg.nArcs(),
+                               s.len, s.off, s.verts, s.failed, s.nFailed + 2};
+        launch_paths_walk(sh->dg, wt, sh->stream);
+        HIPCHK(hipGetLastError());
+        failedTie.resize((size_t)cnt);
+        HIPCHK(hipMemcpyAsync(failedTie.data(), s.failed, (size_t)cnt, hipMemcpyDeviceToHost, sh->stream));
+        std::vector<int32_t> redo;                       // (synchronises; treqs is read by then)
+        if ((rc = failed_tie_rows(sh, x.rows.data(), x.slots.data(), nTie, sh->tie.cap, redo))) return rc;
+        HIPCHK(hipMemsetAsync(s.failed, 0, (size_t)cnt, sh->stream));
+        for (int32_t i = 0, r = 0; i < nTie && r < (int32_t)redo.size(); ++i)
+            if (x.rows[(size_t)i] == redo[(size_t)r]) { slotBad[(size_t)i] = 1; ++r; }
+    }
+    // what goes on to the emulation: rows the pass sent to the full emulation,
+    // and the requests that left a tier after its check
+    std::vector<int32_t> uniq2, place2(uniq.size(), -1);
+    std::vector<std::pair<int32_t, PathReq>> walk2;
+    std::vector<uint8_t> served(uniq.size(), 1);
+    for (const auto& w : walk) {
+        const int32_t ci = cls[(size_t)w.first];
+        const size_t rq = (size_t)w.second.req;
+        const bool left = ci == 0 ? failed[rq] != 0 : ci > 0 && (slotBad[(size_t)ci - 1] || failedTie[rq]);
+        if (ci >= 0 && !left) continue;
+        served[(size_t)w.first] = 0;
+        pe->pathsInfo[3] += left;
+        if (place2[(size_t)w.first] < 0) {
+            place2[(size_t)w.first] = (int32_t)uniq2.size();
+            uniq2.push_back(uniq[(size_t)w.first]);
+        }
+        walk2.push_back({place2[(size_t)w.first], w.second});
+    }
+    for (size_t i = 0; i < served.size(); ++i)
+        if (served[i]) pe->pathsInfo[cls[i] > 0 ? 1 : 0] += 1;
+    std::stable_sort(walk2.begin(), walk2.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
+    uniq.swap(uniq2);
+    walk.swap(walk2);
+    return SHD_PE_OK;
+}
+
+// Paths of requests [c0, c0 + cnt) that shard k answers (paths_size_chunk ran):
+// the grouped emulation of their unique sources, the walks, the hop attributes,
+// and the copy into the caller's arrays at the global offsets.
+static int paths_extract_chunk(ShdPe* pe, PathsCall& c, size_t k, int64_t c0, int32_t cnt) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    int64_t total = 0;
+    for (int32_t i = 0; i < cnt; ++i) total += s.hLen[(size_t)i];
+    if (total == 0) return SHD_PE_OK;
+    int rc = paths_stage_extract(pe, c, k);
+    if (rc) return rc;
+    if (total > s.entries) return SHD_PE_EINVAL;         // (the chunking keeps it within)
+    sh->pathSrc = -1;                                    // shd_pe_get_path's cached parents do not survive the call
+    // requests by the place of their source among the chunk's unique sources
+    // (first appearance); those without a walk first
+    std::vector<int32_t> uniq;                           // table positions
+    std::vector<PathReq> reqs;
+    std::vector<std::pair<int32_t, PathReq>> walk;       // (place of the source, request)
+    for (int32_t i = 0; i < cnt; ++i) {
+        if (s.hLen[(size_t)i] <= 0) continue;
+        const int32_t sv = c.src[c0 + i], tv = c.dst[c0 + i];
+        if (sv == tv || pe->mode == 2) {
+            reqs.push_back(PathReq{i, -1, sv, tv});
+            continue;
+        }
+        const int32_t ps = pe->posOf[sv];
+        if (c.slotOf[ps] < 0) {
+            c.slotOf[ps] = (int32_t)uniq.size();
+            uniq.push_back(ps);
+        }
+        const bool relabelled = !pe->devOf.empty();
+        walk.push_back({c.slotOf[ps], PathReq{i, 0, relabelled ? pe->devOf[sv] : sv,
+                                               relabelled ? pe->devOf[tv] : tv}});
+    }
+    for (int32_t p : uniq) c.slotOf[p] = -1;
+    std::stable_sort(walk.begin(), walk.end(),
+                     [](const auto& a, const auto& b) { return a.first < b.first; });
+    const int32_t G = std::min(c.group, sh->exactGrid);
+    HIPCHK(hipEventRecord(sh->ev0, sh->stream));
+    HIPCHK(hipMemsetAsync(s.failed, 0, (size_t)cnt, sh->stream));
+    HIPCHK(hipMemsetAsync(s.nFailed, 0, 16, sh->stream));
+    PathsWalkArgs wa{s.reqs, 0, sh->sc.pred, sh->sc.stride, (int32_t)pe->hg.nArcs(), s.len, s.off, s.verts,
+                     s.failed, s.nFailed};
+    if (!reqs.empty()) {
+        HIPCHK(hipMemcpyAsync(s.reqs, reqs.data(), reqs.size() * sizeof(PathReq), hipMemcpyHostToDevice,
+                              sh->stream));
+        wa.nReqs = (int32_t)reqs.size();
+        launch_paths_walk(sh->dg, wa, sh->stream);
+        HIPCHK(hipGetLastError());
+    }
+    // the batch tier first where the shard runs the split batch kernels; what
+    // it hands on (and everything, elsewhere) goes to the grouped emulation
+    if (!walk.empty() && paths_batch_tier_applies(pe, sh) &&
+        (rc = paths_batch_tier(pe, c, k, cnt, uniq, walk)))   // (leaves in uniq / walk what it handed on)
+        return rc;
+    // igraph's whole Dijkstra for each unique source, a group per launch: row
+    // i of the group runs in workgroup i and leaves every popped vertex's
+    // chosen IN-arc in scratch slot i (no tie slots: full emulations).  The
+    // emulation rewrites the table rows with the same values but marks every
+    // entry F_EXACT: the rows' flag bytes are saved before and put back after.
+    // (rows and requests of every group are uploaded once, up front: no host
+    // buffer is reused while a copy may still read it)
+    std::vector<PathReq> wreqs(walk.size());
+    for (size_t i = 0; i < walk.size(); ++i) {
+        wreqs[i] = walk[i].second;
+        wreqs[i].slot = walk[i].first % G;
+    }
+    PathReq* const dWalk = s.reqs + reqs.size();         // behind the requests without a walk
+    if (!uniq.empty()) {
+        HIPCHK(hipMemcpyAsync(s.rows, uniq.data(), uniq.size() * 4, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipMemcpyAsync(dWalk, wreqs.data(), wreqs.size() * sizeof(PathReq), hipMemcpyHostToDevice,
+                              sh->stream));
+    }
+    size_t w0 = 0;
+    for (size_t u0 = 0; u0 < uniq.size(); u0 += (size_t)G) {
+        const int32_t g = (int32_t)std::min<size_t>((size_t)G, uniq.size() - u0);
+        sh->pathSrc = -1;                                // shd_pe_get_path's slot 0 is reused
+        launch_paths_flags(sh->tab, s.rows + u0, g, s.flags, false, sh->stream);
+        launch_exact_rows(sh->dg, sh->tab, sh->sc, s.rows + u0, g, g, sh->exactHc, pe->tu.exactHc > 0,
+                          nullptr, sh->tie, nullptr, sh->stream);
+        launch_paths_flags(sh->tab, s.rows + u0, g, s.flags, true, sh->stream);
+        HIPCHK(hipGetLastError());
+        size_t w1 = w0;
+        while (w1 < walk.size() && walk[w1].first < (int32_t)u0 + g) ++w1;
+        wa.reqs = dWalk + w0;
+        wa.nReqs = (int32_t)(w1 - w0);
+        launch_paths_walk(sh->dg, wa, sh->stream);
+        HIPCHK(hipGetLastError());
+        w0 = w1;
+        pe->pathsInfo[2] += g;
+        pe->pathsInfo[4] += 1;
+    }
+    if (c.hops) {
+        launch_paths_hops(sh->dgAux, s.off, cnt, total, s.verts, s.hopLat, s.hopRel, s.nFailed + 1, sh->stream);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(sh->ev1, sh->stream));
+    int32_t nFailed[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(nFailed, s.nFailed, 8, hipMemcpyDeviceToHost, sh->stream));
+    const ShdPePathsOut& o = *c.out;
+    const int64_t* goff = o.offsets + c0;
+    if (pe->shards.size() == 1) {
+        // one shard answers every request: its compact order is the caller's
+        HIPCHK(hipMemcpyAsync(o.verts + goff[0], s.verts, (size_t)total * 4, hipMemcpyDeviceToHost, sh->stream));
+        if (o.hopLat)
+            HIPCHK(hipMemcpyAsync(o.hopLat + goff[0], s.hopLat, (size_t)total * 8, hipMemcpyDeviceToHost, sh->stream));
+        if (o.hopRel)
+            HIPCHK(hipMemcpyAsync(o.hopRel + goff[0], s.hopRel, (size_t)total * 8, hipMemcpyDeviceToHost, sh->stream));
+        HIPCHK(hipStreamSynchronize(sh->stream));
+    } else {
+        std::vector<int32_t> hv((size_t)total);
+        std::vector<double> hl(o.hopLat ? (size_t)total : 0), hr(o.hopRel ? (size_t)total : 0);
+        HIPCHK(hipMemcpyAsync(hv.data(), s.verts, (size_t)total * 4, hipMemcpyDeviceToHost, sh->stream));
+        if (o.hopLat) HIPCHK(hipMemcpyAsync(hl.data(), s.hopLat, (size_t)total * 8, hipMemcpyDeviceToHost, sh->stream));
+        if (o.hopRel) HIPCHK(hipMemcpyAsync(hr.data(), s.hopRel, (size_t)total * 8, hipMemcpyDeviceToHost, sh->stream));
+        HIPCHK(hipStreamSynchronize(sh->stream));
+        int64_t lo = 0;
+        for (int32_t i = 0; i < cnt; ++i) {
+            const int32_t L = s.hLen[(size_t)i];
+            if (L <= 0) continue;
+            std::memcpy(o.verts + goff[i], hv.data() + lo, (size_t)L * 4);
+            if (o.hopLat) std::memcpy(o.hopLat + goff[i], hl.data() + lo, (size_t)L * 8);
+            if (o.hopRel) std::memcpy(o.hopRel + goff[i], hr.data() + lo, (size_t)L * 8);
+            lo += L;
+        }
+    }
+    c.ms += elapsed(sh->ev0, sh->ev1);
+    // the emulation is the last tier: a walk that missed its source, or a hop
+    // without an edge, means the scratch parents are not what the table says
+    if (nFailed[0] || nFailed[1]) return SHD_PE_EHIP;
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* dst, int64_t count,
+                                const ShdPePathsOut* out) {
+    if (!pe || !out || !out->offsets || count < 0 || (count > 0 && (!src || !dst))) return SHD_PE_EINVAL;
+    if (out->verts && out->cap < 0) return SHD_PE_EINVAL;
+    if ((out->hopLat || out->hopRel) && !out->verts) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(pe->mu);
+    for (int64_t& x : pe->pathsInfo) x = 0;
+    out->offsets[0] = 0;
+    if (count == 0) return SHD_PE_OK;
+    const HostGraph& g = pe->hg;
+    const int32_t T = (int32_t)pe->attached.size();
+    int rc;
+    // rows the lengths are read from, computed first where missing
+    if (pe->mode != 2) {
+        std::vector<int32_t> todo;
+        std::vector<uint8_t> seen((size_t)T, 0);
+        for (int64_t i = 0; i < count; ++i) {
+            const int32_t s = src[i], t = dst[i];
+            if (s < 0 || s >= g.n || t < 0 || t >= g.n || s == t) continue;
+            const int32_t ps = pe->posOf[s];
+            if (ps < pe->ownStart || ps >= pe->ownEnd || pe->posOf[t] < 0 || seen[(size_t)ps]) continue;
+            seen[(size_t)ps] = 1;
+            if (!row_done(pe, ps)) todo.push_back(ps);
+        }
+        if ((rc = compute_positions_locked(pe, todo.data(), (int32_t)todo.size()))) return rc;
+    }
+    PathsCall c;
+    c.src = src;
+    c.dst = dst;
+    c.out = out;
+    c.chunk = (int32_t)std::min<int64_t>(count, pe->tu.pathsChunk > 0 ? pe->tu.pathsChunk : PATHS_CHUNK);
+    c.group = INT32_MAX;
+    for (auto& sh : pe->shards) {
+        c.group = std::min(c.group, sh->exactGrid);
+    }
+    // (a chunk's unique sources of a shard fit its dBatchRows / dBatchAmb: they
+    // are rows of the shard, so at most min(chunk, rowCount) <= rowsCap)
+    c.chunk = std::min(c.chunk, 1 << 20);
+    if (pe->tu.pathsGroup > 0) c.group = std::min(c.group, pe->tu.pathsGroup);
+    c.entries = std::max<int64_t>(PATHS_ENTRIES, (int64_t)g.n + 1);
+    c.hops = out->hopLat || out->hopRel;
+    c.st.resize(pe->shards.size());
+    c.slotOf.assign((size_t)T, -1);
+    auto finish = [&](int r) {
+        pe->pathsInfo[5] = (int64_t)std::llround(c.ms * 1000.0);
+        return r;
+    };
+    // pass 1, sizing: every request's length and status -> offsets
+    int64_t total = 0;
+    for (int64_t c0 = 0; c0 < count; c0 += c.chunk) {
+        const int32_t cnt = (int32_t)std::min<int64_t>(c.chunk, count - c0);
+        for (size_t k = 0; k < pe->shards.size(); ++k)
+            if ((rc = paths_size_chunk(pe, c, k, c0, cnt))) return finish(rc);
+        for (int32_t i = 0; i < cnt; ++i) {
+            int32_t L = 0, st = SHD_PE_ENOTOWNED;
+            for (const PathsStage& s : c.st)
+                if (s.hStat[(size_t)i] != PATHS_NOT_MINE) { L = s.hLen[(size_t)i]; st = s.hStat[(size_t)i]; }
+            if (out->status) out->status[c0 + i] = st;
+            total += L;
+            out->offsets[c0 + i + 1] = total;
+        }
+    }
+    if (!out->verts) return finish(SHD_PE_OK);
+    if (total > out->cap) return finish(SHD_PE_EINVAL);
+    // pass 2, extraction: chunks bounded in requests and in output entries
+    for (int64_t c0 = 0; c0 < count;) {
+        int64_t c1 = c0 + 1;
+        while (c1 < count && c1 - c0 < c.chunk && out->offsets[c1 + 1] - out->offsets[c0] <= c.entries) ++c1;
+        const int32_t cnt = (int32_t)(c1 - c0);
+        for (size_t k = 0; k < pe->shards.size(); ++k)
+            if ((rc = paths_size_chunk(pe, c, k, c0, cnt)) || (rc = paths_extract_chunk(pe, c, k, c0, cnt)))
+                return finish(rc);
+        c0 = c1;
+    }
+    return finish(SHD_PE_OK);
+}
+
+extern "C" int shd_pe_paths_info(const ShdPe* pe, int64_t* info, int32_t n) {
+    if (!pe || !info || n < 0) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
+    for (int32_t k = 0; k < std::min<int32_t>(n, 6); ++k) info[k] = pe->pathsInfo[k];
     return SHD_PE_OK;
 }
 

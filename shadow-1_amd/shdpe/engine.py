@@ -48,6 +48,7 @@ EXPORTS = [
     "shd_graphml_vertex_attrs", "shd_graphml_attr_code", "shd_graphml_vertex_attr_string",
     "shd_pe_attach_new", "shd_pe_attach_free", "shd_pe_attach_hosts", "shd_pe_attach_host",
     "shd_pe_attach_set_chunk", "shd_pe_attach_timing",
+    "shd_pe_get_paths", "shd_pe_paths_info",
 ]
 VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
 VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
@@ -100,6 +101,12 @@ class AttachResultC(C.Structure):
     """ShdPeAttachResult"""
     _fields_ = [("vertex", C.c_void_p), ("candidateSet", C.c_void_p), ("numCandidates", C.c_void_p),
                 ("usedRandom", C.c_void_p), ("bwDown", C.c_void_p), ("bwUp", C.c_void_p)]
+
+
+class PathsOutC(C.Structure):
+    """ShdPePathsOut"""
+    _fields_ = [("offsets", C.c_void_p), ("verts", C.c_void_p), ("hopLat", C.c_void_p),
+                ("hopRel", C.c_void_p), ("status", C.c_void_p), ("cap", C.c_int64)]
 
 
 class EngineError(RuntimeError):
@@ -202,14 +209,17 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_attach_host": (C.c_int, [vp, vp, i64, vp]),
         "shd_pe_attach_set_chunk": (C.c_int, [vp, i64]),
         "shd_pe_attach_timing": (C.c_int, [vp, vp]),
+        "shd_pe_get_paths": (C.c_int, [vp, vp, vp, i64, vp]),
+        "shd_pe_paths_info": (C.c_int, [vp, vp, i32]),
     }
-    # ABI-3 / ABI-4 / ABI-5 additions: an older build loaded through SHDPE_LIB (same-box
+    # ABI-3 ... ABI-6 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
     optional = {"shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_fill_rowstore_ex",
                 "shd_topology_fill", "shd_graphml_vertex_attrs", "shd_graphml_attr_code",
                 "shd_graphml_vertex_attr_string", "shd_pe_attach_new", "shd_pe_attach_free",
                 "shd_pe_attach_hosts", "shd_pe_attach_host", "shd_pe_attach_set_chunk",
-                "shd_pe_attach_timing"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_pe_attach_timing", "shd_pe_get_paths",
+                "shd_pe_paths_info"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -490,6 +500,38 @@ class Engine:
         self._chk(self._lib.shd_pe_get_path(self.h, int(src), int(dst), _p(buf), int(cap), C.byref(ln)),
                   "shd_pe_get_path")
         return buf[:ln.value].tolist()
+
+    def get_paths(self, src, dst, hops: bool = False):
+        """shd_pe_get_paths: the igraph paths of the pairs (src[i], dst[i]) in
+        one call -> (offsets, verts, status[, hop_lat, hop_rel]); path i is
+        verts[offsets[i]:offsets[i+1]], empty where status[i] != 0.  The sizing
+        call is made here."""
+        s = np.ascontiguousarray(src, dtype=np.int32)
+        d = np.ascontiguousarray(dst, dtype=np.int32)
+        if s.ndim != 1 or s.shape != d.shape:
+            raise ValueError("src/dst must be 1-D arrays of one length")
+        n = s.shape[0]
+        offsets = np.zeros(n + 1, np.int64)
+        status = np.zeros(n, np.int32)
+        o = PathsOutC(_p(offsets), None, None, None, _p(status), 0)
+        self._chk(self._lib.shd_pe_get_paths(self.h, _p(s), _p(d), n, C.byref(o)), "shd_pe_get_paths")
+        total = int(offsets[n])
+        verts = np.empty(max(total, 1), np.int32)
+        lat = np.empty(max(total, 1)) if hops else None
+        rel = np.empty(max(total, 1)) if hops else None
+        o = PathsOutC(_p(offsets), _p(verts), _p(lat), _p(rel), _p(status), total)
+        self._chk(self._lib.shd_pe_get_paths(self.h, _p(s), _p(d), n, C.byref(o)), "shd_pe_get_paths")
+        if hops:
+            return offsets, verts[:total], status, lat[:total], rel[:total]
+        return offsets, verts[:total], status
+
+    def paths_info(self) -> dict:
+        """shd_pe_paths_info of the last get_paths: unique sources per tier,
+        requests handed on, emulation groups, device ms."""
+        info = np.zeros(6, np.int64)
+        self._chk(self._lib.shd_pe_paths_info(self.h, _p(info), 6), "shd_pe_paths_info")
+        return {"batch": int(info[0]), "tie": int(info[1]), "emulated": int(info[2]),
+                "handed_on": int(info[3]), "groups": int(info[4]), "device_ms": info[5] / 1000.0}
 
     def tune(self):
         """shd_pe_tune: time both k_batch_rows variants on this engine's rows,
