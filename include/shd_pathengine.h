@@ -223,7 +223,10 @@ int shd_pe_get_rows(ShdPe* pe, int32_t start, int32_t count, double* lat, double
  * target's predecessor, so the first call for a source re-runs igraph's
  * Dijkstra for it on the device (the exact 2-wheap emulation, one wave:
  * milliseconds to ~1 s at 10^5 vertices); later calls for the same source
- * are a device walk until the next compute.  src == dst -> [src]; complete
+ * are a device walk until the next compute or emulation of another source.
+ * The walk is shd_pe_get_paths' for one request: the length comes from the
+ * table's hops, the vertices are written in order, and a walk that does not
+ * end on src is SHD_PE_EUNREACHABLE.  src == dst -> [src]; complete
  * graphs -> [src, dst] (_topology_lookupDirectPath).  SHD_PE_ENOTOWNED for a
  * source outside this engine's shard, SHD_PE_EUNREACHABLE, SHD_PE_EINVAL when
  * the path needs more than cap entries. */

@@ -73,6 +73,14 @@ struct BatchTrial {
     double msRelax = 0.0, msPost = 0.0;
 };
 
+// shd_pe_get_path: PathsWalkArgs' arrays for one request (off = 0); the path's vertices follow.
+struct PathOne {
+    int64_t off;
+    int32_t len, nFailed;
+    PathReq req;
+    uint8_t failed, pad[31];
+};
+
 struct Shard {
     int gindex = 0;                 // global shard index
     int device = 0;
@@ -92,7 +100,7 @@ struct Shard {
     uint8_t* dRowAmbig = nullptr;
     int32_t* dDbg = nullptr;
     int32_t pathSrc = -1;           // source whose full parent array sits in exact slot 0
-    int32_t* dPath = nullptr;       // path walk output (+ length), shd_pe_get_path
+    PathOne* dPath = nullptr;       // shd_pe_get_path's one-request staging, its n vertices behind it
     int32_t rowsCap = 0;
     SparseLaunch cfg{};
     int exactGrid = 0, exactHc = 1;
@@ -1455,19 +1463,18 @@ static const BatchLaunch& post_launch(const Shard* sh, const BatchTrial* trial) 
     return trial ? trial->post : sh->plan.post;
 }
 
-// (orderOut / roundHook: shd_pe_get_paths -- the batch order the rounds run
-// in, handed out before the first launch, and the per-round hook of
-// batch_rounds; split kernels only)
+// (batchOrder / roundHook: shd_pe_get_paths -- batch_order of these rows, which
+// that caller needs first, and batch_rounds' per-round hook; split kernels only)
 static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, ExactWork& x,
-                         BatchTrial* trial, std::vector<int32_t>* orderOut = nullptr,
+                         BatchTrial* trial, const std::vector<int32_t>* batchOrder = nullptr,
                          const RoundHook* roundHook = nullptr) {
     ShdPeStats& st = sh->stats;
     int rc;
     if ((rc = ensure_batch(pe, sh))) return rc;
     const BatchLaunch& relax = relax_launch(sh, trial);
     int32_t nB = 0;
-    const std::vector<int32_t> order = batch_order(pe, relax.lb, pos, cnt, nB);
-    if (orderOut) *orderOut = order;
+    const std::vector<int32_t> order = batchOrder ? *batchOrder : batch_order(pe, relax.lb, pos, cnt, nB);
+    nB = (int32_t)(order.size() / (size_t)relax.lb);
     HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
     if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
     if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
@@ -2142,6 +2149,17 @@ extern "C" int shd_pe_get_rows(ShdPe* pe, int32_t start, int32_t count, double* 
     return get_rows_staged(pe, start, count, lat, rel, hops, pred, flags);
 }
 
+// The exact kernel for the path code (row i of dRows leaves its parents in scratch slot i;
+// dSlots: early-stop rows).  It reuses slot 0: shd_pe_get_path's cached parents do not survive it.
+static int paths_emulate(ShdPe* pe, Shard* sh, const int32_t* dRows, int32_t n, int32_t grid,
+                         const int32_t* dSlots) {
+    sh->pathSrc = -1;
+    launch_exact_rows(sh->dg, sh->tab, sh->sc, dRows, n, grid, sh->exactHc, pe->tu.exactHc > 0, dSlots,
+                      sh->tie, nullptr, sh->stream);
+    HIPCHK(hipGetLastError());
+    return SHD_PE_OK;
+}
+
 extern "C" int shd_pe_get_path(ShdPe* pe, int32_t srcVertex, int32_t dstVertex, int32_t* verts,
                                int32_t cap, int32_t* len) {
     if (!pe || !verts || !len || cap < 1) return SHD_PE_EINVAL;
@@ -2171,45 +2189,47 @@ extern "C" int shd_pe_get_path(ShdPe* pe, int32_t srcVertex, int32_t dstVertex, 
     if (rc) return rc;
     if (!sh->dPath) {
         void* p;
-        if ((rc = dev_alloc(sh, &p, ((size_t)g.n + 64) * 4))) return rc;
-        sh->dPath = (int32_t*)p;
+        if ((rc = dev_alloc(sh, &p, sizeof(PathOne) + (size_t)g.n * 4))) return rc;
+        sh->dPath = (PathOne*)p;
     }
     if (sh->pathSrc != srcVertex) {
         // igraph's whole Dijkstra for this source (full 2-wheap emulation,
         // one wave): every vertex popped before the last target keeps its
         // chosen IN-arc in slot 0; the row it rewrites is the table's own
         HIPCHK(hipMemcpyAsync(sh->dRows, &ps, 4, hipMemcpyHostToDevice, sh->stream));
-        launch_exact_rows(sh->dg, sh->tab, sh->sc, sh->dRows, 1, 1, sh->exactHc, pe->tu.exactHc > 0,
-                          nullptr, sh->tie, nullptr, sh->stream);
-        HIPCHK(hipGetLastError());
+        if ((rc = paths_emulate(pe, sh, sh->dRows, 1, 1, nullptr))) return rc;
         sh->pathSrc = srcVertex;
     }
-    int32_t* dLen = sh->dPath + g.n + 32;
-    // reachability from the row the emulation just wrote: an unreached
-    // target has no parent chain in slot 0 (its P entry is whatever an
-    // earlier row left there), so it must not be walked
-    {
-        uint8_t f = 0;
-        const size_t cell = (size_t)(ps - sh->tab.rowStart) * pe->attached.size() + pe->posOf[dstVertex];
-        HIPCHK(hipMemcpyAsync(&f, sh->tab.flags + cell, 1, hipMemcpyDeviceToHost, sh->stream));
-        HIPCHK(hipStreamSynchronize(sh->stream));
-        if (f & F_UNREACHABLE) return SHD_PE_EUNREACHABLE;
-    }
-    // device ids of s and t (the batched path relabels vertices)
-    int32_t sD = srcVertex, tD = dstVertex;
-    if (!pe->devOf.empty()) { sD = pe->devOf[srcVertex]; tD = pe->devOf[dstVertex]; }
-    launch_path_walk(sh->dg, sh->sc.pred, sD, tD, sh->dPath, std::min<int32_t>(cap, g.n + 1), dLen,
-                     (int32_t)g.nArcs(), sh->stream);
-    HIPCHK(hipGetLastError());
-    int32_t n = 0;
-    HIPCHK(hipMemcpyAsync(&n, dLen, 4, hipMemcpyDeviceToHost, sh->stream));
+    // the cell of the row the emulation wrote, judged as k_paths_size judges it: an unreached
+    // target has no parent chain in slot 0 (its P entry is whatever an earlier row left there), so
+    // it must not be walked; hops gives the length.  (F_NOEDGE: a complete graph's table)
+    uint8_t f = 0;
+    int32_t hops = 0;
+    const size_t cell = (size_t)(ps - sh->tab.rowStart) * pe->attached.size() + pe->posOf[dstVertex];
+    HIPCHK(hipMemcpyAsync(&f, sh->tab.flags + cell, 1, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipMemcpyAsync(&hops, sh->tab.hops + cell, 4, hipMemcpyDeviceToHost, sh->stream));
     HIPCHK(hipStreamSynchronize(sh->stream));
-    if (n == -2) return SHD_PE_EINVAL;            // cap too small for the path
-    if (n < 0) return SHD_PE_EUNREACHABLE;
-    std::vector<int32_t> rev(n);
-    HIPCHK(hipMemcpy(rev.data(), sh->dPath, (size_t)n * 4, hipMemcpyDeviceToHost));
-    for (int32_t k = 0; k < n; ++k) verts[k] = rev[n - 1 - k];
-    *len = n;
+    if (f & F_UNREACHABLE) return SHD_PE_EUNREACHABLE;
+    if (hops < 1 || hops >= g.n) return SHD_PE_EHIP;
+    const int32_t L = hops + 1;
+    if (L > cap) return SHD_PE_EINVAL;            // cap too small for the path
+    // one request of k_paths_walk over slot 0, in device ids (the batched path relabels vertices)
+    const bool relabelled = !pe->devOf.empty();
+    PathOne one{0, L, 0, PathReq{0, 0, relabelled ? pe->devOf[srcVertex] : srcVertex,
+                                 relabelled ? pe->devOf[dstVertex] : dstVertex}, 0, {}};
+    PathOne* const d = sh->dPath;
+    int32_t* const dVerts = reinterpret_cast<int32_t*>(d + 1);
+    HIPCHK(hipMemcpyAsync(d, &one, sizeof(one), hipMemcpyHostToDevice, sh->stream));
+    launch_paths_walk(sh->dg, PathsWalkArgs{&d->req, 1, sh->sc.pred, sh->sc.stride, (int32_t)g.nArcs(), &d->len,
+                                            &d->off, dVerts, &d->failed, &d->nFailed}, sh->stream);
+    HIPCHK(hipGetLastError());
+    std::vector<int32_t> path((size_t)L);
+    HIPCHK(hipMemcpyAsync(&one.failed, &d->failed, 1, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipMemcpyAsync(path.data(), dVerts, (size_t)L * 4, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    if (one.failed) return SHD_PE_EUNREACHABLE;   // the walk did not arrive at the source
+    std::copy(path.begin(), path.end(), verts);
+    *len = L;
     return SHD_PE_OK;
 }
 
@@ -2233,6 +2253,7 @@ struct PathsStage {
     double *hopLat = nullptr, *hopRel = nullptr;
     int64_t entries = 0;             // capacity of verts / hopLat / hopRel
     std::vector<int32_t> hLen, hStat;
+    std::vector<PathReq> hTrivial, hWalk;   // `reqs` on the host: [trivial | emulation], until the copy-out
     ~PathsStage() {
         if (mem.empty()) return;
         (void)hipSetDevice(device);
@@ -2256,8 +2277,62 @@ struct PathsCall {
     int64_t entries;                 // output entries per chunk
     bool hops;
     std::vector<PathsStage> st;      // per local shard
-    std::vector<int32_t> slotOf;     // table position -> its place among a chunk's unique sources, -1
+    int64_t c0 = 0;                  // the chunk at hand: requests [c0, c0 + cnt)
+    int32_t cnt = 0;
     double ms = 0.0;
+};
+
+// The requests of a launch (sorted by slot) whose slot lies in [lo, hi): [first, second).
+std::pair<size_t, size_t> reqs_in(const std::vector<PathReq>& reqs, int32_t lo, int32_t hi) {
+    const auto below = [](const PathReq& q, int32_t v) { return q.slot < v; };
+    const auto a = std::lower_bound(reqs.begin(), reqs.end(), lo, below);
+    return {(size_t)(a - reqs.begin()), (size_t)(std::lower_bound(a, reqs.end(), hi, below) - reqs.begin())};
+}
+
+// The requests of a chunk that need a parent walk, as one shard answers them:
+// what the tiers pass along.  Each tier serves what it can and keeps the rest.
+struct PathsWork {
+    std::vector<int32_t> uniq;       // the unique sources: table positions in order of first appearance
+    std::vector<PathReq> reqs;       // the requests, sorted by the place of their source in uniq; here
+                                     // `slot` is that place (a tier's upload carries the slot it walks)
+
+    // from the chunk's requests that shard k answers (hLen > 0), less [s] and,
+    // on a complete graph, [s, t]; s / t in device ids
+    void build(const ShdPe* pe, const PathsCall& c, size_t k) {
+        std::vector<int32_t> place(pe->attached.size(), -1);     // table position -> place in uniq
+        const bool relabelled = !pe->devOf.empty();
+        for (int32_t i = 0; i < c.cnt && pe->mode != 2; ++i) {
+            const int32_t sv = c.src[c.c0 + i], tv = c.dst[c.c0 + i];
+            if (c.st[k].hLen[(size_t)i] <= 0 || sv == tv) continue;
+            int32_t& p = place[(size_t)pe->posOf[sv]];
+            if (p < 0) {
+                p = (int32_t)uniq.size();
+                uniq.push_back(pe->posOf[sv]);
+            }
+            reqs.push_back(PathReq{i, p, relabelled ? pe->devOf[sv] : sv, relabelled ? pe->devOf[tv] : tv});
+        }
+        std::stable_sort(reqs.begin(), reqs.end(),
+                         [](const PathReq& a, const PathReq& b) { return a.slot < b.slot; });
+    }
+    // Keeps the requests i with stay[i] and the sources of those, in order, places renumbered.
+    // Returns the number of sources dropped: those whose every request the tier served.
+    int64_t keep(const std::vector<uint8_t>& stay) {
+        std::vector<int32_t> to(uniq.size(), -1);
+        size_t nu = 0, nr = 0;
+        for (size_t i = 0; i < reqs.size(); ++i) {
+            if (!stay[i]) continue;
+            const size_t was = (size_t)reqs[i].slot;             // (>= nu: the places only shrink)
+            if (to[was] < 0) {
+                to[was] = (int32_t)nu;
+                uniq[nu++] = uniq[was];
+            }
+            reqs[nr] = reqs[i];
+            reqs[nr++].slot = to[was];
+        }
+        reqs.resize(nr);
+        uniq.resize(nu);
+        return (int64_t)(to.size() - nu);
+    }
 };
 
 }  // namespace
@@ -2321,268 +2396,200 @@ static int paths_size_chunk(ShdPe* pe, PathsCall& c, size_t k, int64_t c0, int32
     return SHD_PE_OK;
 }
 
-// The batch tier serves shards on the split batch kernels (the C4 / C5
-// default); every other path (non-split, sparse, dense, forceMode 3, latFold
-// multigraphs) goes to the grouped emulation alone.  SHDPE_PATHS_FAST=0: off.
-static bool paths_batch_tier_applies(const ShdPe* pe, const Shard* sh) {
-    return pe->tu.pathsFast != 0 && pe->mode == 1 && pe->batched && pe->opt.forceMode != 3 &&
-           !pe->hg.latFold && sh->plan.relax.split != 0;
+// k_paths_walk over the stage's arrays on the parent arrays at `parents`.
+static int paths_walk(const ShdPe* pe, Shard* sh, const PathsStage& s, const PathReq* dReqs, size_t nReqs,
+                      const int32_t* parents, int64_t stride, int counter) {
+    launch_paths_walk(sh->dg, PathsWalkArgs{dReqs, (int32_t)nReqs, parents, stride, (int32_t)pe->hg.nArcs(),
+                                            s.len, s.off, s.verts, s.failed, s.nFailed + counter}, sh->stream);
+    HIPCHK(hipGetLastError());
+    return SHD_PE_OK;
 }
 
-// Batch tier: one relax + post pass of the split batch kernels over the
-// chunk's unique sources (`uniq`, table positions), and after each round's post
-// kernel and tie export one k_paths_walk_dist over the requests (`walk`:
-// place of the source in uniq, request) whose source sits in that round, on
-// the round's persisted distance arrays.  The pass stores no table row
-// (BatchTrial::noTable): the table is not touched here at all.
-// Tie tier: the rows the pass gave a tie slot (early-stop tie rows) then run
-// what the exact stage runs for them -- relevance scan and the emulation up to
-// the row's tie threshold, which leaves the final parents in tie.P of the
-// slot -- without k_tie_write (the table holds the row already), and one
-// k_paths_walk over their requests on tie.P.  A slot that failed the
-// emulation's consistency check, and a walk that did not arrive, hand on.
-// On return uniq / walk hold what goes to the grouped emulation only (places
-// renumbered): rows the pass sent to the full emulation, and every request
-// handed on.  ShdPeStats is put back as it was.
-static int paths_batch_tier(ShdPe* pe, PathsCall& c, size_t k, int32_t cnt, std::vector<int32_t>& uniq,
-                            std::vector<std::pair<int32_t, PathReq>>& walk) {
+// The requests without a walk: [s] and, on a complete graph, [s, t] (caller's ids).
+static int paths_trivial(ShdPe* pe, PathsCall& c, size_t k, PathsWork&) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    s.hTrivial.clear();
+    for (int32_t i = 0; i < c.cnt; ++i) {
+        const int32_t sv = c.src[c.c0 + i], tv = c.dst[c.c0 + i];
+        if (s.hLen[(size_t)i] > 0 && (sv == tv || pe->mode == 2)) s.hTrivial.push_back(PathReq{i, -1, sv, tv});
+    }
+    if (s.hTrivial.empty()) return SHD_PE_OK;
+    HIPCHK(hipMemcpyAsync(s.reqs, s.hTrivial.data(), s.hTrivial.size() * sizeof(PathReq), hipMemcpyHostToDevice,
+                          sh->stream));
+    return paths_walk(pe, sh, s, s.reqs, s.hTrivial.size(), sh->sc.pred, sh->sc.stride, 0);
+}
+
+// Batch tier, on shards that run the split batch kernels (the C4 / C5 default;
+// SHDPE_PATHS_FAST=0: off; not sparse, dense, forceMode 3 or latFold): one relax
+// + post pass over the work set's sources, and after each round's post kernel
+// and tie export one k_paths_walk_dist over the requests whose source sits in
+// that round, on the round's persisted distance arrays.  The pass stores no
+// table row (BatchTrial::noTable) and ShdPeStats is put back as it was.
+// Served: the requests of the rows the pass resolved, less those whose walk
+// failed its checks (handed on).  The rows it flagged keep all requests and go
+// to `x`: those with a tie slot first (row and slot), then the full emulation's.
+static int paths_tier_batch(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w, ExactWork& x) {
     Shard* sh = pe->shards[k].get();
     PathsStage& s = c.st[k];
     int rc;
+    if (w.reqs.empty() || !pe->tu.pathsFast || pe->mode != 1 || !pe->batched || pe->opt.forceMode == 3 ||
+        pe->hg.latFold || !sh->plan.relax.split)
+        return SHD_PE_OK;
     if ((rc = ensure_batch(pe, sh))) return rc;
     if (!sh->plan.relax.split) return SHD_PE_OK;
-    const ShdPeStats savedStats = sh->stats;
-    BatchTrial trial;                                    // the plan's picks; for a cooperative relax the
-    trial.relax = sh->plan.relax;                        // plain kernel of the post variant (as ensure_batch)
-    if (trial.relax.coop >= 2) trial.relax = sh->plan.post;
+    BatchTrial trial;   // the plan's picks; for a cooperative relax the post variant's plain kernel (as ensure_batch)
+    trial.relax = sh->plan.relax.coop >= 2 ? sh->plan.post : sh->plan.relax;
     trial.relax.coop = 0;
     trial.post = sh->plan.post;
     trial.noTable = true;
     const int32_t LB = trial.relax.lb;
-    std::vector<int32_t> order;                          // batch order of the pass: table positions, -1 pads
-    std::vector<std::pair<int32_t, PathReq>> byOrd;      // (index of the source in order, request)
-    std::vector<PathReq> breqs;
-    const RoundHook hook = [&](int32_t r0, int32_t rn) -> int {
-        if (byOrd.empty()) {
-            for (size_t i = 0; i < order.size(); ++i)
-                if (order[i] >= 0) c.slotOf[(size_t)order[i]] = (int32_t)i;
-            byOrd.reserve(walk.size());
-            for (const auto& w : walk) {
-                PathReq q = w.second;
-                q.slot = c.slotOf[(size_t)uniq[(size_t)w.first]];
-                byOrd.push_back({q.slot, q});
-            }
-            for (int32_t p : uniq) c.slotOf[(size_t)p] = -1;
-            std::stable_sort(byOrd.begin(), byOrd.end(),
-                             [](const auto& a, const auto& b) { return a.first < b.first; });
-            breqs.resize(byOrd.size());
-            for (size_t i = 0; i < byOrd.size(); ++i) breqs[i] = byOrd[i].second;
-            HIPCHK(hipMemcpyAsync(s.reqsB, breqs.data(), breqs.size() * sizeof(PathReq), hipMemcpyHostToDevice,
-                                  sh->stream));
-        }
-        const auto cmp = [](const std::pair<int32_t, PathReq>& a, int32_t v) { return a.first < v; };
-        const size_t lo = std::lower_bound(byOrd.begin(), byOrd.end(), r0 * LB, cmp) - byOrd.begin();
-        const size_t hi = std::lower_bound(byOrd.begin(), byOrd.end(), (r0 + rn) * LB, cmp) - byOrd.begin();
-        const PathsDistArgs a{s.reqsB + lo, (int32_t)(hi - lo), LB, r0 * LB, sh->dBatchAmb + (size_t)r0 * LB,
-                              s.len, s.off, s.verts, s.failed};
+    // the pass's batch order (table positions, -1 pads); the requests by their source's index in it
+    int32_t nB = 0;
+    const std::vector<int32_t> order = batch_order(pe, LB, w.uniq.data(), (int32_t)w.uniq.size(), nB);
+    std::vector<int32_t> ordOf(pe->attached.size());     // by table position
+    for (size_t i = 0; i < order.size(); ++i)
+        if (order[i] >= 0) ordOf[(size_t)order[i]] = (int32_t)i;
+    std::vector<size_t> at(order.size() + 1, 0);         // counting sort: first request of each index
+    for (const PathReq& q : w.reqs) ++at[(size_t)ordOf[(size_t)w.uniq[(size_t)q.slot]] + 1];
+    for (size_t i = 0; i < order.size(); ++i) at[i + 1] += at[i];
+    std::vector<PathReq> breqs(w.reqs.size());
+    for (PathReq q : w.reqs) {
+        q.slot = ordOf[(size_t)w.uniq[(size_t)q.slot]];
+        breqs[at[(size_t)q.slot]++] = q;
+    }
+    HIPCHK(hipMemcpyAsync(s.reqsB, breqs.data(), breqs.size() * sizeof(PathReq), hipMemcpyHostToDevice, sh->stream));
+    const RoundHook walkRound = [&](int32_t r0, int32_t rn) -> int {
+        const std::pair<size_t, size_t> r = reqs_in(breqs, r0 * LB, (r0 + rn) * LB);
+        const PathsDistArgs a{s.reqsB + r.first, (int32_t)(r.second - r.first), LB, r0 * LB,
+                              sh->dBatchAmb + (size_t)r0 * LB, s.len, s.off, s.verts, s.failed};
         launch_paths_walk_dist(sh->dg, sh->bsc, a, sh->stream);
         HIPCHK(hipGetLastError());
         return SHD_PE_OK;
     };
-    ExactWork x;
-    rc = relax_batched(pe, sh, uniq.data(), (int32_t)uniq.size(), x, &trial, &order, &hook);
-    sh->stats = savedStats;
+    const ShdPeStats savedStats = sh->stats;
+    rc = relax_batched(pe, sh, w.uniq.data(), (int32_t)w.uniq.size(), x, &trial, &order, &walkRound);
+    sh->stats = savedStats;                              // (relax_batched synchronised: breqs is read)
     if (rc) return rc;
-    std::vector<uint8_t> failed((size_t)cnt), failedTie;
-    HIPCHK(hipMemcpyAsync(failed.data(), s.failed, (size_t)cnt, hipMemcpyDeviceToHost, sh->stream));
+    std::vector<uint8_t> failed((size_t)c.cnt), flagged(pe->attached.size(), 0), stay(w.reqs.size());
+    HIPCHK(hipMemcpyAsync(failed.data(), s.failed, failed.size(), hipMemcpyDeviceToHost, sh->stream));
     HIPCHK(hipStreamSynchronize(sh->stream));
-    HIPCHK(hipMemsetAsync(s.failed, 0, (size_t)cnt, sh->stream));
-    // per unique source (place in uniq) what the pass made of it: 0 resolved,
-    // 1 + i: early-stop tie row i of x (its slot x.slots[i]), -1: full emulation
-    int32_t nTie = 0;
-    while (nTie < (int32_t)x.slots.size() && x.slots[(size_t)nTie] >= 0) ++nTie;
-    std::vector<int32_t> cls(uniq.size(), 0);
-    for (size_t i = 0; i < uniq.size(); ++i) c.slotOf[(size_t)uniq[i]] = (int32_t)i;
-    for (size_t j = 0; j < x.rows.size(); ++j)
-        cls[(size_t)c.slotOf[(size_t)x.rows[j]]] = (int32_t)j < nTie ? 1 + (int32_t)j : -1;
-    for (int32_t p : uniq) c.slotOf[(size_t)p] = -1;
-    // tie tier: the early-stop part of the exact stage on those rows (no table
-    // write), then their requests walked on tie.P
-    std::vector<uint8_t> slotBad((size_t)nTie, 0);
-    if (nTie > 0) {
-        std::vector<PathReq> treqs;
-        for (const auto& w : walk) {
-            const int32_t ci = cls[(size_t)w.first];
-            if (ci <= 0) continue;
-            PathReq q = w.second;
-            q.slot = x.slots[(size_t)ci - 1];
-            treqs.push_back(q);
-        }
-        sh->pathSrc = -1;                                // the exact kernel reuses scratch slot 0
-        HIPCHK(hipMemcpyAsync(sh->dRows, x.rows.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
-        HIPCHK(hipMemcpyAsync(sh->dSlots, x.slots.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
-        HIPCHK(hipMemcpyAsync(s.reqsB, treqs.data(), treqs.size() * sizeof(PathReq), hipMemcpyHostToDevice,
-                              sh->stream));
-        scan_tie_slots(pe, sh, x.slots, nTie);
-        launch_exact_rows(sh->dg, sh->tab, sh->sc, sh->dRows, nTie, sh->exactGrid, sh->exactHc,
-                          pe->tu.exactHc > 0, sh->dSlots, sh->tie, nullptr, sh->stream);
-        HIPCHK(hipGetLastError());
-        const PathsWalkArgs wt{s.reqsB, (int32_t)treqs.size(), sh->tie.P, sh->tie.n, (int32_t)pe->hg.nArcs(),
-                               s.len, s.off, s.verts, s.failed, s.nFailed + 2};
-        launch_paths_walk(sh->dg, wt, sh->stream);
-        HIPCHK(hipGetLastError());
-        failedTie.resize((size_t)cnt);
-        HIPCHK(hipMemcpyAsync(failedTie.data(), s.failed, (size_t)cnt, hipMemcpyDeviceToHost, sh->stream));
-        std::vector<int32_t> redo;                       // (synchronises; treqs is read by then)
-        if ((rc = failed_tie_rows(sh, x.rows.data(), x.slots.data(), nTie, sh->tie.cap, redo))) return rc;
-        HIPCHK(hipMemsetAsync(s.failed, 0, (size_t)cnt, sh->stream));
-        for (int32_t i = 0, r = 0; i < nTie && r < (int32_t)redo.size(); ++i)
-            if (x.rows[(size_t)i] == redo[(size_t)r]) { slotBad[(size_t)i] = 1; ++r; }
+    HIPCHK(hipMemsetAsync(s.failed, 0, failed.size(), sh->stream));
+    for (int32_t p : x.rows) flagged[(size_t)p] = 1;     // (by table position)
+    for (size_t i = 0; i < w.reqs.size(); ++i) {
+        const bool rowLeft = flagged[(size_t)w.uniq[(size_t)w.reqs[i].slot]];
+        stay[i] = rowLeft || failed[(size_t)w.reqs[i].req];
+        pe->pathsInfo[3] += stay[i] && !rowLeft;
     }
-    // what goes on to the emulation: rows the pass sent to the full emulation,
-    // and the requests that left a tier after its check
-    std::vector<int32_t> uniq2, place2(uniq.size(), -1);
-    std::vector<std::pair<int32_t, PathReq>> walk2;
-    std::vector<uint8_t> served(uniq.size(), 1);
-    for (const auto& w : walk) {
-        const int32_t ci = cls[(size_t)w.first];
-        const size_t rq = (size_t)w.second.req;
-        const bool left = ci == 0 ? failed[rq] != 0 : ci > 0 && (slotBad[(size_t)ci - 1] || failedTie[rq]);
-        if (ci >= 0 && !left) continue;
-        served[(size_t)w.first] = 0;
-        pe->pathsInfo[3] += left;
-        if (place2[(size_t)w.first] < 0) {
-            place2[(size_t)w.first] = (int32_t)uniq2.size();
-            uniq2.push_back(uniq[(size_t)w.first]);
-        }
-        walk2.push_back({place2[(size_t)w.first], w.second});
-    }
-    for (size_t i = 0; i < served.size(); ++i)
-        if (served[i]) pe->pathsInfo[cls[i] > 0 ? 1 : 0] += 1;
-    std::stable_sort(walk2.begin(), walk2.end(), [](const auto& a, const auto& b) { return a.first < b.first; });
-    uniq.swap(uniq2);
-    walk.swap(walk2);
+    pe->pathsInfo[0] += w.keep(stay);
     return SHD_PE_OK;
 }
 
-// Paths of requests [c0, c0 + cnt) that shard k answers (paths_size_chunk ran):
-// the grouped emulation of their unique sources, the walks, the hop attributes,
-// and the copy into the caller's arrays at the global offsets.
-static int paths_extract_chunk(ShdPe* pe, PathsCall& c, size_t k, int64_t c0, int32_t cnt) {
+// Tie tier: the early-stop tie rows of the pass (the head of `tie`) run what
+// the exact stage runs for them -- relevance scan and the emulation up to the
+// row's tie threshold, which leaves the final parents in tie.P of the slot --
+// without k_tie_write (the table holds the row already), and one k_paths_walk
+// over their requests on tie.P.  Handed on: the rows whose slot failed the
+// emulation's consistency check, and the walks that did not arrive.
+static int paths_tier_tie(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w, const ExactWork& tie) {
     Shard* sh = pe->shards[k].get();
     PathsStage& s = c.st[k];
-    int64_t total = 0;
-    for (int32_t i = 0; i < cnt; ++i) total += s.hLen[(size_t)i];
-    if (total == 0) return SHD_PE_OK;
-    int rc = paths_stage_extract(pe, c, k);
-    if (rc) return rc;
-    if (total > s.entries) return SHD_PE_EINVAL;         // (the chunking keeps it within)
-    sh->pathSrc = -1;                                    // shd_pe_get_path's cached parents do not survive the call
-    // requests by the place of their source among the chunk's unique sources
-    // (first appearance); those without a walk first
-    std::vector<int32_t> uniq;                           // table positions
-    std::vector<PathReq> reqs;
-    std::vector<std::pair<int32_t, PathReq>> walk;       // (place of the source, request)
-    for (int32_t i = 0; i < cnt; ++i) {
-        if (s.hLen[(size_t)i] <= 0) continue;
-        const int32_t sv = c.src[c0 + i], tv = c.dst[c0 + i];
-        if (sv == tv || pe->mode == 2) {
-            reqs.push_back(PathReq{i, -1, sv, tv});
-            continue;
-        }
-        const int32_t ps = pe->posOf[sv];
-        if (c.slotOf[ps] < 0) {
-            c.slotOf[ps] = (int32_t)uniq.size();
-            uniq.push_back(ps);
-        }
-        const bool relabelled = !pe->devOf.empty();
-        walk.push_back({c.slotOf[ps], PathReq{i, 0, relabelled ? pe->devOf[sv] : sv,
-                                               relabelled ? pe->devOf[tv] : tv}});
-    }
-    for (int32_t p : uniq) c.slotOf[p] = -1;
-    std::stable_sort(walk.begin(), walk.end(),
-                     [](const auto& a, const auto& b) { return a.first < b.first; });
-    const int32_t G = std::min(c.group, sh->exactGrid);
-    HIPCHK(hipEventRecord(sh->ev0, sh->stream));
-    HIPCHK(hipMemsetAsync(s.failed, 0, (size_t)cnt, sh->stream));
-    HIPCHK(hipMemsetAsync(s.nFailed, 0, 16, sh->stream));
-    PathsWalkArgs wa{s.reqs, 0, sh->sc.pred, sh->sc.stride, (int32_t)pe->hg.nArcs(), s.len, s.off, s.verts,
-                     s.failed, s.nFailed};
-    if (!reqs.empty()) {
-        HIPCHK(hipMemcpyAsync(s.reqs, reqs.data(), reqs.size() * sizeof(PathReq), hipMemcpyHostToDevice,
-                              sh->stream));
-        wa.nReqs = (int32_t)reqs.size();
-        launch_paths_walk(sh->dg, wa, sh->stream);
-        HIPCHK(hipGetLastError());
-    }
-    // the batch tier first where the shard runs the split batch kernels; what
-    // it hands on (and everything, elsewhere) goes to the grouped emulation
-    if (!walk.empty() && paths_batch_tier_applies(pe, sh) &&
-        (rc = paths_batch_tier(pe, c, k, cnt, uniq, walk)))   // (leaves in uniq / walk what it handed on)
+    int32_t nTie = 0;
+    while (nTie < (int32_t)tie.slots.size() && tie.slots[(size_t)nTie] >= 0) ++nTie;
+    if (nTie == 0) return SHD_PE_OK;
+    int rc;
+    std::vector<int32_t> tieSlot(pe->attached.size(), -1);   // table position -> its tie slot; -2: a bad one
+    for (int32_t j = 0; j < nTie; ++j) tieSlot[(size_t)tie.rows[(size_t)j]] = tie.slots[(size_t)j];
+    std::vector<PathReq> treqs;
+    for (const PathReq& q : w.reqs)
+        if (tieSlot[(size_t)w.uniq[(size_t)q.slot]] >= 0)
+            treqs.push_back(PathReq{q.req, tieSlot[(size_t)w.uniq[(size_t)q.slot]], q.s, q.t});
+    HIPCHK(hipMemcpyAsync(sh->dRows, tie.rows.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemcpyAsync(sh->dSlots, tie.slots.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemcpyAsync(s.reqsB, treqs.data(), treqs.size() * sizeof(PathReq), hipMemcpyHostToDevice, sh->stream));
+    scan_tie_slots(pe, sh, tie.slots, nTie);
+    if ((rc = paths_emulate(pe, sh, sh->dRows, nTie, sh->exactGrid, sh->dSlots)) ||
+        (rc = paths_walk(pe, sh, s, s.reqsB, treqs.size(), sh->tie.P, sh->tie.n, 2)))
         return rc;
-    // igraph's whole Dijkstra for each unique source, a group per launch: row
-    // i of the group runs in workgroup i and leaves every popped vertex's
-    // chosen IN-arc in scratch slot i (no tie slots: full emulations).  The
-    // emulation rewrites the table rows with the same values but marks every
-    // entry F_EXACT: the rows' flag bytes are saved before and put back after.
-    // (rows and requests of every group are uploaded once, up front: no host
-    // buffer is reused while a copy may still read it)
-    std::vector<PathReq> wreqs(walk.size());
-    for (size_t i = 0; i < walk.size(); ++i) {
-        wreqs[i] = walk[i].second;
-        wreqs[i].slot = walk[i].first % G;
+    std::vector<uint8_t> failed((size_t)c.cnt), stay(w.reqs.size());
+    HIPCHK(hipMemcpyAsync(failed.data(), s.failed, failed.size(), hipMemcpyDeviceToHost, sh->stream));
+    std::vector<int32_t> redo;                           // (synchronises; treqs is read by then)
+    if ((rc = failed_tie_rows(sh, tie.rows.data(), tie.slots.data(), nTie, sh->tie.cap, redo))) return rc;
+    HIPCHK(hipMemsetAsync(s.failed, 0, failed.size(), sh->stream));
+    for (int32_t p : redo) tieSlot[(size_t)p] = -2;
+    for (size_t i = 0; i < w.reqs.size(); ++i) {
+        const int32_t sl = tieSlot[(size_t)w.uniq[(size_t)w.reqs[i].slot]];
+        stay[i] = sl == -1 || sl == -2 || failed[(size_t)w.reqs[i].req];
+        pe->pathsInfo[3] += stay[i] && sl != -1;
     }
-    PathReq* const dWalk = s.reqs + reqs.size();         // behind the requests without a walk
-    if (!uniq.empty()) {
-        HIPCHK(hipMemcpyAsync(s.rows, uniq.data(), uniq.size() * 4, hipMemcpyHostToDevice, sh->stream));
-        HIPCHK(hipMemcpyAsync(dWalk, wreqs.data(), wreqs.size() * sizeof(PathReq), hipMemcpyHostToDevice,
-                              sh->stream));
-    }
-    size_t w0 = 0;
-    for (size_t u0 = 0; u0 < uniq.size(); u0 += (size_t)G) {
-        const int32_t g = (int32_t)std::min<size_t>((size_t)G, uniq.size() - u0);
-        sh->pathSrc = -1;                                // shd_pe_get_path's slot 0 is reused
+    pe->pathsInfo[1] += w.keep(stay);
+    return SHD_PE_OK;
+}
+
+// Grouped emulation, the last tier: igraph's whole Dijkstra for each source
+// left, a group per launch: row i of the group runs in workgroup i and leaves
+// every popped vertex's chosen IN-arc in scratch slot i (no tie slots: full
+// emulations); one k_paths_walk per group.  The emulation rewrites the table
+// rows with the same values but marks every entry F_EXACT: the rows' flag
+// bytes are saved before and put back after.  (Rows and requests are uploaded
+// once, from w.uniq and the stage's hWalk, which stay as they are until the
+// chunk's copy-out has synchronised.)
+static int paths_tier_emulation(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    if (w.uniq.empty()) return SHD_PE_OK;
+    int rc;
+    const int32_t G = std::min(c.group, sh->exactGrid);
+    s.hWalk = w.reqs;
+    for (PathReq& q : s.hWalk) q.slot %= G;
+    PathReq* const dWalk = s.reqs + s.hTrivial.size();   // behind the requests without a walk
+    HIPCHK(hipMemcpyAsync(s.rows, w.uniq.data(), w.uniq.size() * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemcpyAsync(dWalk, s.hWalk.data(), s.hWalk.size() * sizeof(PathReq), hipMemcpyHostToDevice,
+                          sh->stream));
+    for (size_t u0 = 0; u0 < w.uniq.size(); u0 += (size_t)G) {
+        const int32_t g = (int32_t)std::min<size_t>((size_t)G, w.uniq.size() - u0);
+        const std::pair<size_t, size_t> r = reqs_in(w.reqs, (int32_t)u0, (int32_t)u0 + g);
         launch_paths_flags(sh->tab, s.rows + u0, g, s.flags, false, sh->stream);
-        launch_exact_rows(sh->dg, sh->tab, sh->sc, s.rows + u0, g, g, sh->exactHc, pe->tu.exactHc > 0,
-                          nullptr, sh->tie, nullptr, sh->stream);
+        if ((rc = paths_emulate(pe, sh, s.rows + u0, g, g, nullptr))) return rc;
         launch_paths_flags(sh->tab, s.rows + u0, g, s.flags, true, sh->stream);
         HIPCHK(hipGetLastError());
-        size_t w1 = w0;
-        while (w1 < walk.size() && walk[w1].first < (int32_t)u0 + g) ++w1;
-        wa.reqs = dWalk + w0;
-        wa.nReqs = (int32_t)(w1 - w0);
-        launch_paths_walk(sh->dg, wa, sh->stream);
-        HIPCHK(hipGetLastError());
-        w0 = w1;
+        if ((rc = paths_walk(pe, sh, s, dWalk + r.first, r.second - r.first, sh->sc.pred, sh->sc.stride, 0)))
+            return rc;
         pe->pathsInfo[2] += g;
         pe->pathsInfo[4] += 1;
     }
+    return SHD_PE_OK;
+}
+
+// The hop attributes of the chunk's paths and the copy into the caller's arrays
+// at the global offsets.
+static int paths_hops_and_copy_out(ShdPe* pe, PathsCall& c, size_t k, int64_t total) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
     if (c.hops) {
-        launch_paths_hops(sh->dgAux, s.off, cnt, total, s.verts, s.hopLat, s.hopRel, s.nFailed + 1, sh->stream);
+        launch_paths_hops(sh->dgAux, s.off, c.cnt, total, s.verts, s.hopLat, s.hopRel, s.nFailed + 1, sh->stream);
         HIPCHK(hipGetLastError());
     }
     HIPCHK(hipEventRecord(sh->ev1, sh->stream));
     int32_t nFailed[2] = {0, 0};
     HIPCHK(hipMemcpyAsync(nFailed, s.nFailed, 8, hipMemcpyDeviceToHost, sh->stream));
     const ShdPePathsOut& o = *c.out;
-    const int64_t* goff = o.offsets + c0;
-    if (pe->shards.size() == 1) {
-        // one shard answers every request: its compact order is the caller's
-        HIPCHK(hipMemcpyAsync(o.verts + goff[0], s.verts, (size_t)total * 4, hipMemcpyDeviceToHost, sh->stream));
-        if (o.hopLat)
-            HIPCHK(hipMemcpyAsync(o.hopLat + goff[0], s.hopLat, (size_t)total * 8, hipMemcpyDeviceToHost, sh->stream));
-        if (o.hopRel)
-            HIPCHK(hipMemcpyAsync(o.hopRel + goff[0], s.hopRel, (size_t)total * 8, hipMemcpyDeviceToHost, sh->stream));
-        HIPCHK(hipStreamSynchronize(sh->stream));
-    } else {
-        std::vector<int32_t> hv((size_t)total);
-        std::vector<double> hl(o.hopLat ? (size_t)total : 0), hr(o.hopRel ? (size_t)total : 0);
-        HIPCHK(hipMemcpyAsync(hv.data(), s.verts, (size_t)total * 4, hipMemcpyDeviceToHost, sh->stream));
-        if (o.hopLat) HIPCHK(hipMemcpyAsync(hl.data(), s.hopLat, (size_t)total * 8, hipMemcpyDeviceToHost, sh->stream));
-        if (o.hopRel) HIPCHK(hipMemcpyAsync(hr.data(), s.hopRel, (size_t)total * 8, hipMemcpyDeviceToHost, sh->stream));
-        HIPCHK(hipStreamSynchronize(sh->stream));
+    const int64_t* goff = o.offsets + c.c0;
+    // one shard answers every request: its compact order is the caller's, the
+    // DMA lands there; several: through host buffers, path by path
+    const bool direct = pe->shards.size() == 1;
+    std::vector<int32_t> hv(direct ? 0 : (size_t)total);
+    std::vector<double> hl(o.hopLat && !direct ? (size_t)total : 0), hr(o.hopRel && !direct ? (size_t)total : 0);
+    HIPCHK(hipMemcpyAsync(direct ? o.verts + goff[0] : hv.data(), s.verts, (size_t)total * 4,
+                          hipMemcpyDeviceToHost, sh->stream));
+    if (o.hopLat) HIPCHK(hipMemcpyAsync(direct ? o.hopLat + goff[0] : hl.data(), s.hopLat, (size_t)total * 8,
+                                        hipMemcpyDeviceToHost, sh->stream));
+    if (o.hopRel) HIPCHK(hipMemcpyAsync(direct ? o.hopRel + goff[0] : hr.data(), s.hopRel, (size_t)total * 8,
+                                        hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    if (!direct) {
         int64_t lo = 0;
-        for (int32_t i = 0; i < cnt; ++i) {
+        for (int32_t i = 0; i < c.cnt; ++i) {
             const int32_t L = s.hLen[(size_t)i];
             if (L <= 0) continue;
             std::memcpy(o.verts + goff[i], hv.data() + lo, (size_t)L * 4);
@@ -2596,6 +2603,31 @@ static int paths_extract_chunk(ShdPe* pe, PathsCall& c, size_t k, int64_t c0, in
     // without an edge, means the scratch parents are not what the table says
     if (nFailed[0] || nFailed[1]) return SHD_PE_EHIP;
     return SHD_PE_OK;
+}
+
+// Paths of the chunk's requests that shard k answers (paths_size_chunk ran):
+// the tiers in sequence, then the hop attributes and the copy-out.  Each tier
+// serves what it can of the work set, counts the sources it served in full
+// into pathsInfo, and leaves in the set exactly what it hands on.
+static int paths_extract_chunk(ShdPe* pe, PathsCall& c, size_t k) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    int64_t total = 0;
+    for (int32_t i = 0; i < c.cnt; ++i) total += s.hLen[(size_t)i];
+    if (total == 0) return SHD_PE_OK;
+    int rc = paths_stage_extract(pe, c, k);
+    if (rc) return rc;
+    if (total > s.entries) return SHD_PE_EINVAL;         // (the chunking keeps it within)
+    PathsWork w;
+    ExactWork tie;                                       // the rows the batch tier's pass flagged
+    w.build(pe, c, k);
+    HIPCHK(hipEventRecord(sh->ev0, sh->stream));
+    HIPCHK(hipMemsetAsync(s.failed, 0, (size_t)c.cnt, sh->stream));
+    HIPCHK(hipMemsetAsync(s.nFailed, 0, 16, sh->stream));
+    if ((rc = paths_trivial(pe, c, k, w)) || (rc = paths_tier_batch(pe, c, k, w, tie)) ||
+        (rc = paths_tier_tie(pe, c, k, w, tie)) || (rc = paths_tier_emulation(pe, c, k, w)))
+        return rc;
+    return paths_hops_and_copy_out(pe, c, k, total);
 }
 
 extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* dst, int64_t count,
@@ -2630,9 +2662,7 @@ extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* ds
     c.out = out;
     c.chunk = (int32_t)std::min<int64_t>(count, pe->tu.pathsChunk > 0 ? pe->tu.pathsChunk : PATHS_CHUNK);
     c.group = INT32_MAX;
-    for (auto& sh : pe->shards) {
-        c.group = std::min(c.group, sh->exactGrid);
-    }
+    for (auto& sh : pe->shards) c.group = std::min(c.group, sh->exactGrid);
     // (a chunk's unique sources of a shard fit its dBatchRows / dBatchAmb: they
     // are rows of the shard, so at most min(chunk, rowCount) <= rowsCap)
     c.chunk = std::min(c.chunk, 1 << 20);
@@ -2640,7 +2670,6 @@ extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* ds
     c.entries = std::max<int64_t>(PATHS_ENTRIES, (int64_t)g.n + 1);
     c.hops = out->hopLat || out->hopRel;
     c.st.resize(pe->shards.size());
-    c.slotOf.assign((size_t)T, -1);
     auto finish = [&](int r) {
         pe->pathsInfo[5] = (int64_t)std::llround(c.ms * 1000.0);
         return r;
@@ -2666,9 +2695,10 @@ extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* ds
     for (int64_t c0 = 0; c0 < count;) {
         int64_t c1 = c0 + 1;
         while (c1 < count && c1 - c0 < c.chunk && out->offsets[c1 + 1] - out->offsets[c0] <= c.entries) ++c1;
-        const int32_t cnt = (int32_t)(c1 - c0);
+        c.c0 = c0;
+        c.cnt = (int32_t)(c1 - c0);
         for (size_t k = 0; k < pe->shards.size(); ++k)
-            if ((rc = paths_size_chunk(pe, c, k, c0, cnt)) || (rc = paths_extract_chunk(pe, c, k, c0, cnt)))
+            if ((rc = paths_size_chunk(pe, c, k, c0, c.cnt)) || (rc = paths_extract_chunk(pe, c, k)))
                 return finish(rc);
         c0 = c1;
     }

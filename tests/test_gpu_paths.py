@@ -212,6 +212,36 @@ def test_bad_tie_slot_is_handed_on(E, corrupt, monkeypatch):
     eng.close()
 
 
+def test_partial_hand_on_counts_once(E, monkeypatch):
+    """A corrupted tie slot sends its row's requests through every tier: each
+    unique source is still counted once, the sources of the untouched tiers
+    keep their counter, and the bytes are those of the uncorrupted run."""
+    top, att, force, _ = _case("quantized_batched")
+    src, dst = _requests(att, n_src=att.shape[0], n_dst=3)
+    for s in np.unique(src):                              # (CPU) several targets per source
+        assert np.unique(dst[src == s]).shape[0] >= 2, s
+    n_uniq = np.unique(src[src != dst]).shape[0]
+    eng = E.Engine(top, att, force_mode=force)
+    ref = eng.get_paths(src, dst, hops=True)
+    ref_info = eng.paths_info()
+    eng.close()
+    monkeypatch.setenv("SHDPE_TIE_CORRUPT", "2")
+    eng = E.Engine(top, att, force_mode=force, debug_flags=E.DEBUG_ENV)
+    got = eng.get_paths(src, dst, hops=True)
+    info = eng.paths_info()
+    eng.close()
+    print(ref_info, info)
+    assert ref_info["batch"] + ref_info["tie"] + ref_info["emulated"] == n_uniq
+    assert info["batch"] + info["tie"] + info["emulated"] == n_uniq
+    # a source under `emulated` is in no other counter: the batch tier's sources
+    # are the same in both runs, and what the tie tier lost the emulation gained
+    assert info["emulated"] > ref_info["emulated"] and info["handed_on"] > 0
+    assert info["batch"] == ref_info["batch"]
+    assert info["emulated"] - ref_info["emulated"] == ref_info["tie"] - info["tie"]
+    for g, r in zip(got, ref):
+        assert g.tobytes() == r.tobytes()
+
+
 def test_grouping_and_chunking(E, oracle_mod, monkeypatch):
     """600 unique sources in emulation groups of 64 and staging chunks of 100
     requests: the same bytes as the unchunked call."""
@@ -267,6 +297,55 @@ def test_equals_loop_of_get_path(E):
     eng.get_paths(src, dst)
     assert eng.get_path(s, int(att[7])) == eng.get_paths([s], [int(att[7])])[1].tolist()
     assert eng.get_path(s, t) == one
+    eng.close()
+
+
+@pytest.mark.parametrize("force_mode", [0, 5])
+def test_get_path_cap_boundary(E, force_mode):
+    """shd_pe_get_path with a capacity of exactly the path's length returns the
+    path; one short is SHD_PE_EINVAL, and the refusal leaves the cached source
+    usable.  (force_mode 5 relabels the vertices on the device.)"""
+    top = G.random_sparse(500, 5, seed=36, quantum=1.0)
+    att = np.arange(0, 500, 2, dtype=np.int32)
+    rng = np.random.default_rng(11)
+    src = np.repeat(rng.choice(att, 3, replace=False), 20).astype(np.int32)
+    dst = rng.choice(att, src.shape[0]).astype(np.int32)
+    eng = E.Engine(top, att, force_mode=force_mode)
+    offsets, verts, status = eng.get_paths(src, dst)
+    lens = np.diff(offsets)
+    picks = [i for i in range(src.shape[0]) if status[i] == 0 and lens[i] >= 3][:5]
+    assert len(picks) == 5                                # (of the first source or two: the cached walk)
+    for i in picks:
+        s, t, n = int(src[i]), int(dst[i]), int(lens[i])
+        want = verts[offsets[i]:offsets[i + 1]].tolist()
+        assert eng.get_path(s, t, cap=n) == want, (s, t)
+        with pytest.raises(E.EngineError) as err:
+            eng.get_path(s, t, cap=n - 1)
+        assert err.value.code == E.EINVAL, (s, t)
+        assert eng.get_path(s, t) == want, (s, t)
+    eng.close()
+
+
+@pytest.mark.parametrize("force_mode", [0, 5])
+def test_get_path_many_targets_one_emulation(E, force_mode):
+    """One shd_pe_get_path per attached target of a source (the cached parent
+    array walked hundreds of times): path and code of shd_pe_get_paths for the
+    same pairs (SHD_PE_EUNREACHABLE in both where the directed graph has no path)."""
+    top = G.random_sparse(700, 5, seed=31, directed=True)
+    att = np.arange(0, 700, 3, dtype=np.int32)
+    eng = E.Engine(top, att, force_mode=force_mode)
+    srcs = att[[1, 60, 117, 230]]
+    src = np.repeat(srcs, att.shape[0]).astype(np.int32)
+    dst = np.tile(att, srcs.shape[0]).astype(np.int32)
+    offsets, verts, status = eng.get_paths(src, dst)
+    assert set(status.tolist()) <= {0, E.EUNREACHABLE} and np.count_nonzero(status == 0) > 800
+    for i in range(src.shape[0]):
+        try:
+            one, code = eng.get_path(int(src[i]), int(dst[i])), 0
+        except E.EngineError as e:
+            one, code = [], e.code
+        assert code == status[i], (i, src[i], dst[i])
+        assert one == verts[offsets[i]:offsets[i + 1]].tolist(), (i, src[i], dst[i])
     eng.close()
 
 

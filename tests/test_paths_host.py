@@ -49,6 +49,7 @@ def test_kernels_built_for_gfx950(E):
     for k in (b"k_paths_size", b"k_paths_scan", b"k_paths_hops", b"k_paths_flags", b"k_paths_walk_dist"):
         assert k in data, k
     assert re.search(rb"k_paths_walk(?!_dist)", data)     # (not only as the prefix of k_paths_walk_dist)
+    assert b"k_path_walk" not in data                     # the one-pair call's own walk kernel is gone
 
 
 def test_paths_out_struct_layout(E):
