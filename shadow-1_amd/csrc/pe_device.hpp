@@ -9,7 +9,8 @@
 //   vertex : vrel[f64] (1 - vertex packetloss, 1.0 when absent/NaN),
 //            self-loop latency/rel + hasSelf (the (s,s) hop, topology.c:1469).
 //   table  : row-major [T rows][T cols] lat f64 | rel f64 | hops i32 |
-//            flags u8 (| pred i32 optional), row/col order = attached[].
+//            pred i32 (optional) | flags u8, one array each (TABLE_FIELDS
+//            below), row/col order = attached[].
 //   scratch: one slot per resident workgroup: dist f64, hops i32, rel f64,
 //            pred i32 (+ heap key/idx, index2 for the exact kernel).
 #pragma once
@@ -76,6 +77,67 @@ struct DevTable {
     int64_t T;
     int64_t rowStart;
 };
+
+// The table's fields, the one list of them for host code: allocation, every
+// copy out of, into and between tables, and the staging layout walk it in
+// this order.  (Kernels name the members.)
+struct TableField {
+    int32_t off;       // of the field's pointer in DevTable
+    int32_t esize;     // bytes per table cell
+};
+constexpr TableField TABLE_FIELDS[5] = {
+    {(int32_t)__builtin_offsetof(DevTable, lat), 8},  {(int32_t)__builtin_offsetof(DevTable, rel), 8},
+    {(int32_t)__builtin_offsetof(DevTable, hops), 4}, {(int32_t)__builtin_offsetof(DevTable, pred), 4},
+    {(int32_t)__builtin_offsetof(DevTable, flags), 1}};
+
+constexpr int64_t table_cell_bytes() {
+    int64_t b = 0;
+    for (const TableField& f : TABLE_FIELDS) b += f.esize;
+    return b;
+}
+
+inline unsigned char* table_field(const DevTable& t, const TableField& f) {
+    unsigned char* p;
+    __builtin_memcpy(&p, reinterpret_cast<const char*>(&t) + f.off, sizeof(p));
+    return p;
+}
+
+inline void set_table_field(DevTable& t, const TableField& f, void* p) {
+    __builtin_memcpy(reinterpret_cast<char*>(&t) + f.off, &p, sizeof(p));
+}
+
+// Rows [row0, row0 + rows) (table positions) of every field that both views
+// hold: copy(dst, src, bytes, esize) per field, each side's pointer offset by
+// its own rowStart and T; stops at the first non-zero return and returns it.
+// A view is any DevTable-shaped description of memory, host or device: a
+// caller's buffers are one with rowStart = the first position they hold.
+template <class Copy>
+inline int for_each_field(const DevTable& src, const DevTable& dst, int64_t row0, int64_t rows, Copy&& copy) {
+    for (const TableField& f : TABLE_FIELDS) {
+        unsigned char* const s = table_field(src, f);
+        unsigned char* const d = table_field(dst, f);
+        if (!s || !d) continue;
+        const int rc = copy(d + (row0 - dst.rowStart) * dst.T * f.esize, s + (row0 - src.rowStart) * src.T * f.esize,
+                            rows * src.T * f.esize, (int)f.esize);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
+// A staging block as a view: the fields `wanted` holds, nRows rows of each
+// from position firstRow, packed back to back from `base`.
+inline DevTable stage_view(void* base, int64_t firstRow, int64_t nRows, const DevTable& wanted) {
+    DevTable v{};
+    v.T = wanted.T;
+    v.rowStart = firstRow;
+    unsigned char* q = static_cast<unsigned char*>(base);
+    for (const TableField& f : TABLE_FIELDS) {
+        if (!table_field(wanted, f)) continue;
+        set_table_field(v, f, q);
+        q += nRows * wanted.T * f.esize;
+    }
+    return v;
+}
 
 // Engine tuning (defaults in the engine; SHDPE_* environment overrides only
 // with SHD_PE_DEBUG_ENV, never in a production build of Shadow).

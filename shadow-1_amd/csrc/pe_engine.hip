@@ -11,15 +11,12 @@
 // engines in several processes own the rest (shardIndex / shardCount).  Each
 // shard holds its own graph copy, stream and a shard-sized table
 // (rows x T); compute runs all local shards concurrently (one host thread
-// per device), never exchanging data.  shd_pe_gather assembles the whole
+// per device), never exchanging data.  Reading, copying and exchanging the
+// finished rows is pe_rows.hip: there shd_pe_gather assembles the whole
 // table on every device with RCCL (a group of broadcasts = all-gather with
 // per-shard sizes) over xGMI, or with device copies when several logical
 // shards share a device.  The reference serialises every row on one core
 // under graphLock (topology.c:1747-1781).
-#include <hip/hip_runtime.h>
-#include <rccl/rccl.h>
-#include <sys/mman.h>
-
 #include <algorithm>
 #include <atomic>
 #include <cmath>
@@ -35,155 +32,15 @@
 #include <thread>
 #include <vector>
 
-#include "pe_device.hpp"
-#include "pe_graph.hpp"
-#include "shd_pathengine.h"
+#include "pe_engine.hpp"
 
 using namespace shdpe;
 
-namespace {
-
 constexpr int LDS_BYTES = 160 * 1024;
-
-// A shard's choice of k_batch_rows variant.  configure_batch fills it,
-// ensure_batch lowers every grid in it to the scratch slots (the one place: a
-// workgroup indexes its slot by blockIdx), shd_pe_tune times cand[] and
-// writes the picks.  Every launch of the batched path takes its BatchLaunch
-// from relax / post or from a BatchTrial of the tune.
-struct BatchPlan {
-    BatchLaunch cand[4];            // what shd_pe_tune times, in its order: the untuned relax
-                                    // pick, the other of 4 / 8 waves, 6 waves, the cooperative
-    int nc = 0;
-    int coop = -1;                  // cand[coop] is the cooperative relax (coop >= 2); -1: none
-    BatchLaunch relax{};            // picks in use: the relax launch (with the delta chosen) ...
-    BatchLaunch post{};             // ... and, split kernels, the post launch
-    bool tunable() const { return nc > 1 || coop >= 0; }
-};
-
-// One timed run of shd_pe_tune: the launches to use instead of the plan's
-// picks, and what the split kernels' relax / post parts took (summed over
-// the rounds; 0 when not split).
-// Serves two callers: shd_pe_tune's timed trials (timed, msRelax / msPost) and
-// the batch tier of shd_pe_get_paths (noTable), both through relax_batched /
-// batch_rounds; a plain compute passes no trial.
-struct BatchTrial {
-    BatchLaunch relax{}, post{};
-    bool timed = false;
-    bool noTable = false;           // shd_pe_get_paths: the post kernel stores no table row
-    double msRelax = 0.0, msPost = 0.0;
-};
-
-// shd_pe_get_path: PathsWalkArgs' arrays for one request (off = 0); the path's vertices follow.
-struct PathOne {
-    int64_t off;
-    int32_t len, nFailed;
-    PathReq req;
-    uint8_t failed, pad[31];
-};
-
-struct Shard {
-    int gindex = 0;                 // global shard index
-    int device = 0;
-    int numCUs = 256;
-    int32_t rowStart = 0, rowCount = 0;   // table positions owned
-    hipStream_t stream = nullptr;
-    hipStream_t copyStream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, evA = nullptr, evB = nullptr;
-    hipEvent_t evP[3] = {nullptr, nullptr, nullptr};   // per-part timing (shd_pe_tune)
-    std::vector<void*> allocs;
-    DevGraph dg{};                  // path kernels (device ids, possibly relabelled)
-    DevGraph dgAux{};               // caller's ids, rows sorted by id (aux kernels)
-    DevTable tab{};                 // this shard's rows
-    DevScratch sc{};
-    bool tableReady = false;
-    int32_t* dRows = nullptr;
-    uint8_t* dRowAmbig = nullptr;
-    int32_t* dDbg = nullptr;
-    int32_t pathSrc = -1;           // source whose full parent array sits in exact slot 0
-    PathOne* dPath = nullptr;       // shd_pe_get_path's one-request staging, its n vertices behind it
-    int32_t rowsCap = 0;
-    SparseLaunch cfg{};
-    int exactGrid = 0, exactHc = 1;
-    BatchPlan plan{};
-    int64_t coopAborts = 0;         // cooperative relax launches refused by the runtime or aborted
-                                    // at a barrier, counted together (round rerun plain):
-                                    // relaxCoopAborts
-    int32_t* dCoopAbort = nullptr;  // host-mapped copy target of the abort word
-    bool tuned = false;
-    BatchScratch bsc{};
-    bool batchReady = false;
-    int32_t batchRound = 0;         // split kernels: batches per round (persisted dist arrays)
-    int32_t batchSlots = 0;         // scratch slots allocated (ensure_batch: no grid of the plan exceeds it)
-    int32_t* dBatchRows = nullptr;
-    uint8_t* dBatchAmb = nullptr;
-    TieBuf tie{};                   // early-stop tie rows (batched path)
-    int32_t* dSlots = nullptr;      // per exact row its tie slot, -1 full emulation
-    TieBuf* dTie = nullptr;         // device copy of `tie` (k_batch_rows reads it)
-    int32_t* dDenseIdx = nullptr;   // dense early-stop tie rows: their row of the D / P matrices
-    long long* dXdbg = nullptr;     // exact-kernel counters (SHD_PE_DEBUG_COUNTERS)
-    bool tieTried = false;
-    double *dW = nullptr, *dRl = nullptr, *dD = nullptr;
-    int32_t* dP = nullptr;
-    uint8_t *dRowA = nullptr, *dRowB = nullptr, *dRowAmbD = nullptr, *dChunkEpoch = nullptr;
-    void* dXList = nullptr;         // k_exact_dense: per slot its pushes / modifies of a pop
-    int32_t* dAny = nullptr;
-    int32_t denseRows = 0;
-    int32_t* dPosOf = nullptr;      // vertex -> table position (caller's ids, as dgAux):
-                                    // uploaded by the first prefer-direct fill under copyMu
-                                    // (not in `allocs`, which the compute lock guards)
-    DevTable full{};                // whole table on this device after gather
-    bool fullOwner = false;         // first shard on its device owns `full`
-    ncclComm_t comm = nullptr;      // in-process communicator (distinct devices)
-    ShdPeStats stats{};
-};
-
-}  // namespace
-
-struct ShdPe {
-    HostGraph hg;
-    std::vector<int32_t> attached;   // unique, first-occurrence order
-    std::vector<int32_t> posOf;      // vertex -> table position or -1
-    ShdPeOptions opt{};
-    Tuning tu{};
-    int mode = 1;
-    bool batched = false;
-    std::vector<int32_t> rank;       // table position -> batch order rank
-    std::vector<double> rowOff;      // table position -> distance to its batch hub (order 1)
-    std::vector<int32_t> devOf;      // caller vertex id -> device id (empty: identity)
-    int G = 1;                       // global row shards
-    std::vector<int32_t> bounds;     // G + 1 position bounds
-    int firstShard = 0;              // global index of shards[0]
-    std::vector<std::unique_ptr<Shard>> shards;
-    std::unique_ptr<std::atomic<uint8_t>[]> rowDone;
-    bool gathered = false;
-    int64_t putRows = 0;             // distinct rows imported by shd_pe_put_rows (host transport)
-    std::vector<uint8_t> putSeen;    // per table row: imported already (a repeated put counts once)
-    bool putInit = false;            // own shard rows copied into the full table
-    ncclComm_t xcomm = nullptr;      // cross-process communicator (shd_pe_comm_init)
-    int32_t ownStart = 0, ownEnd = 0;
-    unsigned char* stage[2] = {nullptr, nullptr};   // pinned host staging (portable)
-    size_t stageBytes = 0;
-    std::mutex mu;                   // compute / gather
-    std::mutex copyMu;               // staging buffers
-    double msGather = 0.0;
-    int64_t pathsInfo[6] = {0, 0, 0, 0, 0, 0};   // shd_pe_paths_info of the last shd_pe_get_paths
-};
-
-#define HIPCHK(x)                                   \
-    do {                                            \
-        if ((x) != hipSuccess) return SHD_PE_EHIP;  \
-    } while (0)
-
-static int dev_alloc(Shard* s, void** p, size_t bytes) {
-    if (bytes == 0) bytes = 16;
-    if (hipMalloc(p, bytes) != hipSuccess) { *p = nullptr; return SHD_PE_ENOMEM; }
-    s->allocs.push_back(*p);
-    return SHD_PE_OK;
-}
 
 template <class T, class A>
 static int dev_upload(Shard* s, T** dst, const std::vector<T, A>& src) {
-    int rc = dev_alloc(s, reinterpret_cast<void**>(dst), src.size() * sizeof(T));
+    int rc = dev_alloc(s, dst, src.size());
     if (rc) return rc;
     if (!src.empty())
         HIPCHK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
@@ -887,69 +744,56 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
     return SHD_PE_OK;
 }
 
-static int ensure_table(ShdPe* pe, Shard* sh) {
+// The field arrays of a table of `rows` rows at position 0 (pred only with
+// storePred); `t` is written once all of them are there.
+int shdpe::alloc_table(Shard* sh, DevTable& t, size_t rows, size_t T, bool storePred) {
+    DevTable a{};
+    a.T = (int64_t)T;
+    for (const TableField& f : TABLE_FIELDS) {
+        if (f.off == (int32_t)offsetof(DevTable, pred) && !storePred) continue;
+        unsigned char* p;
+        const int rc = dev_alloc(sh, &p, rows * T * (size_t)f.esize);
+        if (rc) return rc;
+        set_table_field(a, f, p);
+    }
+    t = a;
+    return SHD_PE_OK;
+}
+
+int shdpe::ensure_table(ShdPe* pe, Shard* sh) {
     if (sh->tableReady) return SHD_PE_OK;
-    const size_t T = pe->attached.size();
-    const size_t cells = (size_t)sh->rowCount * T;
     int rc;
-    void *lat, *rel, *hops, *flags, *pred = nullptr;
-    if ((rc = dev_alloc(sh, &lat, cells * 8)) || (rc = dev_alloc(sh, &rel, cells * 8)) ||
-        (rc = dev_alloc(sh, &hops, cells * 4)) || (rc = dev_alloc(sh, &flags, cells)))
+    if ((rc = alloc_table(sh, sh->tab, (size_t)sh->rowCount, pe->attached.size(), pe->opt.storePred != 0)))
         return rc;
-    if (pe->opt.storePred && (rc = dev_alloc(sh, &pred, cells * 4))) return rc;
-    sh->tab.lat = (double*)lat;
-    sh->tab.rel = (double*)rel;
-    sh->tab.hops = (int32_t*)hops;
-    sh->tab.flags = (uint8_t*)flags;
-    sh->tab.pred = (int32_t*)pred;
-    sh->tab.T = (int64_t)T;
     sh->tab.rowStart = sh->rowStart;
     // scratch slots
-    const int slots = pe->batched ? sh->exactGrid : std::max(sh->cfg.grid, sh->exactGrid);
+    const size_t slots = (size_t)(pe->batched ? sh->exactGrid : std::max(sh->cfg.grid, sh->exactGrid));
     const size_t stride = ((size_t)pe->hg.n + 63) & ~(size_t)63;
     const size_t heapStride = std::max<size_t>(1, (size_t)pe->hg.n - (size_t)sh->exactHc);
-    void *dist, *sho, *sr, *sp, *hk, *i2;
-    if ((rc = dev_alloc(sh, &dist, slots * stride * 8)) ||
-        (rc = dev_alloc(sh, &sho, slots * stride * 4)) ||
-        (rc = dev_alloc(sh, &sr, slots * stride * 8)) ||
-        (rc = dev_alloc(sh, &sp, slots * stride * 4)) ||
-        (rc = dev_alloc(sh, &hk, (size_t)sh->exactGrid * heapStride * 16)) ||
-        (rc = dev_alloc(sh, &i2, (size_t)sh->exactGrid * stride * 4)))
+    // (a heap tail entry: an f64 key and, behind the slot's keys, an i32 vertex id in 16 B)
+    if ((rc = dev_alloc(sh, &sh->sc.dist, slots * stride)) ||
+        (rc = dev_alloc(sh, &sh->sc.hops, slots * stride)) ||
+        (rc = dev_alloc(sh, &sh->sc.rel, slots * stride)) ||
+        (rc = dev_alloc(sh, &sh->sc.pred, slots * stride)) ||
+        (rc = dev_alloc(sh, &sh->sc.heapTail, (size_t)sh->exactGrid * heapStride * 2)) ||
+        (rc = dev_alloc(sh, &sh->sc.index2, (size_t)sh->exactGrid * stride)))
         return rc;
-    sh->sc.dist = (double*)dist;
-    sh->sc.hops = (int32_t*)sho;
-    sh->sc.rel = (double*)sr;
-    sh->sc.pred = (int32_t*)sp;
-    sh->sc.heapTail = (double*)hk;
     sh->sc.heapStride = (int64_t)heapStride;
-    sh->sc.index2 = (int32_t*)i2;
     sh->sc.stride = (int64_t)stride;
     sh->sc.lfold = nullptr;
-    if (pe->hg.latFold) {
-        void* lf;
-        if ((rc = dev_alloc(sh, &lf, slots * stride * 8))) return rc;
-        sh->sc.lfold = (double*)lf;
-    }
+    if (pe->hg.latFold && (rc = dev_alloc(sh, &sh->sc.lfold, slots * stride))) return rc;
     if (!pe->batched && (sh->cfg.layout == 3 || sh->cfg.layout == 0)) {
-        void* q;
         const size_t per = 2 * ((size_t)sh->cfg.qcap + sh->cfg.hcap);
-        if ((rc = dev_alloc(sh, &q, (size_t)sh->cfg.grid * per * 4))) return rc;
-        sh->sc.queue = (int32_t*)q;
+        if ((rc = dev_alloc(sh, &sh->sc.queue, (size_t)sh->cfg.grid * per))) return rc;
     }
     sh->rowsCap = (int32_t)std::max<size_t>(1, std::min<size_t>(sh->rowCount, 1 << 20));
-    void *rows, *amb;
-    if ((rc = dev_alloc(sh, &rows, (size_t)sh->rowsCap * 4)) ||
-        (rc = dev_alloc(sh, &amb, (size_t)sh->rowsCap)))
+    if ((rc = dev_alloc(sh, &sh->dRows, (size_t)sh->rowsCap)) ||
+        (rc = dev_alloc(sh, &sh->dRowAmbig, (size_t)sh->rowsCap)))
         return rc;
-    sh->dRows = (int32_t*)rows;
-    sh->dRowAmbig = (uint8_t*)amb;
-    if (pe->tu.debug) {
-        void* dbg;
-        if ((rc = dev_alloc(sh, &dbg, (size_t)sh->rowsCap * 64))) return rc;
-        sh->dDbg = (int32_t*)dbg;
-        void* xd;
-        if ((rc = dev_alloc(sh, &xd, (size_t)sh->rowsCap * 64))) return rc;
-        sh->dXdbg = (long long*)xd;
+    if (pe->tu.debug) {          // 64 B of counters per row
+        if ((rc = dev_alloc(sh, &sh->dDbg, (size_t)sh->rowsCap * 16)) ||
+            (rc = dev_alloc(sh, &sh->dXdbg, (size_t)sh->rowsCap * 8)))
+            return rc;
     }
     sh->tableReady = true;
     return SHD_PE_OK;
@@ -970,21 +814,24 @@ static int ensure_tie(ShdPe* pe, Shard* sh) {
                                    ((size_t)2 << 30) / perTie});
     if (pe->hg.nArcs() >= ((int64_t)1 << 30)) cap = 0;
     if (cap > 0) {
-        void *td, *tp, *th, *tr, *tt, *tc, *sl, *dd, *rq;
+        TieBuf t{}, *dd;
+        int32_t *sl, *rq;
         const size_t cn = cap * (size_t)pe->hg.n;
-        if ((rc = dev_alloc(sh, &td, cn * 8)) || (rc = dev_alloc(sh, &tp, cn * 4)) ||
-            (rc = dev_alloc(sh, &th, cn * 4)) || (rc = dev_alloc(sh, &tr, cn * 8)) ||
-            (rc = dev_alloc(sh, &tt, cap * 8)) || (rc = dev_alloc(sh, &tc, 16)) ||
-            (rc = dev_alloc(sh, &sl, (size_t)sh->rowsCap * 4)) ||
-            (rc = dev_alloc(sh, &dd, sizeof(TieBuf))) || (rc = dev_alloc(sh, &rq, cap * 16)))
-            return rc;
-        // (tc: [0] slot counter, [1] the round word of the deferred export;
+        // (count: 4 words, [0] slot counter, [1] the round word of the deferred export;
         // the batched path's post kernel defers its export to k_tie_export)
-        sh->tie = TieBuf{(int32_t)cap, (int32_t*)tc, (double*)td, (int32_t*)tp, (double*)tt,
-                         (int32_t*)th, (double*)tr, (int64_t)pe->hg.n,
-                         pe->batched ? (int32_t*)rq : nullptr, (int32_t*)tc + 1};
-        sh->dSlots = (int32_t*)sl;
-        sh->dTie = (TieBuf*)dd;
+        if ((rc = dev_alloc(sh, &t.D, cn)) || (rc = dev_alloc(sh, &t.P, cn)) ||
+            (rc = dev_alloc(sh, &t.H, cn)) || (rc = dev_alloc(sh, &t.R, cn)) ||
+            (rc = dev_alloc(sh, &t.thr, cap)) || (rc = dev_alloc(sh, &t.count, 4)) ||
+            (rc = dev_alloc(sh, &sl, (size_t)sh->rowsCap)) ||
+            (rc = dev_alloc(sh, &dd, 1)) || (rc = dev_alloc(sh, &rq, cap * 4)))
+            return rc;
+        t.cap = (int32_t)cap;
+        t.n = (int64_t)pe->hg.n;
+        t.req = pe->batched ? rq : nullptr;
+        t.round = t.count + 1;
+        sh->tie = t;
+        sh->dSlots = sl;
+        sh->dTie = dd;
         HIPCHK(hipMemcpy(sh->dTie, &sh->tie, sizeof(TieBuf), hipMemcpyHostToDevice));
     }
     return SHD_PE_OK;
@@ -1040,47 +887,34 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
         roundB = std::max<size_t>(slots, std::min<size_t>(nBatchesAll, dBudget / perD));
     }
     sh->batchRound = (int32_t)roundB;
-    void *D, *L, *q, *rows, *amb, *fl;
-    if ((rc = dev_alloc(sh, &D, roundB * NS * LB * 8)) || (rc = dev_alloc(sh, &L, slots * NS * LB * 16)) ||
-        (rc = dev_alloc(sh, &q, slots * NS * 4 + 64)) ||
-        (rc = dev_alloc(sh, &rows, ((size_t)sh->rowsCap + 64) * 4)) ||
-        (rc = dev_alloc(sh, &amb, (size_t)sh->rowsCap + 64)) || (rc = dev_alloc(sh, &fl, roundB * 4 + 64)))
+    // (the queues' and the flags' 16 spare words: `next` sits behind the queues)
+    if ((rc = dev_alloc(sh, &sh->bsc.D, roundB * NS * LB)) || (rc = dev_alloc(sh, &sh->bsc.L, slots * NS * LB)) ||
+        (rc = dev_alloc(sh, &sh->bsc.queue, slots * NS + 16)) ||
+        (rc = dev_alloc(sh, &sh->dBatchRows, (size_t)sh->rowsCap + 64)) ||
+        (rc = dev_alloc(sh, &sh->dBatchAmb, (size_t)sh->rowsCap + 64)) ||
+        (rc = dev_alloc(sh, &sh->bsc.flags, roundB + 16)))
         return rc;
-    sh->bsc.flags = (int32_t*)fl;
-    sh->bsc.D = (unsigned long long*)D;
-    sh->bsc.L = (BLabel*)L;
-    sh->bsc.queue = (int32_t*)q;
-    sh->bsc.next = (int32_t*)q + slots * NS;
+    sh->bsc.next = sh->bsc.queue + slots * NS;
     sh->bsc.nStride = (int64_t)NS;
     sh->bsc.bits = nullptr;
-    if (bitBytes) {
-        void* bits;
-        if ((rc = dev_alloc(sh, &bits, slots * bitBytes))) return rc;
-        sh->bsc.bits = (uint32_t*)bits;
-    }
+    if (bitBytes && (rc = dev_alloc(sh, &sh->bsc.bits, slots * bitBytes / 4))) return rc;
     sh->bsc.rowOff = nullptr;
     if (!pe->rowOff.empty()) {
         double* ro;
         if ((rc = dev_upload(sh, &ro, pe->rowOff))) return rc;
         sh->bsc.rowOff = ro;
     }
-    sh->dBatchRows = (int32_t*)rows;
-    sh->dBatchAmb = (uint8_t*)amb;
     if (plan.coop >= 0) {
         // cooperative relax state: control words, one barrier line per group,
         // two publication buffers of near bits + scalars per member per group
         const size_t maxGroups = (size_t)plan.cand[plan.coop].grid;
         const size_t K = (size_t)plan.cand[plan.coop].coop;
         const size_t nwp = (size_t)batch_bits_words(pe->hg.n) / 2;
-        void *cc, *pub, *pubS;
-        if ((rc = dev_alloc(sh, &cc, 128 + maxGroups * 128)) ||
-            (rc = dev_alloc(sh, &pub, maxGroups * 2 * K * nwp * 4)) ||
-            (rc = dev_alloc(sh, &pubS, maxGroups * 2 * K * 16)))
+        if ((rc = dev_alloc(sh, &sh->bsc.coCtl, 32 + maxGroups * 32)) ||
+            (rc = dev_alloc(sh, &sh->bsc.coPub, maxGroups * 2 * K * nwp)) ||
+            (rc = dev_alloc(sh, &sh->bsc.coPubS, maxGroups * 2 * K * 2)))
             return rc;
-        sh->bsc.coCtl = (int32_t*)cc;
-        sh->bsc.coBars = (int32_t*)cc + 32;
-        sh->bsc.coPub = (uint32_t*)pub;
-        sh->bsc.coPubS = (unsigned long long*)pubS;
+        sh->bsc.coBars = sh->bsc.coCtl + 32;
         sh->bsc.coK = (int32_t)K;
         sh->bsc.coSpin = pe->tu.coopSpin;
         if (hipHostMalloc(reinterpret_cast<void**>(&sh->dCoopAbort), 4, hipHostMallocDefault) != hipSuccess)
@@ -1096,21 +930,18 @@ static int ensure_dense(ShdPe* pe, Shard* sh) {
     const int64_t n = pe->hg.n;
     const int64_t R = std::max<int32_t>(1, sh->rowCount);
     int rc;
-    void *w, *rl, *d, *p, *ra, *rb, *am, *any, *ce;
+    double* w;                      // (dW marks the whole set ready: written last)
     // rows per batch: D (f64) + P (i32) per row
     const int64_t budget = (int64_t)(pe->tu.denseBatchGB * (double)(1LL << 30));
     int64_t rows = std::max<int64_t>(64, budget / (n * 12));
     rows = std::min<int64_t>(rows, R);
-    if ((rc = dev_alloc(sh, &w, (size_t)(n * n * 8))) || (rc = dev_alloc(sh, &rl, (size_t)(n * n * 8))) ||
-        (rc = dev_alloc(sh, &d, (size_t)(rows * n * 8))) || (rc = dev_alloc(sh, &p, (size_t)(rows * n * 4))) ||
-        (rc = dev_alloc(sh, &ra, (size_t)rows)) || (rc = dev_alloc(sh, &rb, (size_t)rows)) ||
-        (rc = dev_alloc(sh, &am, (size_t)rows)) || (rc = dev_alloc(sh, &any, 16)) ||
-        (rc = dev_alloc(sh, &ce, (size_t)((rows / 16 + 1) * (n / 16 + 1)))))
+    if ((rc = dev_alloc(sh, &w, (size_t)(n * n))) || (rc = dev_alloc(sh, &sh->dRl, (size_t)(n * n))) ||
+        (rc = dev_alloc(sh, &sh->dD, (size_t)(rows * n))) || (rc = dev_alloc(sh, &sh->dP, (size_t)(rows * n))) ||
+        (rc = dev_alloc(sh, &sh->dRowA, (size_t)rows)) || (rc = dev_alloc(sh, &sh->dRowB, (size_t)rows)) ||
+        (rc = dev_alloc(sh, &sh->dRowAmbD, (size_t)rows)) || (rc = dev_alloc(sh, &sh->dAny, 4)) ||
+        (rc = dev_alloc(sh, &sh->dChunkEpoch, (size_t)((rows / 16 + 1) * (n / 16 + 1)))))
         return rc;
-    sh->dChunkEpoch = (uint8_t*)ce;
-    sh->dW = (double*)w; sh->dRl = (double*)rl; sh->dD = (double*)d; sh->dP = (int32_t*)p;
-    sh->dRowA = (uint8_t*)ra; sh->dRowB = (uint8_t*)rb; sh->dRowAmbD = (uint8_t*)am;
-    sh->dAny = (int32_t*)any;
+    sh->dW = w;
     sh->denseRows = (int32_t)rows;
     launch_dense_build(sh->dg, sh->dW, sh->dRl, n, pe->hg.nArcs(), sh->stream);
     HIPCHK(hipGetLastError());
@@ -1118,7 +949,7 @@ static int ensure_dense(ShdPe* pe, Shard* sh) {
     return SHD_PE_OK;
 }
 
-static float elapsed(hipEvent_t a, hipEvent_t b) {
+float shdpe::elapsed(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, a, b);
     return ms;
@@ -1613,11 +1444,7 @@ static int repair_tie_rows(ShdPe* pe, Shard* sh, const std::vector<int32_t>& red
 static int exact_dense_early(ShdPe* pe, Shard* sh, const ExactWork& x) {
     ShdPeStats& st = sh->stats;
     int rc;
-    if (!sh->dDenseIdx) {
-        void* di;
-        if ((rc = dev_alloc(sh, &di, (size_t)sh->rowsCap * 4))) return rc;
-        sh->dDenseIdx = (int32_t*)di;
-    }
+    if (!sh->dDenseIdx && (rc = dev_alloc(sh, &sh->dDenseIdx, (size_t)sh->rowsCap))) return rc;
     if ((rc = ensure_xlist(sh))) return rc;
     const int32_t cap = sh->tie.cap;
     std::vector<int32_t> slots(cap), redo;
@@ -1734,7 +1561,7 @@ static int compute_shard(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t count
     return SHD_PE_OK;
 }
 
-static Shard* owner_of(ShdPe* pe, int32_t p) {
+Shard* shdpe::owner_of(ShdPe* pe, int32_t p) {
     for (auto& s : pe->shards)
         if (p >= s->rowStart && p < s->rowStart + s->rowCount) return s.get();
     return nullptr;
@@ -1742,7 +1569,7 @@ static Shard* owner_of(ShdPe* pe, int32_t p) {
 
 // Compute positions (caller holds pe->mu): split by shard, one host thread
 // per shard when several shards have work (their devices run concurrently).
-static int compute_positions_locked(ShdPe* pe, const int32_t* pos, int32_t count) {
+int shdpe::compute_positions_locked(ShdPe* pe, const int32_t* pos, int32_t count) {
     if (count <= 0) return SHD_PE_OK;
     std::vector<std::vector<int32_t>> per(pe->shards.size());
     for (int32_t i = 0; i < count; ++i) {
@@ -1772,7 +1599,7 @@ static int compute_positions_locked(ShdPe* pe, const int32_t* pos, int32_t count
     return SHD_PE_OK;
 }
 
-static bool row_done(const ShdPe* pe, int32_t p) {
+bool shdpe::row_done(const ShdPe* pe, int32_t p) {
     return pe->rowDone[p].load(std::memory_order_acquire) != 0;
 }
 
@@ -1961,7 +1788,7 @@ extern "C" int shd_pe_compute_rows(ShdPe* pe, const int32_t* src, int32_t count)
 }
 
 // Compute whatever rows of [start, start+count) are owned here and missing.
-static int ensure_rows(ShdPe* pe, int32_t start, int32_t count) {
+int shdpe::ensure_rows(ShdPe* pe, int32_t start, int32_t count) {
     bool all = true;
     for (int32_t i = start; i < start + count && all; ++i) all = row_done(pe, i);
     if (all) return SHD_PE_OK;
@@ -1973,180 +1800,6 @@ static int ensure_rows(ShdPe* pe, int32_t start, int32_t count) {
         todo.push_back(i);
     }
     return compute_positions_locked(pe, todo.data(), (int32_t)todo.size());
-}
-
-// A contiguous run of table rows readable from one device table.
-struct Piece {
-    const DevTable* tab;
-    hipStream_t stream;
-    int device;
-    int32_t start, count;   // table positions
-};
-
-static int table_pieces(ShdPe* pe, int32_t start, int32_t count, std::vector<Piece>& out) {
-    out.clear();
-    if (pe->gathered) {
-        Shard* s = pe->shards[0].get();
-        out.push_back(Piece{&s->full, s->copyStream, s->device, start, count});
-        return SHD_PE_OK;
-    }
-    int32_t p = start;
-    while (p < start + count) {
-        Shard* s = owner_of(pe, p);
-        if (!s || !s->tableReady) return SHD_PE_ENOTOWNED;
-        const int32_t end = std::min(start + count, s->rowStart + s->rowCount);
-        out.push_back(Piece{&s->tab, s->copyStream, s->device, p, end - p});
-        p = end;
-    }
-    return SHD_PE_OK;
-}
-
-static int get_rows_staged(ShdPe* pe, int32_t start, int32_t count, double* lat, double* rel,
-                           int32_t* hops, int32_t* pred, uint8_t* flags);
-
-extern "C" int shd_pe_get_row(ShdPe* pe, int32_t srcVertex, double* lat, double* rel,
-                              int32_t* hops, int32_t* pred, uint8_t* flags) {
-    if (!pe || srcVertex < 0 || srcVertex >= pe->hg.n) return SHD_PE_EINVAL;
-    const int32_t p = pe->posOf[srcVertex];
-    if (p < 0) return SHD_PE_ENOTATTACHED;
-    if (pred && !pe->opt.storePred) return SHD_PE_EINVAL;
-    int rc = ensure_rows(pe, p, 1);
-    if (rc) return rc;
-    return get_rows_staged(pe, p, 1, lat, rel, hops, pred, flags);
-}
-
-// Host memcpy split over up to 8 threads: the drain of a staging block into
-// caller (pageable, often freshly allocated) memory runs at one core's
-// page-fault + copy rate otherwise.
-static void par_memcpy(void* dst, const void* src, size_t bytes) {
-    const size_t minChunk = (size_t)2 << 20;
-    const unsigned hc = std::thread::hardware_concurrency();
-    const int nt = (int)std::max<size_t>(1, std::min<size_t>({(size_t)8, hc ? hc : 1, bytes / minChunk}));
-    if (nt <= 1) { std::memcpy(dst, src, bytes); return; }
-    std::vector<std::thread> th;
-    const size_t per = (bytes + nt - 1) / nt;
-    for (int t = 1; t < nt; ++t) {
-        const size_t o = per * t;
-        if (o >= bytes) break;
-        th.emplace_back([=]() { std::memcpy((char*)dst + o, (const char*)src + o, std::min(per, bytes - o)); });
-    }
-    std::memcpy(dst, src, std::min(per, bytes));
-    for (auto& x : th) x.join();
-}
-
-// Page-locked host memory the device can DMA into (hipHostMalloc or
-// hipHostRegister): such caller buffers skip the staging copy.
-static bool is_pinned(const void* p) {
-    if (!p) return true;
-    hipPointerAttribute_t at;
-    if (hipPointerGetAttributes(&at, p) != hipSuccess) {
-        (void)hipGetLastError();
-        return false;
-    }
-    return at.type == hipMemoryTypeHost && at.hostPointer != nullptr;
-}
-
-// Rows [start, start+count) -> caller host buffers.  Pinned caller buffers
-// take the DMA straight (five field copies per table piece); otherwise two
-// pinned staging buffers: block b's field copies run on the copy stream
-// while host threads copy block b-1 out of the other buffer.
-static int get_rows_staged(ShdPe* pe, int32_t start, int32_t count, double* lat, double* rel,
-                           int32_t* hops, int32_t* pred, uint8_t* flags) {
-    const size_t T = pe->attached.size();
-    const size_t perRow = T * (8 + 8 + 4 + 4 + 1);
-    std::lock_guard<std::mutex> lk(pe->copyMu);
-    std::vector<Piece> pieces;
-    int rc = table_pieces(pe, start, count, pieces);
-    if (rc) return rc;
-    if (is_pinned(lat) && is_pinned(rel) && is_pinned(hops) && is_pinned(pred) && is_pinned(flags)) {
-        for (const Piece& pc : pieces) {
-            HIPCHK(hipSetDevice(pc.device));
-            const DevTable& tb = *pc.tab;
-            const size_t off = (size_t)(pc.start - tb.rowStart) * T, cells = (size_t)pc.count * T;
-            const size_t o = (size_t)(pc.start - start) * T;
-            if (lat) HIPCHK(hipMemcpyAsync(lat + o, tb.lat + off, cells * 8, hipMemcpyDeviceToHost, pc.stream));
-            if (rel) HIPCHK(hipMemcpyAsync(rel + o, tb.rel + off, cells * 8, hipMemcpyDeviceToHost, pc.stream));
-            if (hops) HIPCHK(hipMemcpyAsync(hops + o, tb.hops + off, cells * 4, hipMemcpyDeviceToHost, pc.stream));
-            if (pred) HIPCHK(hipMemcpyAsync(pred + o, tb.pred + off, cells * 4, hipMemcpyDeviceToHost, pc.stream));
-            if (flags) HIPCHK(hipMemcpyAsync(flags + o, tb.flags + off, cells, hipMemcpyDeviceToHost, pc.stream));
-        }
-        for (const Piece& pc : pieces) {
-            HIPCHK(hipSetDevice(pc.device));
-            HIPCHK(hipStreamSynchronize(pc.stream));
-        }
-        return SHD_PE_OK;
-    }
-    if (!pe->stage[0]) {
-        const size_t want = std::max<size_t>(perRow, (size_t)64 << 20);
-        for (auto& h : pe->stage)
-            HIPCHK(hipHostMalloc(reinterpret_cast<void**>(&h), want, hipHostMallocPortable));
-        pe->stageBytes = want;
-    }
-    const int32_t B = (int32_t)std::max<size_t>(1, pe->stageBytes / perRow);
-    for (const Piece& pc : pieces) {
-        HIPCHK(hipSetDevice(pc.device));
-        const DevTable& tb = *pc.tab;
-        struct Blk { int32_t r0, n; };   // r0 relative to pc.start
-        auto issue = [&](int buf, Blk b) -> int {
-            unsigned char* q = pe->stage[buf];
-            const size_t off = ((size_t)(pc.start - tb.rowStart) + b.r0) * T, cells = (size_t)b.n * T;
-            if (lat) { HIPCHK(hipMemcpyAsync(q, tb.lat + off, cells * 8, hipMemcpyDeviceToHost, pc.stream)); q += cells * 8; }
-            if (rel) { HIPCHK(hipMemcpyAsync(q, tb.rel + off, cells * 8, hipMemcpyDeviceToHost, pc.stream)); q += cells * 8; }
-            if (hops) { HIPCHK(hipMemcpyAsync(q, tb.hops + off, cells * 4, hipMemcpyDeviceToHost, pc.stream)); q += cells * 4; }
-            if (pred) { HIPCHK(hipMemcpyAsync(q, tb.pred + off, cells * 4, hipMemcpyDeviceToHost, pc.stream)); q += cells * 4; }
-            if (flags) { HIPCHK(hipMemcpyAsync(q, tb.flags + off, cells, hipMemcpyDeviceToHost, pc.stream)); }
-            return SHD_PE_OK;
-        };
-        auto drain = [&](int buf, Blk b) {
-            const unsigned char* q = pe->stage[buf];
-            const size_t o = ((size_t)(pc.start - start) + b.r0) * T, cells = (size_t)b.n * T;
-            if (lat) { par_memcpy(lat + o, q, cells * 8); q += cells * 8; }
-            if (rel) { par_memcpy(rel + o, q, cells * 8); q += cells * 8; }
-            if (hops) { par_memcpy(hops + o, q, cells * 4); q += cells * 4; }
-            if (pred) { par_memcpy(pred + o, q, cells * 4); q += cells * 4; }
-            if (flags) par_memcpy(flags + o, q, cells);
-        };
-        hipEvent_t done[2];
-        HIPCHK(hipEventCreateWithFlags(&done[0], hipEventDisableTiming));
-        if (hipEventCreateWithFlags(&done[1], hipEventDisableTiming) != hipSuccess) {
-            (void)hipEventDestroy(done[0]);
-            return SHD_PE_EHIP;
-        }
-        Blk prev{0, 0};
-        int buf = 0;
-        for (int32_t r0 = 0; r0 < pc.count && rc == SHD_PE_OK; r0 += B) {
-            const Blk cur{r0, std::min(B, pc.count - r0)};
-            if ((rc = issue(buf, cur)) == SHD_PE_OK &&
-                hipEventRecord(done[buf], pc.stream) != hipSuccess)
-                rc = SHD_PE_EHIP;
-            if (rc == SHD_PE_OK && prev.n) {
-                if (hipEventSynchronize(done[buf ^ 1]) != hipSuccess) rc = SHD_PE_EHIP;
-                else drain(buf ^ 1, prev);
-            }
-            prev = cur;
-            buf ^= 1;
-        }
-        if (rc == SHD_PE_OK && prev.n) {
-            if (hipEventSynchronize(done[buf ^ 1]) != hipSuccess) rc = SHD_PE_EHIP;
-            else drain(buf ^ 1, prev);
-        }
-        (void)hipStreamSynchronize(pc.stream);
-        (void)hipEventDestroy(done[0]);
-        (void)hipEventDestroy(done[1]);
-        if (rc) return rc;
-    }
-    return rc;
-}
-
-extern "C" int shd_pe_get_rows(ShdPe* pe, int32_t start, int32_t count, double* lat, double* rel,
-                               int32_t* hops, int32_t* pred, uint8_t* flags) {
-    if (!pe || start < 0 || count < 0 || (int64_t)start + count > (int64_t)pe->attached.size())
-        return SHD_PE_EINVAL;
-    if (pred && !pe->opt.storePred) return SHD_PE_EINVAL;
-    if (count == 0) return SHD_PE_OK;
-    int rc = ensure_rows(pe, start, count);
-    if (rc) return rc;
-    return get_rows_staged(pe, start, count, lat, rel, hops, pred, flags);
 }
 
 // The exact kernel for the path code (row i of dRows leaves its parents in scratch slot i;
@@ -2188,9 +1841,9 @@ extern "C" int shd_pe_get_path(ShdPe* pe, int32_t srcVertex, int32_t dstVertex, 
     int rc = ensure_table(pe, sh);
     if (rc) return rc;
     if (!sh->dPath) {
-        void* p;
+        unsigned char* p;            // in bytes: one PathOne and the n vertices behind it
         if ((rc = dev_alloc(sh, &p, sizeof(PathOne) + (size_t)g.n * 4))) return rc;
-        sh->dPath = (PathOne*)p;
+        sh->dPath = reinterpret_cast<PathOne*>(p);
     }
     if (sh->pathSrc != srcVertex) {
         // igraph's whole Dijkstra for this source (full 2-wheap emulation,
@@ -2709,480 +2362,6 @@ extern "C" int shd_pe_paths_info(const ShdPe* pe, int64_t* info, int32_t n) {
     if (!pe || !info || n < 0) return SHD_PE_EINVAL;
     std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
     for (int32_t k = 0; k < std::min<int32_t>(n, 6); ++k) info[k] = pe->pathsInfo[k];
-    return SHD_PE_OK;
-}
-
-extern "C" int shd_pe_host_alloc(int64_t bytes, void** out) {
-    if (!out || bytes <= 0) return SHD_PE_EINVAL;
-    *out = nullptr;
-    if (hipHostMalloc(out, (size_t)bytes, hipHostMallocPortable) != hipSuccess) {
-        *out = nullptr;
-        return SHD_PE_ENOMEM;
-    }
-    return SHD_PE_OK;
-}
-
-extern "C" void shd_pe_host_free(void* p) {
-    if (p) (void)hipHostFree(p);
-}
-
-extern "C" int shd_pe_copy_rows_device(ShdPe* pe, int32_t start, int32_t count, double* dLat,
-                                       double* dRel, int32_t* dHops, uint8_t* dFlags) {
-    if (!pe || start < 0 || count < 0 || (int64_t)start + count > (int64_t)pe->attached.size())
-        return SHD_PE_EINVAL;
-    if (count == 0) return SHD_PE_OK;
-    int rc = ensure_rows(pe, start, count);       // same contract as shd_pe_get_rows
-    if (rc) return rc;
-    // table_pieces reads gathered / the full table, which shd_pe_gather
-    // writes under copyMu
-    std::lock_guard<std::mutex> lk(pe->copyMu);
-    std::vector<Piece> pieces;
-    if ((rc = table_pieces(pe, start, count, pieces))) return rc;
-    const size_t T = pe->attached.size();
-    for (const Piece& pc : pieces) {
-        HIPCHK(hipSetDevice(pc.device));
-        const DevTable& tb = *pc.tab;
-        const size_t off = (size_t)(pc.start - tb.rowStart) * T, cells = (size_t)pc.count * T;
-        const size_t o = (size_t)(pc.start - start) * T;
-        if (dLat) HIPCHK(hipMemcpyAsync(dLat + o, tb.lat + off, cells * 8, hipMemcpyDeviceToDevice, pc.stream));
-        if (dRel) HIPCHK(hipMemcpyAsync(dRel + o, tb.rel + off, cells * 8, hipMemcpyDeviceToDevice, pc.stream));
-        if (dHops) HIPCHK(hipMemcpyAsync(dHops + o, tb.hops + off, cells * 4, hipMemcpyDeviceToDevice, pc.stream));
-        if (dFlags) HIPCHK(hipMemcpyAsync(dFlags + o, tb.flags + off, cells, hipMemcpyDeviceToDevice, pc.stream));
-        HIPCHK(hipStreamSynchronize(pc.stream));
-    }
-    return SHD_PE_OK;
-}
-
-extern "C" int shd_pe_row_checksums(ShdPe* pe, int32_t start, int32_t count, uint64_t* out) {
-    if (!pe || !out || start < 0 || count < 0 || (int64_t)start + count > (int64_t)pe->attached.size())
-        return SHD_PE_EINVAL;
-    if (count == 0) return SHD_PE_OK;
-    int rc = ensure_rows(pe, start, count);
-    if (rc) return rc;
-    std::lock_guard<std::mutex> lk(pe->copyMu);
-    std::vector<Piece> pieces;
-    if ((rc = table_pieces(pe, start, count, pieces))) return rc;
-    for (const Piece& pc : pieces) {
-        HIPCHK(hipSetDevice(pc.device));
-        uint64_t* d = nullptr;
-        if (hipMalloc(&d, (size_t)pc.count * 8) != hipSuccess) return SHD_PE_ENOMEM;
-        launch_row_checksums(*pc.tab, (int64_t)pc.start - pc.tab->rowStart, pc.count, d, pc.stream);
-        hipError_t e = hipGetLastError();
-        if (e == hipSuccess)
-            e = hipMemcpyAsync(out + (pc.start - start), d, (size_t)pc.count * 8, hipMemcpyDeviceToHost,
-                               pc.stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(pc.stream);
-        (void)hipFree(d);
-        if (e != hipSuccess) return SHD_PE_EHIP;
-    }
-    return SHD_PE_OK;
-}
-
-// The whole-table path-cache fill (topology.c:1805-1864 for every row, in
-// position order) as one device pass: k_pack_rowstore builds the row
-// store's own image of its triangular rows (2.3 GB at C4 vs 7.8 GB of
-// rows), one DMA lands it in page-locked host memory the store adopts.
-//
-// The host image (2.3 GB at C4) is anonymous memory with transparent huge
-// pages, first-touched by 16 threads and then registered with the device
-// (page-locked): hipHostMalloc of the same size took 430 ms, most of it
-// faulting and zeroing 4-KB pages on one thread.  When the rows still have
-// to be computed, that preparation runs on a host thread while the device
-// computes them.
-struct HostImage {
-    void* p = nullptr;
-    size_t bytes = 0;
-    bool registered = false;
-    double msTouch = 0.0, msRegister = 0.0;
-    ~HostImage();
-};
-
-static void host_image_prepare(HostImage* im, size_t bytes) {
-    const auto t0 = std::chrono::steady_clock::now();
-    void* p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
-    if (p == MAP_FAILED) return;
-    (void)madvise(p, bytes, MADV_HUGEPAGE);
-    const size_t nt = 16, chunk = ((bytes + nt - 1) / nt + 4095) & ~(size_t)4095;
-    std::vector<std::thread> th;
-    for (size_t t = 0; t < nt; ++t)
-        th.emplace_back([=] {
-            unsigned char* q = static_cast<unsigned char*>(p);
-            for (size_t o = t * chunk; o < std::min(bytes, (t + 1) * chunk); o += 4096) q[o] = 0;
-        });
-    for (auto& x : th) x.join();
-    im->p = p;
-    im->bytes = bytes;
-    const auto t1 = std::chrono::steady_clock::now();
-    im->registered = hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess;
-    const auto t2 = std::chrono::steady_clock::now();
-    im->msTouch = std::chrono::duration<double, std::milli>(t1 - t0).count();
-    im->msRegister = std::chrono::duration<double, std::milli>(t2 - t1).count();
-}
-
-static void host_image_release(HostImage* im) {
-    if (!im->p) return;
-    if (im->registered) (void)hipHostUnregister(im->p);
-    (void)munmap(im->p, im->bytes);
-    im->p = nullptr;
-}
-
-HostImage::~HostImage() { host_image_release(this); }   // every exit path of fill_rowstore
-
-static void host_image_free_cb(void* ctx, void* p) {
-    (void)p;
-    delete static_cast<HostImage*>(ctx);
-}
-
-extern "C" int shd_pe_fill_rowstore_ex(ShdPe* pe, ShdRowStore* st, int32_t fillFlags,
-                                       int32_t* rowResult, double* msOut) {
-    if (!pe || !st) return SHD_PE_EINVAL;
-    if (fillFlags & ~(SHD_PE_FILL_PREFER_DIRECT | SHD_PE_FILL_DIRECT_PAIRS)) return SHD_PE_EINVAL;
-    if (shd_rowstore_size(st) != 0) return SHD_PE_EINVAL;   // (adopt_image re-checks under its lock)
-    const int32_t T = (int32_t)pe->attached.size();
-    const bool wantDirect = (fillFlags & SHD_PE_FILL_DIRECT_PAIRS) != 0;
-    // the pack kernel's variant: 0 the non-direct rule alone (no flag, or
-    // DIRECT_PAIRS without a pair topology.c:2019-2021 serves directly), 1 a
-    // complete graph's direct table (k_direct_rows wrote the entries), 2 the
-    // adjacency rule (prefersDirectPaths; a complete graph whose table holds
-    // Dijkstra rows, forceMode)
-    int packMode = 0;
-    if (pe->hg.isComplete) packMode = pe->mode == 2 ? 1 : 2;
-    else if (fillFlags & SHD_PE_FILL_PREFER_DIRECT) packMode = 2;
-    if (packMode == 2 && pack_adj_lds_bytes(T, pe->hg.directed) < 0) return SHD_PE_ETOOBIG;
-    static const char* const modeName[3] = {"plain", "complete-direct", "prefer-direct"};
-    auto now = [] { return std::chrono::steady_clock::now(); };
-    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
-    std::vector<int64_t> off((size_t)T + 1);
-    shd_rowstore_image_layout(T, off.data());
-    const size_t bytes = (size_t)off[(size_t)T];
-    // a complete graph stores no non-direct path (:1321): only its direct pairs
-    const bool pack = !pe->hg.isComplete || wantDirect;
-    const auto t0 = now();
-    std::unique_ptr<HostImage> him(new HostImage);
-    std::thread prep;
-    if (pack) prep = std::thread(host_image_prepare, him.get(), bytes);   // beside the compute
-    int rc = ensure_rows(pe, 0, T);
-    const auto tc = now();
-    if (prep.joinable()) prep.join();
-    if (std::getenv("SHDPE_FILL_LOG"))
-        std::fprintf(stderr, "[shdpe] fill_rowstore (%s%s): compute %.1f ms, image %.2f GB touch %.1f ms + "
-                     "register %.1f ms (%s), join wait %.1f ms\n", pack ? modeName[packMode] : "nothing stored",
-                     pack && wantDirect ? ", direct pairs" : "", ms(t0, tc), bytes / 1e9, him->msTouch,
-                     him->msRegister, him->registered ? "registered" : "NOT registered", ms(tc, now()));
-    if (rc) return rc;
-    if (pack && !him->p) return SHD_PE_ENOMEM;
-    std::lock_guard<std::mutex> lk(pe->copyMu);
-    const DevTable* tab = nullptr;
-    Shard* s = pe->shards[0].get();
-    if (pe->gathered) tab = &s->full;
-    else if (pe->G == 1) tab = &s->tab;
-    else return SHD_PE_ENOTOWNED;          // rows spread over shards: gather first
-    if (hipSetDevice(s->device) != hipSuccess) return SHD_PE_EHIP;
-    if (pack && packMode == 2 && !s->dPosOf) {   // once per engine
-        void* d = nullptr;
-        if (hipMalloc(&d, pe->posOf.size() * 4) != hipSuccess) return SHD_PE_ENOMEM;
-        if (hipMemcpy(d, pe->posOf.data(), pe->posOf.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return SHD_PE_EHIP;
-        }
-        s->dPosOf = static_cast<int32_t*>(d);
-    }
-    void *dImg = nullptr, *dOff = nullptr, *dAcc = nullptr, *dAll = nullptr;
-    void* const hImg = him->p;
-    struct Free {   // device temporaries, every exit path (the host image: ~HostImage)
-        void** p[4];
-        ~Free() {
-            for (void** q : p) if (*q) (void)hipFree(*q);
-        }
-    } fr{{&dImg, &dOff, &dAcc, &dAll}};
-    if ((pack && hipMalloc(&dImg, bytes) != hipSuccess) ||
-        hipMalloc(&dOff, off.size() * 8) != hipSuccess || hipMalloc(&dAcc, 16) != hipSuccess ||
-        hipMalloc(&dAll, (size_t)T * 4) != hipSuccess)
-        return SHD_PE_ENOMEM;
-    const auto t1 = now();
-    const unsigned long long acc0[2] = {0ull, 0x7FF0000000000000ull};
-    unsigned long long acc[2] = {0ull, 0ull};
-    hipError_t e = hipMemcpyAsync(dOff, off.data(), off.size() * 8, hipMemcpyHostToDevice, s->copyStream);
-    if (e == hipSuccess) e = hipMemcpyAsync(dAcc, acc0, 16, hipMemcpyHostToDevice, s->copyStream);
-    if (e == hipSuccess) {
-        if (pack && launch_pack_rowstore(*tab, (const int64_t*)dOff, (uint8_t*)dImg,
-                                         (unsigned long long*)dAcc, packMode, &s->dgAux, s->dPosOf,
-                                         wantDirect, pe->hg.isComplete, s->copyStream))
-            return SHD_PE_ETOOBIG;
-        launch_rows_all_success(*tab, (int32_t*)dAll, s->copyStream);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) e = hipStreamSynchronize(s->copyStream);
-    const auto t2 = now();
-    if (e == hipSuccess && pack) e = hipMemcpyAsync(hImg, dImg, bytes, hipMemcpyDeviceToHost, s->copyStream);
-    if (e == hipSuccess) e = hipMemcpyAsync(acc, dAcc, 16, hipMemcpyDeviceToHost, s->copyStream);
-    if (e == hipSuccess && rowResult)
-        e = hipMemcpyAsync(rowResult, dAll, (size_t)T * 4, hipMemcpyDeviceToHost, s->copyStream);
-    if (e == hipSuccess) e = hipStreamSynchronize(s->copyStream);
-    const auto t3 = now();
-    if (e != hipSuccess) return SHD_PE_EHIP;
-    if (pack) {
-        double mn;
-        std::memcpy(&mn, &acc[1], 8);
-        rc = shd_rowstore_adopt_image(st, hImg, (int64_t)bytes, host_image_free_cb, him.get(),
-                                      (int64_t)acc[0], mn);
-        if (rc) return rc;
-        him.release();   // the store owns it now
-    }
-    if (msOut) { msOut[0] = ms(t0, t1); msOut[1] = ms(t1, t2); msOut[2] = ms(t2, t3); }
-    return SHD_PE_OK;
-}
-
-extern "C" int shd_pe_fill_rowstore(ShdPe* pe, ShdRowStore* st, int32_t* rowResult, double* msOut) {
-    return shd_pe_fill_rowstore_ex(pe, st, 0, rowResult, msOut);
-}
-
-// ---------------------------------------------------------------------------
-// Gather: the whole table on every device of this engine (and, with a
-// cross-process communicator, of every engine).
-// ---------------------------------------------------------------------------
-static int ensure_full(ShdPe* pe, Shard* s, Shard* owner) {
-    if (s != owner) { s->full = owner->full; return SHD_PE_OK; }
-    if (s->full.lat) return SHD_PE_OK;
-    const size_t T = pe->attached.size(), cells = T * T;
-    if (pe->G == 1) { s->full = s->tab; return SHD_PE_OK; }   // the shard is the table
-    HIPCHK(hipSetDevice(s->device));
-    int rc;
-    void *lat, *rel, *hops, *flags, *pred = nullptr;
-    if ((rc = dev_alloc(s, &lat, cells * 8)) || (rc = dev_alloc(s, &rel, cells * 8)) ||
-        (rc = dev_alloc(s, &hops, cells * 4)) || (rc = dev_alloc(s, &flags, cells)))
-        return rc;
-    if (pe->opt.storePred && (rc = dev_alloc(s, &pred, cells * 4))) return rc;
-    s->full = DevTable{(double*)lat, (double*)rel, (int32_t*)hops, (int32_t*)pred, (uint8_t*)flags,
-                       (int64_t)T, 0};
-    return SHD_PE_OK;
-}
-
-struct Field { size_t off; size_t esize; ncclDataType_t type; };
-
-static void table_fields(const ShdPe* pe, std::vector<Field>& f) {
-    f = {{offsetof(DevTable, lat), 8, ncclUint64}, {offsetof(DevTable, rel), 8, ncclUint64},
-         {offsetof(DevTable, hops), 4, ncclInt32}, {offsetof(DevTable, flags), 1, ncclUint8}};
-    if (pe->opt.storePred) f.push_back({offsetof(DevTable, pred), 4, ncclInt32});
-}
-
-static void* field_ptr(const DevTable& t, const Field& f) {
-    return *reinterpret_cast<void* const*>(reinterpret_cast<const char*>(&t) + f.off);
-}
-
-static int gather_locked(ShdPe* pe) {
-    const int32_t T = (int32_t)pe->attached.size();
-    std::vector<int32_t> all;
-    for (int32_t p = pe->ownStart; p < pe->ownEnd; ++p)
-        if (!row_done(pe, p)) all.push_back(p);
-    int rc = compute_positions_locked(pe, all.data(), (int32_t)all.size());
-    if (rc) return rc;
-    for (auto& s : pe->shards) if ((rc = ensure_table(pe, s.get()))) return rc;
-    // one full table per distinct device, owned by its first shard
-    for (auto& s : pe->shards) {
-        Shard* owner = nullptr;
-        for (auto& o : pe->shards)
-            if (o->device == s->device) { owner = o.get(); break; }
-        if ((rc = ensure_full(pe, s.get(), owner))) return rc;
-    }
-    std::vector<Field> fields;
-    table_fields(pe, fields);
-    const size_t ts = (size_t)T;
-    Shard* s0 = pe->shards[0].get();
-    bool distinct = true;
-    for (size_t i = 0; i < pe->shards.size(); ++i)
-        for (size_t j = 0; j < i; ++j)
-            if (pe->shards[i]->device == pe->shards[j]->device) distinct = false;
-    // in-process RCCL over xGMI (distinct devices): one communicator per
-    // device, created before the timed region
-    if (pe->G > 1 && !pe->xcomm && distinct && !s0->comm) {
-        std::vector<ncclComm_t> comms(pe->shards.size());
-        std::vector<int> devs;
-        for (auto& s : pe->shards) devs.push_back(s->device);
-        if (ncclCommInitAll(comms.data(), (int)devs.size(), devs.data()) != ncclSuccess)
-            return SHD_PE_ECOMM;
-        for (size_t i = 0; i < comms.size(); ++i) pe->shards[i]->comm = comms[i];
-    }
-    struct Events {   // destroyed on every exit path
-        hipEvent_t e[2] = {nullptr, nullptr};
-        ~Events() { for (hipEvent_t x : e) if (x) (void)hipEventDestroy(x); }
-    } ev;
-    HIPCHK(hipSetDevice(s0->device));
-    HIPCHK(hipEventCreate(&ev.e[0]));
-    HIPCHK(hipEventCreate(&ev.e[1]));
-    hipEvent_t e0 = ev.e[0], e1 = ev.e[1];
-    HIPCHK(hipEventRecord(e0, s0->stream));
-    if (pe->G == 1 && !pe->xcomm) {
-        // nothing to exchange
-    } else if (pe->xcomm) {
-        // cross-process: every process owns one shard (nDevices == 1), rows
-        // contiguous per shard.  Equal blocks (the plan's usual outcome, e.g.
-        // C4 over 8 ranks: 2,048 rows each): one ncclAllGather per field
-        // straight into the full table; otherwise a group of per-shard
-        // broadcasts (an all-gather-v with blocks landing in place)
-        Shard* s = s0;
-        bool equal = true;
-        for (int g = 1; g < pe->G; ++g)
-            equal = equal && pe->bounds[g + 1] - pe->bounds[g] == pe->bounds[1] - pe->bounds[0];
-        if (ncclGroupStart() != ncclSuccess) return SHD_PE_ECOMM;
-        if (equal) {
-            const size_t nr = (size_t)(pe->bounds[1] - pe->bounds[0]);
-            for (const Field& f : fields)
-                if (nr && ncclAllGather(field_ptr(s->tab, f), field_ptr(s->full, f), nr * ts, f.type, pe->xcomm,
-                                        s->stream) != ncclSuccess)
-                    rc = SHD_PE_ECOMM;
-        } else {
-            for (int g = 0; g < pe->G && rc == SHD_PE_OK; ++g) {
-                const size_t r0 = (size_t)pe->bounds[g], nr = (size_t)(pe->bounds[g + 1] - pe->bounds[g]);
-                if (!nr) continue;
-                for (const Field& f : fields) {
-                    char* dst = (char*)field_ptr(s->full, f) + r0 * ts * f.esize;
-                    const void* src = g == s->gindex ? field_ptr(s->tab, f) : (const void*)dst;
-                    if (ncclBroadcast(src, dst, nr * ts, f.type, g, pe->xcomm, s->stream) != ncclSuccess)
-                        rc = SHD_PE_ECOMM;
-                }
-            }
-        }
-        if (ncclGroupEnd() != ncclSuccess) rc = SHD_PE_ECOMM;
-        if (rc) return rc;
-    } else {
-        if (distinct) {
-            // in-process RCCL over xGMI: a group of per-shard broadcasts
-            if (ncclGroupStart() != ncclSuccess) return SHD_PE_ECOMM;
-            for (size_t r = 0; r < pe->shards.size(); ++r) {
-                Shard* root = pe->shards[r].get();
-                const size_t r0 = (size_t)root->rowStart, nr = (size_t)root->rowCount;
-                if (!nr) continue;
-                for (auto& sp : pe->shards) {
-                    Shard* s = sp.get();
-                    for (const Field& f : fields) {
-                        char* dst = (char*)field_ptr(s->full, f) + r0 * ts * f.esize;
-                        const void* src = s == root ? field_ptr(root->tab, f) : (const void*)dst;
-                        if (ncclBroadcast(src, dst, nr * ts, f.type, (int)r, s->comm, s->stream) !=
-                            ncclSuccess)
-                            rc = SHD_PE_ECOMM;
-                    }
-                }
-            }
-            if (ncclGroupEnd() != ncclSuccess) rc = SHD_PE_ECOMM;
-            if (rc) return rc;
-        } else {
-            // logical shards sharing a device (tests): device / peer copies
-            for (auto& src : pe->shards) {
-                if (!src->rowCount) continue;
-                for (auto& dstS : pe->shards) {
-                    if (!dstS->fullOwner) continue;
-                    HIPCHK(hipSetDevice(dstS->device));
-                    for (const Field& f : fields) {
-                        char* dst = (char*)field_ptr(dstS->full, f) + (size_t)src->rowStart * ts * f.esize;
-                        HIPCHK(hipMemcpyAsync(dst, field_ptr(src->tab, f),
-                                              (size_t)src->rowCount * ts * f.esize,
-                                              hipMemcpyDeviceToDevice, dstS->stream));
-                    }
-                }
-            }
-        }
-    }
-    for (auto& s : pe->shards) {
-        HIPCHK(hipSetDevice(s->device));
-        HIPCHK(hipStreamSynchronize(s->stream));
-    }
-    HIPCHK(hipSetDevice(s0->device));
-    HIPCHK(hipEventRecord(e1, s0->stream));
-    HIPCHK(hipEventSynchronize(e1));
-    pe->msGather += elapsed(e0, e1);
-    for (int32_t p = 0; p < T; ++p) pe->rowDone[p].store(1, std::memory_order_release);
-    pe->gathered = true;
-    return SHD_PE_OK;
-}
-
-// Host-transport assembly (no RCCL): rows of other engines' shards arrive in
-// host buffers (MPI, sockets, torch.distributed/gloo -- e.g. several ranks
-// sharing one GPU, where RCCL refuses a communicator) and are written into
-// the full table on every device of this engine; this engine's own rows are
-// copied in on the first call.  Once all T rows are present the engine reads
-// every row from the full table, as after shd_pe_gather.
-extern "C" int shd_pe_put_rows(ShdPe* pe, int32_t start, int32_t count, const double* lat,
-                               const double* rel, const int32_t* hops, const int32_t* pred,
-                               const uint8_t* flags) {
-    if (!pe || start < 0 || count < 0 || (int64_t)start + count > (int64_t)pe->attached.size())
-        return SHD_PE_EINVAL;
-    if (!lat || !rel || !hops || !flags || (pe->opt.storePred && !pred)) return SHD_PE_EINVAL;
-    if (pe->opt.shardCount < 2 || pe->opt.nDevices != 1) return SHD_PE_EINVAL;
-    if (start < pe->ownEnd && start + count > pe->ownStart) return SHD_PE_EINVAL;   // own rows
-    if (count == 0) return SHD_PE_OK;
-    std::lock_guard<std::mutex> lk(pe->mu);
-    std::lock_guard<std::mutex> lk2(pe->copyMu);
-    Shard* s = pe->shards[0].get();
-    int rc = ensure_table(pe, s);
-    if (rc) return rc;
-    if (!pe->putInit) {
-        std::vector<int32_t> all;
-        for (int32_t p = pe->ownStart; p < pe->ownEnd; ++p)
-            if (!row_done(pe, p)) all.push_back(p);
-        if ((rc = compute_positions_locked(pe, all.data(), (int32_t)all.size()))) return rc;
-        if ((rc = ensure_full(pe, s, s))) return rc;
-        HIPCHK(hipSetDevice(s->device));
-        std::vector<Field> fields;
-        table_fields(pe, fields);
-        const size_t ts = pe->attached.size();
-        for (const Field& f : fields)
-            HIPCHK(hipMemcpyAsync((char*)field_ptr(s->full, f) + (size_t)s->rowStart * ts * f.esize,
-                                  field_ptr(s->tab, f), (size_t)s->rowCount * ts * f.esize,
-                                  hipMemcpyDeviceToDevice, s->stream));
-        HIPCHK(hipStreamSynchronize(s->stream));
-        pe->putInit = true;
-    }
-    HIPCHK(hipSetDevice(s->device));
-    const size_t ts = pe->attached.size(), o = (size_t)start * ts, cells = (size_t)count * ts;
-    HIPCHK(hipMemcpyAsync(s->full.lat + o, lat, cells * 8, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->full.rel + o, rel, cells * 8, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->full.hops + o, hops, cells * 4, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipMemcpyAsync(s->full.flags + o, flags, cells, hipMemcpyHostToDevice, s->stream));
-    if (pe->opt.storePred)
-        HIPCHK(hipMemcpyAsync(s->full.pred + o, pred, cells * 4, hipMemcpyHostToDevice, s->stream));
-    HIPCHK(hipStreamSynchronize(s->stream));
-    if (pe->putSeen.empty()) pe->putSeen.assign(ts, 0);
-    for (int32_t p = start; p < start + count; ++p)
-        if (!pe->putSeen[(size_t)p]) { pe->putSeen[(size_t)p] = 1; ++pe->putRows; }
-    if (pe->putRows + (pe->ownEnd - pe->ownStart) >= (int64_t)ts) {
-        for (size_t p = 0; p < ts; ++p) pe->rowDone[p].store(1, std::memory_order_release);
-        pe->gathered = true;
-    }
-    return SHD_PE_OK;
-}
-
-extern "C" int shd_pe_gather(ShdPe* pe) {
-    if (!pe) return SHD_PE_EINVAL;
-    std::lock_guard<std::mutex> lk(pe->mu);
-    std::lock_guard<std::mutex> lk2(pe->copyMu);
-    if (pe->G > 1 && pe->opt.shardCount > 1 && !pe->xcomm) return SHD_PE_ECOMM;
-    return gather_locked(pe);
-}
-
-extern "C" int shd_pe_comm_unique_id(void* out, int32_t bytes) {
-    if (!out || bytes < (int32_t)sizeof(ncclUniqueId)) return SHD_PE_EINVAL;
-    ncclUniqueId id;
-    if (ncclGetUniqueId(&id) != ncclSuccess) return SHD_PE_ECOMM;
-    std::memcpy(out, &id, sizeof(id));
-    return SHD_PE_OK;
-}
-
-extern "C" int shd_pe_comm_init(ShdPe* pe, const void* uniqueId, int32_t bytes) {
-    if (!pe || !uniqueId || bytes < (int32_t)sizeof(ncclUniqueId)) return SHD_PE_EINVAL;
-    // (shardCount 1: a one-rank communicator -- the gather then runs the same
-    // RCCL calls as at N > 1, an in-place all-gather of the engine's own
-    // rows: how the RCCL path is exercised on a one-GPU box)
-    if (pe->opt.nDevices != 1 || pe->opt.shardCount < 1) return SHD_PE_EINVAL;
-    std::lock_guard<std::mutex> lk(pe->mu);
-    if (pe->xcomm) return SHD_PE_OK;
-    ncclUniqueId id;
-    std::memcpy(&id, uniqueId, sizeof(id));
-    if (hipSetDevice(pe->shards[0]->device) != hipSuccess) return SHD_PE_EHIP;
-    if (ncclCommInitRank(&pe->xcomm, pe->opt.shardCount, id, pe->opt.shardIndex) != ncclSuccess) {
-        pe->xcomm = nullptr;
-        return SHD_PE_ECOMM;
-    }
     return SHD_PE_OK;
 }
 

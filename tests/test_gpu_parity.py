@@ -150,6 +150,11 @@ def test_bulk_get_rows_matches_get_row(E):
     eng.get_rows(5, 2990, out=pin)
     for k in ("lat", "rel", "hops", "pred", "flags"):
         assert np.array_equal(blk[k].view(np.uint8), pin[k].view(np.uint8)), k
+    # two fields only, pageable: the packed-subset staging layout across block boundaries
+    sub = eng.get_rows(5, 2990, out={"lat": np.empty((2990, 3000)), "flags": np.empty((2990, 3000), np.uint8)})
+    for k in ("lat", "flags"):
+        assert np.array_equal(blk[k].view(np.uint8), sub[k].view(np.uint8)), k
+    assert sub["rel"] is None and sub["hops"] is None and sub["pred"] is None
     for i in (0, 1, 1337, 2989):
         one = eng.get_row(int(eng.attached[5 + i]))
         for k in ("lat", "rel", "hops", "pred", "flags"):

@@ -225,6 +225,173 @@ def test_put_rows_host_transport_and_checksums(E):
 
 
 # ---------------------------------------------------------------------------
+# row transport: field subsets, no predecessors, device copies (pe_rows.hip)
+# ---------------------------------------------------------------------------
+@pytest.fixture(scope="module")
+def small(E):
+    """A 300-row table and its rows from a one-shard engine with predecessors
+    (read once, never written): what every route below must reproduce."""
+    top = G.rgg(300, seed=71)
+    att = np.arange(top.n, dtype=np.int32)
+    one = E.Engine(top, att)
+    one.compute_all()
+    ref = _all_rows(one)
+    one.close()
+    for v in ref.values():
+        v.setflags(write=False)
+    return top, att, ref
+
+
+def _same_fields(got, ref, fields, ctx):
+    for k in FIELDS:
+        if k in fields:
+            assert np.array_equal(got[k].view(np.uint8), ref[k].view(np.uint8)), (ctx, k)
+        else:
+            assert got[k] is None, (ctx, k)
+
+
+_DTYPES = {"lat": np.float64, "rel": np.float64, "hops": np.int32, "pred": np.int32, "flags": np.uint8}
+
+
+def test_get_rows_field_subsets_across_pieces(E, small):
+    """get_rows for a subset of the fields over rows [1, T-1) of three shards
+    (three table pieces, no boundary aligned), into pageable buffers (packed
+    staging blocks) and into pinned ones (direct DMA): byte-equal to the same
+    fields of a plain five-field read, before and after the gather; fields
+    not asked for stay None."""
+    top, att, _ = small
+    eng = E.Engine(top, att, devices=[0, 0, 0])
+    eng.compute_all()
+    T = eng.T
+    b = eng.shard_bounds()
+    assert 1 < b[1] < b[2] < T - 1
+    for state in ("per-shard", "gathered"):
+        if state == "gathered":
+            eng.gather()
+        full = eng.get_rows(1, T - 2)
+        assert all(full[k] is not None for k in FIELDS)
+        for subset in (("lat", "flags"), ("hops",), ("rel", "pred")):
+            pageable = {k: np.full((T - 2, T), 0x5A, _DTYPES[k]) if k in subset else None for k in FIELDS}
+            got = eng.get_rows(1, T - 2, out=pageable)
+            _same_fields(got, full, subset, f"{state} pageable {subset}")
+            pinned = eng.pinned_rows(T - 2, fields=subset)
+            for k in subset:
+                pinned[k][...] = 0x5A
+            got = eng.get_rows(1, T - 2, out=pinned)
+            _same_fields(got, full, subset, f"{state} pinned {subset}")
+    eng.close()
+
+
+def test_engines_without_predecessors(E, small):
+    """store_pred=False, one shard and two: the four remaining fields are
+    byte-equal to those of an engine that stores predecessors, before and
+    after the gather; the device fingerprints of the two engines agree; a
+    pred buffer is refused; and two shardCount=2 engines assemble the same
+    table through put_rows."""
+    top, att, ref = small
+    four = tuple(k for k in FIELDS if k != "pred")
+    cks = []
+    for devices in ([0], [0, 0]):
+        eng = E.Engine(top, att, devices=devices, store_pred=False)
+        eng.compute_all()
+        for state in ("per-shard", "gathered"):
+            if state == "gathered":
+                eng.gather()
+            _same_fields(_all_rows(eng), ref, four, f"{len(devices)} shard(s) {state}")
+            cks.append(eng.row_checksums(0, eng.T))
+        out = {k: np.empty((2, eng.T), _DTYPES[k]) for k in FIELDS}
+        with pytest.raises(ValueError):
+            eng.get_rows(0, 2, out=out)
+        rc = eng._lib.shd_pe_get_rows(eng.h, 0, 2, *(E._p(out[k]) for k in ("lat", "rel", "hops", "pred", "flags")))
+        assert rc == E.EINVAL
+        eng.close()
+    for ck in cks[1:]:
+        assert np.array_equal(ck, cks[0])
+    engs = [E.Engine(top, att, store_pred=False, shard_index=i, shard_count=2) for i in range(2)]
+    for e in engs:
+        e.compute_all()
+    for a, b in ((0, 1), (1, 0)):
+        s, c = engs[b].owned
+        engs[a].put_rows(s, engs[b].get_rows(s, c))
+    for e in engs:
+        _same_fields(_all_rows(e), ref, four, "put_rows assembled, no pred")
+        assert np.array_equal(e.row_checksums(0, e.T), cks[0])
+        e.close()
+
+
+HIP_MEMCPY_DEVICE_TO_HOST = 2       # hipMemcpyKind::hipMemcpyDeviceToHost (hip/driver_types.h)
+
+
+def _hip(lib):
+    """The few HIP runtime calls the device-buffer test needs, typed, from the
+    runtime libshdpe.so itself links (a dependency's symbols resolve through
+    the library's handle)."""
+    import ctypes as C
+    sig = {"hipSetDevice": [C.c_int], "hipMalloc": [C.POINTER(C.c_void_p), C.c_size_t],
+           "hipMemset": [C.c_void_p, C.c_int, C.c_size_t], "hipDeviceSynchronize": [],
+           "hipMemcpy": [C.c_void_p, C.c_void_p, C.c_size_t, C.c_int], "hipFree": [C.c_void_p]}
+    for name, args in sig.items():
+        fn = getattr(lib, name)
+        fn.argtypes, fn.restype = args, C.c_int      # hipError_t, 0 = hipSuccess
+    return lib
+
+
+class _DeviceBuf:
+    """A (shape, dtype) array in device memory, every byte `fill`.  Not a
+    torch tensor: torch's wheel carries a second copy of the HIP runtime, and
+    the second copy to start in a process finds no GPU."""
+
+    def __init__(self, lib, shape, dtype, fill):
+        import ctypes as C
+        self._hip, self.shape, self.dtype = _hip(lib), shape, np.dtype(dtype)
+        self.nbytes = int(np.prod(shape)) * self.dtype.itemsize
+        self.p = C.c_void_p()
+        assert self._hip.hipSetDevice(0) == 0
+        assert self._hip.hipMalloc(C.byref(self.p), self.nbytes) == 0
+        assert self._hip.hipMemset(self.p, fill, self.nbytes) == 0
+        assert self._hip.hipDeviceSynchronize() == 0
+
+    def host(self):
+        out = np.empty(self.shape, self.dtype)
+        assert self._hip.hipMemcpy(out.ctypes.data, self.p, self.nbytes, HIP_MEMCPY_DEVICE_TO_HOST) == 0
+        return out
+
+    def free(self):
+        if self.p:
+            assert self._hip.hipFree(self.p) == 0
+            self.p = None
+
+
+def test_copy_rows_device(E, small):
+    """shd_pe_copy_rows_device into caller device buffers, rows [1, T-1) of
+    two shards: byte-equal to get_rows before and after the gather; with only
+    d_hops given, hops is written."""
+    top, att, _ = small
+    eng = E.Engine(top, att, devices=[0, 0])
+    eng.compute_all()
+    T = eng.T
+    n = T - 2
+    b = eng.shard_bounds()
+    assert 1 < b[1] < T - 1
+    four = tuple(k for k in FIELDS if k != "pred")
+    for state in ("per-shard", "gathered"):
+        if state == "gathered":
+            eng.gather()
+        want = eng.get_rows(1, n)
+        d = {k: _DeviceBuf(eng._lib, (n, T), _DTYPES[k], 0x5A) for k in four}
+        eng.copy_rows_device(1, n, d_lat=d["lat"].p.value, d_rel=d["rel"].p.value,
+                             d_hops=d["hops"].p.value, d_flags=d["flags"].p.value)
+        for k in four:
+            assert np.array_equal(d[k].host().view(np.uint8), want[k].view(np.uint8)), (state, k)
+            d[k].free()
+    hops = _DeviceBuf(eng._lib, (n, T), np.int32, 0x5A)
+    eng.copy_rows_device(1, n, d_hops=hops.p.value)
+    assert np.array_equal(hops.host(), want["hops"])
+    hops.free()
+    eng.close()
+
+
+# ---------------------------------------------------------------------------
 # concurrent readers (header: get_row may be called from any thread)
 # ---------------------------------------------------------------------------
 def test_get_row_from_8_threads(E):

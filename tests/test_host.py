@@ -332,3 +332,26 @@ def test_row_checksums_host_properties(lib):
     assert row_checksums_host(u)[9] != base[9]
     nopred = {k: v for k, v in t.items() if k != "pred"}
     assert not np.array_equal(row_checksums_host(nopred), base)
+
+
+def test_table_field_walk_under_sanitizers(tmp_path):
+    """pe_device.hpp's field table, for_each_field and stage_view (what every
+    row copy of pe_rows.hip goes through) driven with memcpy over host arrays,
+    built with -fsanitize=address,undefined: field subsets, a missing pred on
+    either side, sub-ranges and a two-block packed staging round trip copy
+    exactly the cells asked for and leave every other byte alone."""
+    import shutil
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    exe = str(tmp_path / "table_fields")
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+           "-I", os.path.join(ROOT, "shadow-1_amd", "csrc"),
+           os.path.join(ROOT, "tests", "native", "table_fields.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "asan" in (b.stderr or "").lower():
+        pytest.skip("AddressSanitizer runtime unavailable")
+    assert b.returncode == 0, b.stderr[-2000:]
+    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1 exitcode=66", UBSAN_OPTIONS="halt_on_error=1 exitcode=66")
+    r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and "OK" in r.stdout and not r.stderr.strip(), (r.stdout, r.stderr[-3000:])
