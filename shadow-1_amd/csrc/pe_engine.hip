@@ -27,12 +27,12 @@
 #include <memory>
 #include <mutex>
 #include <new>
-#include <queue>
 #include <chrono>
 #include <thread>
 #include <vector>
 
 #include "pe_engine.hpp"
+#include "pe_plan.hpp"
 
 using namespace shdpe;
 
@@ -45,6 +45,15 @@ static int dev_upload(Shard* s, T** dst, const std::vector<T, A>& src) {
     if (!src.empty())
         HIPCHK(hipMemcpy(*dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
     return SHD_PE_OK;
+}
+
+// ... into a member of DevGraph (pointers to const)
+template <class T, class A>
+static int dev_upload(Shard* s, const T** dst, const std::vector<T, A>& src) {
+    T* p = nullptr;
+    const int rc = dev_upload(s, &p, src);
+    *dst = p;
+    return rc;
 }
 
 // SHDPE_* tuning variables are read only under SHD_PE_DEBUG_ENV: a library
@@ -350,110 +359,6 @@ static int configure(ShdPe* pe, Shard* sh) {
     return SHD_PE_OK;
 }
 
-// Batch order of the table positions: sources of one batch should have
-// similar distance profiles so their delta-stepping frontiers coincide.
-//   order 0: BFS visit rank (components in vertex order);
-//   order 1 (default): nearest-hub cells -- a multi-source Dijkstra from
-//            the K highest-degree vertices gives every vertex its closest
-//            hub; sources sort by (hub, distance to it), so a batch holds
-//            sources that reach the rest of the graph through one hub, and
-//            the distance to the hub becomes the lane's bucket key offset
-//            (k_batch_rows: a lane's key is dist + maxOff - off).
-// Scheduling only: results never depend on it (tools/sim/ models the
-// schedule: C4 arc visits 3.9 -> 2.2 x m per batch with offsets, dirty
-// lanes and a far set at delta = mean arc latency).
-static void compute_ranks(ShdPe* pe) {
-    const HostGraph& g = pe->hg;
-    std::vector<int32_t> order;
-    order.reserve(g.n);
-    if (pe->tu.batchOrder == 1) {
-        const int32_t K = (int32_t)std::max<int64_t>(1, std::min<int64_t>(256, g.n / 400));
-        std::vector<int32_t> byDeg(g.n);
-        for (int32_t v = 0; v < g.n; ++v) byDeg[v] = v;
-        std::stable_sort(byDeg.begin(), byDeg.end(), [&](int32_t a, int32_t b) {
-            return g.rowPtr[a + 1] - g.rowPtr[a] > g.rowPtr[b + 1] - g.rowPtr[b];
-        });
-        std::vector<double> dist(g.n, INFINITY);
-        std::vector<int32_t> owner(g.n, INT32_MAX);
-        typedef std::pair<double, int32_t> QE;
-        std::priority_queue<QE, std::vector<QE>, std::greater<QE>> q;
-        for (int32_t k = 0; k < K; ++k) { dist[byDeg[k]] = 0.0; owner[byDeg[k]] = k; q.push({0.0, byDeg[k]}); }
-        while (!q.empty()) {
-            const QE top = q.top();
-            q.pop();
-            const int32_t u = top.second;
-            if (top.first > dist[u]) continue;
-            for (int32_t a = g.rowPtr[u]; a < g.rowPtr[u + 1]; ++a) {
-                const int32_t v = g.col[a];
-                const double nd = dist[u] + g.lat[a];
-                if (nd < dist[v] || (nd == dist[v] && owner[u] < owner[v])) {
-                    dist[v] = nd;
-                    owner[v] = owner[u];
-                    q.push({nd, v});
-                }
-            }
-        }
-        for (int32_t v = 0; v < g.n; ++v) order.push_back(v);
-        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
-            return owner[a] != owner[b] ? owner[a] < owner[b] : dist[a] < dist[b];
-        });
-        // bucket key offsets: a source's distance to its hub, so the lanes of
-        // a batch reach the vertices behind the hub in the same bucket
-        pe->rowOff.assign(pe->attached.size(), 0.0);
-        for (size_t p = 0; p < pe->attached.size(); ++p) {
-            const double d = dist[pe->attached[p]];
-            pe->rowOff[p] = std::isfinite(d) ? d : 0.0;
-        }
-    } else {
-        std::vector<uint8_t> seen(g.n, 0);
-        for (int32_t r = 0; r < g.n; ++r) {
-            if (seen[r]) continue;
-            seen[r] = 1;
-            size_t head = order.size();
-            order.push_back(r);
-            while (head < order.size()) {
-                const int32_t u = order[head++];
-                for (int32_t a = g.rowPtr[u]; a < g.rowPtr[u + 1]; ++a) {
-                    const int32_t v = g.col[a];
-                    if (!seen[v]) { seen[v] = 1; order.push_back(v); }
-                }
-                if (g.directed) {
-                    for (int32_t a = g.inPtr[u]; a < g.inPtr[u + 1]; ++a) {
-                        const int32_t v = g.inCol[a];
-                        if (!seen[v]) { seen[v] = 1; order.push_back(v); }
-                    }
-                }
-            }
-        }
-    }
-    pe->rank.assign(pe->attached.size(), 0);
-    int32_t k = 0;
-    for (int32_t v : order)
-        if (pe->posOf[v] >= 0) pe->rank[pe->posOf[v]] = k++;
-}
-
-// Row-shard plan: G contiguous position ranges with equal numbers of kernel
-// work units (a unit = one batch of 16 rows in the batched sparse kernel,
-// one row otherwise).  Per-unit cost is near-uniform for this path: every
-// SSSP row settles all n vertices, every dense / direct row is n (T) wide
-// (measured per-batch cycle spread in DESIGN.md §6), so equal units are the
-// balanced split, and contiguous ranges let the all-gather land rows in
-// place.  Host-only (no device), exported for the CPU tests.
-extern "C" int shd_pe_plan_shards(int32_t T, int32_t G, int32_t unit, int32_t* bounds) {
-    if (T < 0 || G < 1 || unit < 1 || !bounds) return SHD_PE_EINVAL;
-    const int64_t units = ((int64_t)T + unit - 1) / unit;
-    for (int g = 0; g < G; ++g)
-        bounds[g] = (int32_t)std::min<int64_t>(T, (units * g / G) * unit);
-    bounds[G] = T;
-    return SHD_PE_OK;
-}
-
-static void plan_shards(ShdPe* pe) {
-    pe->bounds.assign(pe->G + 1, 0);
-    (void)shd_pe_plan_shards((int32_t)pe->attached.size(), pe->G, pe->batched ? 16 : 1,
-                             pe->bounds.data());
-}
-
 static void destroy_shard(Shard* s) {
     if (!s) return;
     (void)hipSetDevice(s->device);
@@ -468,161 +373,82 @@ static void destroy_shard(Shard* s) {
     if (s->dCoopAbort) (void)hipHostFree(s->dCoopAbort);
 }
 
-// Upload the graph as a DevGraph.  oldOf == null: the caller's vertex ids.
-// Otherwise device id k is the caller's vertex oldOf[k]: per-vertex arrays
-// are permuted and arc targets renamed, but every row keeps its arcs in
-// igraph incidence order (ascending CALLER id), so every pop / push order --
-// and the tie-breaking that depends on it -- is unchanged; kernels map pred
-// back through DevGraph::oldId.
-static int upload_graph(ShdPe* pe, Shard* sh, DevGraph* out, const std::vector<int32_t>* oldOf) {
-    const HostGraph& g0 = pe->hg;
-    const int32_t n = g0.n;
-    const int64_t m = g0.nArcs();
-    int rc;
-    // permuted host copies (only when relabelling)
-    std::vector<int32_t> newOf, rp, ip;
-    hvec<int32_t> col, o2i, icol;
-    hvec<double> lat, rel, ilat, irel, flt, srl;
-    std::vector<double> vrel, sl, sr, sml, smr;
-    std::vector<uint8_t> hs;
-    std::vector<int32_t> att;
-    const bool perm = oldOf != nullptr;
-    if (perm) {
-        const std::vector<int32_t>& od = *oldOf;
-        newOf.assign(n, 0);
-        for (int32_t k = 0; k < n; ++k) newOf[od[k]] = k;
-        rp.assign(n + 1, 0);
-        for (int32_t k = 0; k < n; ++k) rp[k + 1] = rp[k] + (g0.rowPtr[od[k] + 1] - g0.rowPtr[od[k]]);
-        std::vector<int32_t> arcNew(m);
-        col.resize(m); lat.resize(m); rel.resize(m); o2i.resize(m);
-        if (g0.latFold) { flt.resize(m); srl.resize(m); }
-        for (int32_t k = 0; k < n; ++k) {
-            const int32_t u = od[k];
-            for (int32_t a = g0.rowPtr[u], j = rp[k]; a < g0.rowPtr[u + 1]; ++a, ++j) {
-                arcNew[a] = j;
-                col[j] = newOf[g0.col[a]];
-                lat[j] = g0.lat[a];
-                rel[j] = g0.rel[a];
-                if (g0.latFold) { flt[j] = g0.foldLat[a]; srl[j] = g0.selfPathRel[a]; }
-            }
-        }
-        if (g0.directed) {
-            ip.assign(n + 1, 0);
-            for (int32_t k = 0; k < n; ++k) ip[k + 1] = ip[k] + (g0.inPtr[od[k] + 1] - g0.inPtr[od[k]]);
-            std::vector<int32_t> inNew(m);
-            icol.resize(m); ilat.resize(m); irel.resize(m);
-            for (int32_t k = 0; k < n; ++k) {
-                const int32_t v = od[k];
-                for (int32_t a = g0.inPtr[v], j = ip[k]; a < g0.inPtr[v + 1]; ++a, ++j) {
-                    inNew[a] = j;
-                    icol[j] = newOf[g0.inCol[a]];
-                    ilat[j] = g0.inLat[a];
-                    irel[j] = g0.inRel[a];
-                }
-            }
-            for (int64_t a = 0; a < m; ++a) o2i[arcNew[a]] = inNew[g0.outToIn[a]];
-        } else {
-            for (int64_t a = 0; a < m; ++a) o2i[arcNew[a]] = arcNew[g0.outToIn[a]];
-        }
-        vrel.resize(n); sl.resize(n); sr.resize(n); hs.resize(n); sml.resize(n); smr.resize(n);
-        for (int32_t k = 0; k < n; ++k) {
-            vrel[k] = g0.vrel[od[k]]; sl[k] = g0.selfLat[od[k]];
-            sr[k] = g0.selfRel[od[k]]; hs[k] = g0.hasSelf[od[k]];
-            sml[k] = g0.selfMinLat[od[k]]; smr[k] = g0.selfMinRel[od[k]];
-        }
-        att.resize(pe->attached.size());
-        for (size_t i = 0; i < att.size(); ++i) att[i] = newOf[pe->attached[i]];
-    }
-    const std::vector<int32_t>& RP = perm ? rp : g0.rowPtr;
-    const hvec<int32_t>& COL = perm ? col : g0.col;
-    const hvec<double>& LAT = perm ? lat : g0.lat;
-    const hvec<double>& REL = perm ? rel : g0.rel;
-    const std::vector<int32_t>& ATT = perm ? att : pe->attached;
+// Upload `g` as a DevGraph; `attached` is in g's vertex ids.  oldOf == null:
+// g is the caller's graph.  Otherwise g = relabel_graph(caller's, *oldOf),
+// device id k being the caller's vertex oldOf[k]; kernels map pred back
+// through DevGraph::oldId.
+static int upload_graph(const HostGraph& g, const std::vector<int32_t>& attached,
+                        const std::vector<int32_t>* oldOf, Shard* sh, DevGraph* out) {
+    const int32_t n = g.n;
     DevGraph d{};
     d.n = n;
-    d.T = (int32_t)pe->attached.size();
+    d.T = (int32_t)attached.size();
+    int rc = SHD_PE_OK;
+    // (after a failure the rest are skipped)
+    auto up = [&](auto& member, const auto& v) { if (!rc) rc = dev_upload(sh, &member, v); };
     std::vector<uint8_t> isAtt(n, 0);
-    for (int32_t v : ATT) isAtt[v] = 1;
-    int32_t *rowPtr, *dcol, *outToIn, *datt;
-    double *dlat, *drel, *dvrel, *dsl, *dsr, *dsml, *dsmr;
-    uint8_t *dhs, *ia;
-    if ((rc = dev_upload(sh, &rowPtr, RP)) || (rc = dev_upload(sh, &dcol, COL)) ||
-        (rc = dev_upload(sh, &dlat, LAT)) || (rc = dev_upload(sh, &drel, REL)) ||
-        (rc = dev_upload(sh, &outToIn, perm ? o2i : g0.outToIn)) ||
-        (rc = dev_upload(sh, &dvrel, perm ? vrel : g0.vrel)) ||
-        (rc = dev_upload(sh, &dsl, perm ? sl : g0.selfLat)) ||
-        (rc = dev_upload(sh, &dsr, perm ? sr : g0.selfRel)) ||
-        (rc = dev_upload(sh, &dsml, perm ? sml : g0.selfMinLat)) ||
-        (rc = dev_upload(sh, &dsmr, perm ? smr : g0.selfMinRel)) ||
-        (rc = dev_upload(sh, &dhs, perm ? hs : g0.hasSelf)) || (rc = dev_upload(sh, &datt, ATT)) ||
-        (rc = dev_upload(sh, &ia, isAtt)))
-        return rc;
+    for (int32_t v : attached) isAtt[v] = 1;
+    up(d.rowPtr, g.rowPtr); up(d.col, g.col); up(d.lat, g.lat); up(d.rel, g.rel);
+    up(d.outToIn, g.outToIn);
+    up(d.vrel, g.vrel); up(d.selfLat, g.selfLat); up(d.selfRel, g.selfRel);
+    up(d.selfMinLat, g.selfMinLat); up(d.selfMinRel, g.selfMinRel); up(d.hasSelf, g.hasSelf);
+    up(d.attached, attached); up(d.isAttached, isAtt);
     {
-        std::vector<Arc> arcs(COL.size());
-        for (size_t a = 0; a < arcs.size(); ++a) arcs[a] = Arc{LAT[a], COL[a], 0};
-        Arc* da;
-        if ((rc = dev_upload(sh, &da, arcs))) return rc;
-        d.arcs = da;
-        std::vector<Arc3> a3(COL.size());
+        std::vector<Arc> arcs(g.col.size());
+        for (size_t a = 0; a < arcs.size(); ++a) arcs[a] = Arc{g.lat[a], g.col[a], 0};
+        up(d.arcs, arcs);
+        std::vector<Arc3> a3(g.col.size());
         for (size_t a = 0; a < a3.size(); ++a) {
             uint64_t bits;
-            std::memcpy(&bits, &LAT[a], 8);
-            a3[a] = Arc3{COL[a], (uint32_t)bits, (uint32_t)(bits >> 32)};
+            std::memcpy(&bits, &g.lat[a], 8);
+            a3[a] = Arc3{g.col[a], (uint32_t)bits, (uint32_t)(bits >> 32)};
         }
-        Arc3* d3;
-        if ((rc = dev_upload(sh, &d3, a3))) return rc;
-        d.arc3 = d3;
+        up(d.arc3, a3);
     }
-    d.rowPtr = rowPtr; d.col = dcol; d.lat = dlat; d.rel = drel; d.outToIn = outToIn;
-    d.vrel = dvrel; d.selfLat = dsl; d.selfRel = dsr; d.hasSelf = dhs; d.attached = datt;
-    d.selfMinLat = dsml; d.selfMinRel = dsmr;
-    d.isAttached = ia;
     {
         const int hd = sh->cfg.heavyDeg;
         std::vector<uint32_t> hb((n + 31) / 32, 0u);
         for (int32_t v = 0; v < n; ++v)
-            if (RP[v + 1] - RP[v] >= hd) hb[v >> 5] |= 1u << (v & 31);
-        uint32_t* dhb;
-        if ((rc = dev_upload(sh, &dhb, hb))) return rc;
-        d.heavyBits = dhb;
+            if (g.rowPtr[v + 1] - g.rowPtr[v] >= hd) hb[v >> 5] |= 1u << (v & 31);
+        up(d.heavyBits, hb);
     }
-    if (g0.directed) {
-        int32_t *dip, *dic;
-        double *dil, *dir;
-        if ((rc = dev_upload(sh, &dip, perm ? ip : g0.inPtr)) || (rc = dev_upload(sh, &dic, perm ? icol : g0.inCol)) ||
-            (rc = dev_upload(sh, &dil, perm ? ilat : g0.inLat)) || (rc = dev_upload(sh, &dir, perm ? irel : g0.inRel)))
-            return rc;
-        d.inPtr = dip; d.inCol = dic; d.inLat = dil; d.inRel = dir;
+    if (g.directed) {
+        up(d.inPtr, g.inPtr); up(d.inCol, g.inCol); up(d.inLat, g.inLat); up(d.inRel, g.inRel);
     } else {
-        d.inPtr = rowPtr; d.inCol = dcol; d.inLat = dlat; d.inRel = drel;
+        d.inPtr = d.rowPtr; d.inCol = d.col; d.inLat = d.lat; d.inRel = d.rel;
     }
-    d.flat = d.srel = nullptr;
-    if (g0.latFold) {
-        double *dfl, *dsp;
-        if ((rc = dev_upload(sh, &dfl, perm ? flt : g0.foldLat)) ||
-            (rc = dev_upload(sh, &dsp, perm ? srl : g0.selfPathRel)))
-            return rc;
-        d.flat = dfl;
-        d.srel = dsp;
-    }
-    d.oldId = nullptr;
-    if (perm) {
-        int32_t* dold;
-        if ((rc = dev_upload(sh, &dold, *oldOf))) return rc;
-        d.oldId = dold;
-    }
+    if (g.latFold) { up(d.flat, g.foldLat); up(d.srel, g.selfPathRel); }
+    if (oldOf) up(d.oldId, *oldOf);
+    if (rc) return rc;
     *out = d;
     return SHD_PE_OK;
 }
 
-// Device state of one shard: graph upload, stream, events, kernel config.
-static int init_shard(ShdPe* pe, Shard* sh) {
-    const HostGraph& g = pe->hg;
+// The batched path's device ids, built once per create: the caller's graph
+// relabelled by descending degree (stable) -- a wave's groups get vertices of
+// similar degree in the queue and predecessor pass (less divergence), and the
+// hubs' [v][LB] lines sit together -- with the attached list in those ids.
+struct Relabelled {
+    std::vector<int32_t> oldOf, attached;
+    HostGraph g;
+};
+
+// Select the shard's device; it must be a gfx950.
+static int open_device(Shard* sh) {
     if (hipSetDevice(sh->device) != hipSuccess) return SHD_PE_ENODEV;
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, sh->device) != hipSuccess) return SHD_PE_ENODEV;
     if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SHD_PE_ENODEV;
     sh->numCUs = prop.multiProcessorCount;
+    return SHD_PE_OK;
+}
+
+// Device state of one shard: graph upload, stream, events, kernel config.
+// `rl` (null: none) is what the path kernels get instead of the caller's ids.
+static int init_shard(ShdPe* pe, Shard* sh, const Relabelled* rl) {
+    const HostGraph& g = pe->hg;
+    int rc = open_device(sh);
+    if (rc) return rc;
     if (hipStreamCreateWithFlags(&sh->stream, hipStreamNonBlocking) != hipSuccess ||
         hipStreamCreateWithFlags(&sh->copyStream, hipStreamNonBlocking) != hipSuccess ||
         hipEventCreate(&sh->ev0) != hipSuccess || hipEventCreate(&sh->ev1) != hipSuccess ||
@@ -630,46 +456,16 @@ static int init_shard(ShdPe* pe, Shard* sh) {
         hipEventCreate(&sh->evP[0]) != hipSuccess || hipEventCreate(&sh->evP[1]) != hipSuccess ||
         hipEventCreate(&sh->evP[2]) != hipSuccess)
         return SHD_PE_ENODEV;
-    int rc = configure(pe, sh);
-    if (rc) return rc;
-    const int32_t T = (int32_t)pe->attached.size();
-    if ((rc = upload_graph(pe, sh, &sh->dgAux, nullptr))) return rc;
+    if ((rc = configure(pe, sh))) return rc;
+    if ((rc = upload_graph(g, pe->attached, nullptr, sh, &sh->dgAux))) return rc;
     sh->dg = sh->dgAux;
-    if (pe->batched && pe->tu.relabel == 1) {
-        // device ids by descending degree (stable): a wave's groups get
-        // vertices of similar degree in the queue and predecessor pass (less
-        // divergence), and the hubs' [v][LB] lines sit together
-        const int32_t n = g.n;
-        std::vector<int32_t> oldOf(n);
-        for (int32_t v = 0; v < n; ++v) oldOf[v] = v;
-        std::stable_sort(oldOf.begin(), oldOf.end(), [&](int32_t a, int32_t b) {
-            return g.rowPtr[a + 1] - g.rowPtr[a] > g.rowPtr[b + 1] - g.rowPtr[b];
-        });
-        if ((rc = upload_graph(pe, sh, &sh->dg, &oldOf))) return rc;
-        if (pe->devOf.empty()) {
-            pe->devOf.assign(n, 0);
-            for (int32_t k = 0; k < n; ++k) pe->devOf[oldOf[k]] = k;
-        }
-    }
+    if (rl && (rc = upload_graph(rl->g, rl->attached, &rl->oldOf, sh, &sh->dg))) return rc;
     sh->stats.mode = pe->mode;
     sh->stats.isComplete = g.isComplete ? 1 : 0;
     sh->stats.nVertices = g.n;
     sh->stats.nArcs = g.nArcs();
-    sh->stats.nAttached = T;
+    sh->stats.nAttached = (int32_t)pe->attached.size();
     return SHD_PE_OK;
-}
-
-static int select_mode(ShdPe* pe) {
-    const HostGraph& g = pe->hg;
-    int mode = (g.isComplete && pe->opt.forceMode != 1 && pe->opt.forceMode != 3) ? 2 : 1;
-    if (pe->opt.forceMode == 2) mode = 2;
-    // dense non-complete graphs: blocked min-plus (K2)
-    const double density = (double)g.nArcs() / ((double)g.n * (double)g.n);
-    const bool fitsDense = (int64_t)g.n <= 65536;
-    if (mode == 1 && pe->opt.forceMode == 0 && fitsDense && density >= pe->tu.denseMin) mode = 3;
-    if (pe->opt.forceMode == 4 && fitsDense) mode = 3;
-    if (pe->opt.forceMode == 5) mode = 1;
-    return mode;
 }
 
 extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attached,
@@ -705,7 +501,7 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
         devs[i] = o.devices ? o.devices[i] : o.device + i;
         if (devs[i] < 0 || devs[i] >= ndev) return SHD_PE_ENODEV;
     }
-    pe->mode = select_mode(pe.get());
+    pe->mode = select_mode(pe->hg, o.forceMode, pe->tu.denseMin);
     pe->G = o.shardCount * o.nDevices;
     pe->firstShard = o.shardIndex * o.nDevices;
     // the batched-kernel decision (and so the shard unit) needs a configured
@@ -713,17 +509,23 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
     {
         Shard probe;
         probe.device = devs[0];
-        if (hipSetDevice(probe.device) != hipSuccess) return SHD_PE_ENODEV;
-        hipDeviceProp_t prop;
-        if (hipGetDeviceProperties(&prop, probe.device) != hipSuccess) return SHD_PE_ENODEV;
-        if (std::strncmp(prop.gcnArchName, "gfx950", 6) != 0) return SHD_PE_ENODEV;
-        probe.numCUs = prop.multiProcessorCount;
+        if ((rc = open_device(&probe))) return rc;
         probe.rowCount = T;
         if ((rc = configure(pe.get(), &probe))) return rc;
     }
-    plan_shards(pe.get());
+    pe->bounds.assign(pe->G + 1, 0);
+    (void)shd_pe_plan_shards(T, pe->G, pe->batched ? 16 : 1, pe->bounds.data());
     pe->ownStart = pe->bounds[pe->firstShard];
     pe->ownEnd = pe->bounds[pe->firstShard + o.nDevices];
+    Relabelled rl;                       // dropped on return: the shards hold their uploads
+    const bool relabel = pe->batched && pe->tu.relabel == 1;
+    if (relabel) {
+        rl.oldOf = degree_order(g);
+        rl.g = relabel_graph(g, rl.oldOf);
+        pe->devOf.assign(g.n, 0);
+        for (int32_t k = 0; k < g.n; ++k) pe->devOf[rl.oldOf[k]] = k;
+        for (int32_t v : pe->attached) rl.attached.push_back(pe->devOf[v]);
+    }
     for (int i = 0; i < o.nDevices; ++i) {
         std::unique_ptr<Shard> sh(new (std::nothrow) Shard());
         if (!sh) return SHD_PE_ENOMEM;
@@ -732,11 +534,15 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
         sh->rowStart = pe->bounds[sh->gindex];
         sh->rowCount = pe->bounds[sh->gindex + 1] - sh->rowStart;
         sh->fullOwner = std::find(devs.begin(), devs.begin() + i, devs[i]) == devs.begin() + i;
-        rc = init_shard(pe.get(), sh.get());
+        rc = init_shard(pe.get(), sh.get(), relabel ? &rl : nullptr);
         pe->shards.push_back(std::move(sh));
         if (rc) { shd_pe_destroy(pe.release()); return rc; }
     }
-    if (pe->mode == 1 && pe->batched) compute_ranks(pe.get());
+    if (pe->mode == 1 && pe->batched) {
+        BatchRanks br = batch_ranks(g, pe->attached, pe->posOf, pe->tu.batchOrder);
+        pe->rank.swap(br.rank);
+        pe->rowOff.swap(br.rowOff);
+    }
     pe->rowDone.reset(new (std::nothrow) std::atomic<uint8_t>[T]);
     if (!pe->rowDone) { shd_pe_destroy(pe.release()); return SHD_PE_ENOMEM; }
     for (int32_t i = 0; i < T; ++i) pe->rowDone[i].store(0, std::memory_order_relaxed);
@@ -1201,38 +1007,6 @@ static int relax_dense(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, Ex
     return SHD_PE_OK;
 }
 
-// Batches of LB nearby sources (BFS rank order), -1 pads the last.  Host only.
-static std::vector<int32_t> batch_order(const ShdPe* pe, int LB, const int32_t* pos, int32_t cnt,
-                                        int32_t& nB) {
-    std::vector<int32_t> order(pos, pos + cnt);
-    std::stable_sort(order.begin(), order.end(),
-                     [&](int32_t a, int32_t b) { return pe->rank[a] < pe->rank[b]; });
-    nB = (cnt + LB - 1) / LB;
-    order.resize((size_t)nB * LB, -1);
-    if (!pe->rowOff.empty() && nB > 1) {
-        // longest batches first (workgroups take batches in order, so the last round is
-        // made of short ones): a batch's cost grows with its sources' mean distance to
-        // their hub (tools/sim/: correlation 0.53 with arc visits at C4)
-        std::vector<std::pair<double, int32_t>> key(nB);
-        for (int32_t b = 0; b < nB; ++b) {
-            double s = 0.0;
-            int c = 0;
-            for (int l = 0; l < LB; ++l) {
-                const int32_t p = order[(size_t)b * LB + l];
-                if (p >= 0) { s += pe->rowOff[p]; ++c; }
-            }
-            key[b] = {c ? -s / c : 0.0, b};
-        }
-        std::stable_sort(key.begin(), key.end());
-        std::vector<int32_t> re((size_t)nB * LB);
-        for (int32_t i = 0; i < nB; ++i)
-            std::copy(order.begin() + (size_t)key[i].second * LB,
-                      order.begin() + (size_t)(key[i].second + 1) * LB, re.begin() + (size_t)i * LB);
-        order.swap(re);
-    }
-    return order;
-}
-
 // Split kernels: rounds of batches: relax all of them, then the post kernel
 // over the same batches (their dist arrays persist in HBM)
 // (the post kernel may run another variant than the relax).  A timed trial
@@ -1304,7 +1078,8 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     if ((rc = ensure_batch(pe, sh))) return rc;
     const BatchLaunch& relax = relax_launch(sh, trial);
     int32_t nB = 0;
-    const std::vector<int32_t> order = batchOrder ? *batchOrder : batch_order(pe, relax.lb, pos, cnt, nB);
+    const std::vector<int32_t> order =
+        batchOrder ? *batchOrder : batch_order(pe->rank, pe->rowOff, relax.lb, pos, cnt, nB);
     nB = (int32_t)(order.size() / (size_t)relax.lb);
     HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
     if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
@@ -2099,7 +1874,7 @@ static int paths_tier_batch(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w, Exa
     const int32_t LB = trial.relax.lb;
     // the pass's batch order (table positions, -1 pads); the requests by their source's index in it
     int32_t nB = 0;
-    const std::vector<int32_t> order = batch_order(pe, LB, w.uniq.data(), (int32_t)w.uniq.size(), nB);
+    const std::vector<int32_t> order = batch_order(pe->rank, pe->rowOff, LB, w.uniq.data(), (int32_t)w.uniq.size(), nB);
     std::vector<int32_t> ordOf(pe->attached.size());     // by table position
     for (size_t i = 0; i < order.size(); ++i)
         if (order[i] >= 0) ordOf[(size_t)order[i]] = (int32_t)i;

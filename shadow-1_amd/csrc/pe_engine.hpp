@@ -1,6 +1,8 @@
 // pe_engine.hpp -- the engine's host state, shared by pe_engine.hip (create,
-// configure, compute, tune, paths) and pe_rows.hip (row transport).  Private
-// to the library: nothing here is part of the C ABI.
+// configure, compute, tune, paths) and pe_rows.hip (row transport).  What create
+// decides on the host alone -- device ids, batch schedule, mode, shard plan --
+// is pe_plan.hpp, free functions that take no engine state.  Private to the
+// library: nothing here is part of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>

@@ -1,0 +1,213 @@
+// pe_plan.cpp -- create-time planning of the engine (pure C++, no HIP); see
+// pe_plan.hpp.
+#include "pe_plan.hpp"
+
+#include <algorithm>
+#include <climits>
+#include <cmath>
+#include <functional>
+#include <queue>
+#include <utility>
+
+namespace shdpe {
+
+std::vector<int32_t> degree_order(const HostGraph& g) {
+    std::vector<int32_t> oldOf(g.n);
+    for (int32_t v = 0; v < g.n; ++v) oldOf[v] = v;
+    std::stable_sort(oldOf.begin(), oldOf.end(), [&](int32_t a, int32_t b) {
+        return g.rowPtr[a + 1] - g.rowPtr[a] > g.rowPtr[b + 1] - g.rowPtr[b];
+    });
+    return oldOf;
+}
+
+// rows[k] = the row of oldOf[k]: the row pointers, and per old arc its new index
+static std::vector<int32_t> permute_rows(const std::vector<int32_t>& ptr, const std::vector<int32_t>& oldOf,
+                                         std::vector<int32_t>& arcNew) {
+    const int32_t n = (int32_t)oldOf.size();
+    std::vector<int32_t> np(n + 1, 0);
+    arcNew.resize(ptr[n]);
+    for (int32_t k = 0; k < n; ++k) {
+        const int32_t u = oldOf[k];
+        np[k + 1] = np[k] + (ptr[u + 1] - ptr[u]);
+        for (int32_t a = ptr[u], j = np[k]; a < ptr[u + 1]; ++a, ++j) arcNew[a] = j;
+    }
+    return np;
+}
+
+template <class V>
+static void permute(V& dst, const V& src, const std::vector<int32_t>& newIdx) {
+    dst.resize(src.size());
+    for (size_t a = 0; a < src.size(); ++a) dst[newIdx[a]] = src[a];
+}
+
+HostGraph relabel_graph(const HostGraph& g, const std::vector<int32_t>& oldOf) {
+    const int32_t n = g.n;
+    const size_t m = (size_t)g.nArcs();
+    HostGraph r;
+    r.n = n; r.directed = g.directed; r.nEdges = g.nEdges;
+    r.latFold = g.latFold; r.isComplete = g.isComplete;
+    r.meanArcLatency = g.meanArcLatency; r.minArcLatency = g.minArcLatency;
+    std::vector<int32_t> newOf(n);
+    for (int32_t k = 0; k < n; ++k) newOf[oldOf[k]] = k;
+    std::vector<int32_t> arcNew, inNew;
+    r.rowPtr = permute_rows(g.rowPtr, oldOf, arcNew);
+    permute(r.lat, g.lat, arcNew);
+    permute(r.rel, g.rel, arcNew);
+    permute(r.foldLat, g.foldLat, arcNew);           // (empty unless latFold)
+    permute(r.selfPathRel, g.selfPathRel, arcNew);
+    r.col.resize(m);
+    for (size_t a = 0; a < m; ++a) r.col[arcNew[a]] = newOf[g.col[a]];
+    if (g.directed) {
+        r.inPtr = permute_rows(g.inPtr, oldOf, inNew);
+        permute(r.inLat, g.inLat, inNew);
+        permute(r.inRel, g.inRel, inNew);
+        r.inCol.resize(m);
+        for (size_t a = 0; a < m; ++a) r.inCol[inNew[a]] = newOf[g.inCol[a]];
+    }
+    // (undirected: the in-arc of an arc is its reverse arc in the OUT arrays)
+    const std::vector<int32_t>& revNew = g.directed ? inNew : arcNew;
+    r.outToIn.resize(m);
+    for (size_t a = 0; a < m; ++a) r.outToIn[arcNew[a]] = revNew[g.outToIn[a]];
+    permute(r.vrel, g.vrel, newOf);
+    permute(r.selfLat, g.selfLat, newOf);
+    permute(r.selfRel, g.selfRel, newOf);
+    permute(r.selfMinLat, g.selfMinLat, newOf);
+    permute(r.selfMinRel, g.selfMinRel, newOf);
+    permute(r.hasSelf, g.hasSelf, newOf);
+    permute(r.edgeCount, g.edgeCount, newOf);        // (empty unless a multigraph)
+    return r;
+}
+
+BatchRanks batch_ranks(const HostGraph& g, const std::vector<int32_t>& attached,
+                       const std::vector<int32_t>& posOf, int batchOrder) {
+    BatchRanks out;
+    std::vector<int32_t> order;
+    order.reserve(g.n);
+    if (batchOrder == 1) {
+        const int32_t K = (int32_t)std::max<int64_t>(1, std::min<int64_t>(256, g.n / 400));
+        const std::vector<int32_t> byDeg = degree_order(g);
+        std::vector<double> dist(g.n, INFINITY);
+        std::vector<int32_t> owner(g.n, INT32_MAX);
+        typedef std::pair<double, int32_t> QE;
+        std::priority_queue<QE, std::vector<QE>, std::greater<QE>> q;
+        for (int32_t k = 0; k < K; ++k) { dist[byDeg[k]] = 0.0; owner[byDeg[k]] = k; q.push({0.0, byDeg[k]}); }
+        while (!q.empty()) {
+            const QE top = q.top();
+            q.pop();
+            const int32_t u = top.second;
+            if (top.first > dist[u]) continue;
+            for (int32_t a = g.rowPtr[u]; a < g.rowPtr[u + 1]; ++a) {
+                const int32_t v = g.col[a];
+                const double nd = dist[u] + g.lat[a];
+                if (nd < dist[v] || (nd == dist[v] && owner[u] < owner[v])) {
+                    dist[v] = nd;
+                    owner[v] = owner[u];
+                    q.push({nd, v});
+                }
+            }
+        }
+        for (int32_t v = 0; v < g.n; ++v) order.push_back(v);
+        std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
+            return owner[a] != owner[b] ? owner[a] < owner[b] : dist[a] < dist[b];
+        });
+        // bucket key offsets: a source's distance to its hub, so the lanes of
+        // a batch reach the vertices behind the hub in the same bucket
+        out.rowOff.assign(attached.size(), 0.0);
+        for (size_t p = 0; p < attached.size(); ++p) {
+            const double d = dist[attached[p]];
+            out.rowOff[p] = std::isfinite(d) ? d : 0.0;
+        }
+    } else {
+        std::vector<uint8_t> seen(g.n, 0);
+        for (int32_t r = 0; r < g.n; ++r) {
+            if (seen[r]) continue;
+            seen[r] = 1;
+            size_t head = order.size();
+            order.push_back(r);
+            while (head < order.size()) {
+                const int32_t u = order[head++];
+                for (int32_t a = g.rowPtr[u]; a < g.rowPtr[u + 1]; ++a) {
+                    const int32_t v = g.col[a];
+                    if (!seen[v]) { seen[v] = 1; order.push_back(v); }
+                }
+                if (g.directed) {
+                    for (int32_t a = g.inPtr[u]; a < g.inPtr[u + 1]; ++a) {
+                        const int32_t v = g.inCol[a];
+                        if (!seen[v]) { seen[v] = 1; order.push_back(v); }
+                    }
+                }
+            }
+        }
+    }
+    out.rank.assign(attached.size(), 0);
+    int32_t k = 0;
+    for (int32_t v : order)
+        if (posOf[v] >= 0) out.rank[posOf[v]] = k++;
+    return out;
+}
+
+std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
+                                 int LB, const int32_t* pos, int32_t cnt, int32_t& nB) {
+    // pos[] stably sorted by rank: (rank, index in pos[]) packed into one
+    // integer key, so the sort compares no more than the keys themselves
+    std::vector<uint64_t> key(cnt);
+    for (int32_t i = 0; i < cnt; ++i)
+        key[i] = (uint64_t)((uint32_t)rank[pos[i]] ^ 0x80000000u) << 32 | (uint32_t)i;
+    std::sort(key.begin(), key.end());
+    std::vector<int32_t> order(cnt);
+    for (int32_t i = 0; i < cnt; ++i) order[i] = pos[(uint32_t)key[i]];
+    nB = (cnt + LB - 1) / LB;
+    order.resize((size_t)nB * LB, -1);
+    if (!rowOff.empty() && nB > 1) {
+        // longest batches first (workgroups take batches in order, so the last round is
+        // made of short ones): a batch's cost grows with its sources' mean distance to
+        // their hub (tools/sim/: correlation 0.53 with arc visits at C4)
+        std::vector<std::pair<double, int32_t>> key(nB);
+        for (int32_t b = 0; b < nB; ++b) {
+            double s = 0.0;
+            int c = 0;
+            for (int l = 0; l < LB; ++l) {
+                const int32_t p = order[(size_t)b * LB + l];
+                if (p >= 0) { s += rowOff[p]; ++c; }
+            }
+            key[b] = {c ? -s / c : 0.0, b};
+        }
+        std::stable_sort(key.begin(), key.end());
+        std::vector<int32_t> re((size_t)nB * LB);
+        for (int32_t i = 0; i < nB; ++i)
+            std::copy(order.begin() + (size_t)key[i].second * LB,
+                      order.begin() + (size_t)(key[i].second + 1) * LB, re.begin() + (size_t)i * LB);
+        order.swap(re);
+    }
+    return order;
+}
+
+int select_mode(const HostGraph& g, int forceMode, double denseMin) {
+    int mode = (g.isComplete && forceMode != 1 && forceMode != 3) ? 2 : 1;
+    if (forceMode == 2) mode = 2;
+    // dense non-complete graphs: blocked min-plus (K2)
+    const double density = (double)g.nArcs() / ((double)g.n * (double)g.n);
+    const bool fitsDense = (int64_t)g.n <= 65536;
+    if (mode == 1 && forceMode == 0 && fitsDense && density >= denseMin) mode = 3;
+    if (forceMode == 4 && fitsDense) mode = 3;
+    if (forceMode == 5) mode = 1;
+    return mode;
+}
+
+}  // namespace shdpe
+
+// Row-shard plan: G contiguous position ranges with equal numbers of kernel
+// work units (a unit = one batch of 16 rows in the batched sparse kernel,
+// one row otherwise).  Per-unit cost is near-uniform for this path: every
+// SSSP row settles all n vertices, every dense / direct row is n (T) wide
+// (measured per-batch cycle spread in DESIGN.md §6), so equal units are the
+// balanced split, and contiguous ranges let the all-gather land rows in
+// place.  Host-only (no device), exported for the CPU tests.
+extern "C" int shd_pe_plan_shards(int32_t T, int32_t G, int32_t unit, int32_t* bounds) {
+    if (T < 0 || G < 1 || unit < 1 || !bounds) return SHD_PE_EINVAL;
+    const int64_t units = ((int64_t)T + unit - 1) / unit;
+    for (int g = 0; g < G; ++g)
+        bounds[g] = (int32_t)std::min<int64_t>(T, (units * g / G) * unit);
+    bounds[G] = T;
+    return SHD_PE_OK;
+}

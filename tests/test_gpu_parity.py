@@ -619,6 +619,48 @@ def test_batched_tie_rows_partial_targets(E, oracle_mod):
     assert st["mode"] == 1 and st["rowsTieEarly"] > 0
 
 
+def _plan_case(name):
+    if name == "quantized":
+        return G.random_sparse(600, 6, seed=301, quantum=1.0)
+    if name == "directed":
+        return G.random_sparse(400, 4, seed=302, directed=True)
+    return G.with_slower_newest_edges(G.random_sparse(400, 6, seed=303, quantum=5.0), 0.4, seed=304)
+
+
+@pytest.mark.parametrize("order", [0, 1])
+@pytest.mark.parametrize("relabel", [0, 1])
+@pytest.mark.parametrize("case", ["quantized", "directed", "latfold"])
+def test_batched_relabel_and_batch_order(E, oracle_mod, monkeypatch, case, relabel, order):
+    """Create-time planning (pe_plan.cpp) on the batched path: device ids by
+    degree or as given (SHDPE_RELABEL) x hub-cell or BFS batch order
+    (SHDPE_BATCH_ORDER).  Neither may change a bit of a row: tie rows
+    (quantized), the relabelled in-arcs and outToIn (directed) and the
+    relabelled foldLat / selfPathRel (latfold) against the oracle.  One
+    relabelled case also takes paths: they come back in the caller's ids."""
+    monkeypatch.setenv("SHDPE_RELABEL", str(relabel))
+    monkeypatch.setenv("SHDPE_BATCH_ORDER", str(order))
+    top = _plan_case(case)
+    att = np.arange(top.n, dtype=np.int32)
+    st = _check_engine(E, oracle_mod, top, att, force=5, debug_flags=E.DEBUG_ENV)
+    assert st["mode"] == 1 and st["batched"] == 1
+    if case == "quantized":
+        assert st["rowsExact"] > 0
+    if case == "directed" and relabel == 1 and order == 1:
+        eng = E.Engine(top, att, force_mode=5, debug_flags=E.DEBUG_ENV)
+        rng = np.random.default_rng(5)
+        src = rng.integers(0, top.n, 50)
+        dst = (src + rng.integers(1, top.n, 50)) % top.n      # never the source
+        offsets, verts, status = eng.get_paths(src, dst)
+        assert np.all(status == 0)                # (strongly connected, every vertex attached)
+        arcs = set(zip(top.src.tolist(), top.dst.tolist()))
+        for i in range(50):
+            path = verts[offsets[i]:offsets[i + 1]].tolist()
+            assert path[0] == src[i] and path[-1] == dst[i]
+            assert all(a in arcs for a in zip(path[:-1], path[1:])), (i, path)
+            assert path == eng.get_path(int(src[i]), int(dst[i]))
+        eng.close()
+
+
 def test_topology_shim_concurrent_readers(E, oracle_mod):
     """8 host threads query the topology mirror at once (the reference's
     worker threads): cache hits take no lock, misses serialise.  Every value

@@ -355,3 +355,70 @@ def test_table_field_walk_under_sanitizers(tmp_path):
     env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1 exitcode=66", UBSAN_OPTIONS="halt_on_error=1 exitcode=66")
     r = subprocess.run([exe], capture_output=True, text=True, timeout=120, env=env)
     assert r.returncode == 0 and "OK" in r.stdout and not r.stderr.strip(), (r.stdout, r.stderr[-3000:])
+
+
+def _plan_graphs():
+    """(name, topology, attached) of tests/native/plan.cpp's cases.  The first
+    is the graph of tests/golden/host_plan_ba1200.txt: 1,200 vertices, so
+    n / 400 = 3 hub cells, the smallest size with more than one.  No attached
+    count is a multiple of 8."""
+    return [
+        ("ba1200", G.power_law(1200, m=3, seed=4), G.sample_attached(1200, 300, seed=2)),
+        ("directed", G.random_sparse(400, 4, seed=7, directed=True), G.sample_attached(400, 150, seed=1)),
+        ("latfold", G.with_slower_newest_edges(G.random_sparse(400, 6, seed=31, quantum=5.0), 0.4, seed=32),
+         G.sample_attached(400, 150, seed=3)),
+        ("vloss_loops", G.with_parallel_loops(G.random_sparse(400, 5, seed=8, vloss=True), 0.3, seed=9),
+         G.sample_attached(400, 150, seed=5)),
+    ]
+
+
+def _write_plan_graph(d, top, att):
+    os.makedirs(d)
+    with open(os.path.join(d, "meta.txt"), "w") as f:
+        f.write(f"{top.n} {int(top.directed)} {int(top.vloss is not None)}\n")
+    top.src.astype(np.int32).tofile(os.path.join(d, "from.i32"))
+    top.dst.astype(np.int32).tofile(os.path.join(d, "to.i32"))
+    top.latency.astype(np.float64).tofile(os.path.join(d, "lat.f64"))
+    top.loss.astype(np.float64).tofile(os.path.join(d, "loss.f64"))
+    if top.vloss is not None:
+        top.vloss.astype(np.float64).tofile(os.path.join(d, "vloss.f64"))
+    np.asarray(att, np.int32).tofile(os.path.join(d, "att.i32"))
+
+
+def test_create_planning_under_sanitizers(tmp_path):
+    """pe_plan.cpp -- the degree relabelling, batch ranks and offsets, batch
+    order, mode selection and shard plan that shd_pe_create runs before any
+    upload -- over HostGraphs built by pe_graph.cpp from raw arrays, with
+    -fsanitize=address,undefined (the checks are in tests/native/plan.cpp).
+    The 1,200-vertex graph's degree order, ranks, offsets and batch orders
+    must equal tests/golden/host_plan_ba1200.txt byte for byte: that file was
+    written by `plan --fixture` when these functions were still the bodies
+    moved verbatim out of pe_engine.hip."""
+    import shutil
+    gxx = shutil.which("g++")
+    if gxx is None:
+        pytest.skip("no g++")
+    csrc = os.path.join(ROOT, "shadow-1_amd", "csrc")
+    exe = str(tmp_path / "plan")
+    cmd = [gxx, "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all", "-pthread",
+           "-I", csrc, "-I", os.path.join(ROOT, "include"),
+           os.path.join(ROOT, "tests", "native", "plan.cpp"), os.path.join(csrc, "pe_plan.cpp"),
+           os.path.join(csrc, "pe_graph.cpp"), "-o", exe]
+    b = subprocess.run(cmd, capture_output=True, text=True)
+    if b.returncode != 0 and "asan" in (b.stderr or "").lower():
+        pytest.skip("AddressSanitizer runtime unavailable")
+    assert b.returncode == 0, b.stderr[-2000:]
+    dirs = []
+    for name, top, att in _plan_graphs():
+        assert len(att) % 8 != 0
+        dirs.append(str(tmp_path / name))
+        _write_plan_graph(dirs[-1], top, att)
+    env = dict(os.environ, ASAN_OPTIONS="halt_on_error=1 exitcode=66", UBSAN_OPTIONS="halt_on_error=1 exitcode=66")
+    r = subprocess.run([exe] + dirs, capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and "OK" in r.stdout and not r.stderr.strip(), (r.stdout, r.stderr[-3000:])
+    assert " latFold 1 " in r.stdout and " directed 1 " in r.stdout
+    out = str(tmp_path / "fixture.txt")
+    r = subprocess.run([exe, "--fixture", out, dirs[0]], capture_output=True, text=True, timeout=120, env=env)
+    assert r.returncode == 0 and not r.stderr.strip(), (r.stdout, r.stderr[-3000:])
+    with open(out, "rb") as f, open(os.path.join(GOLDEN, "host_plan_ba1200.txt"), "rb") as g:
+        assert f.read() == g.read()
