@@ -140,11 +140,15 @@ __global__ __launch_bounds__(256) void k_minplus(DevGraph g, const double* W, do
     const int aK = tid & 15, aR = tid >> 4;          // A: row aR + 16 q, column k0 + aK
     const int bK = tid >> 7, bC = tid & 127;         // B: row k0 + bK + 2 q, column v0 + bC
     const bool bColOk = v0 + bC < n;
-    const double* pA = Dg + (int64_t)(r0 + aR) * ldD + aK;
-    const double* pB = Wg + (int64_t)bK * n + v0 + bC;
     int rmask = 0;
 #pragma unroll
     for (int q = 0; q < MI; ++q) rmask |= (r0 + aR + 16 * q < nRows) << q;
+    // A masked load reads element 0 of its base, so a thread whose own first
+    // element lies outside D (rows past nRows in the last row tile, aK >= n)
+    // or outside W (columns past n in the last strip, bK >= n) is based on
+    // the array's start; every load of such a thread is masked.
+    const double* pA = Dg + ((rmask & 1) && aK < n ? (int64_t)(r0 + aR) * ldD + aK : 0);
+    const double* pB = Wg + (bColOk && bK < n ? (int64_t)bK * n + v0 + bC : 0);
     double ra[MI], rb[KB / 2];
     auto fetch = [&](int64_t k0) {
         const bool uok = k0 + aK < n;
