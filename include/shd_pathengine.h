@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 6   /* 6: batched path extraction (shd_pe_get_paths) */
+#define SHD_PE_ABI_VERSION 7   /* 7: graph property check (shd_pe_graph_props) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -681,6 +681,58 @@ int shd_pe_attach_timing(const ShdPeAttach* at, double* ms);
  * vertices, no GPU (the late single attach, topology.c:2371-2430). */
 int shd_pe_attach_host(const ShdPeVertexAttrs* va, const ShdPeAttachHints* h, int64_t i,
                        const ShdPeAttachResult* r);
+
+/* ------------------------------------------------------------------------
+ * Graph property check (_topology_checkGraphProperties, topology.c:724-809):
+ * igraph_is_connected(IGRAPH_STRONG) (:738), igraph_clusters(IGRAPH_STRONG)
+ * (:745) and _topology_isComplete (:754, body :450-552) in one call, before
+ * any host attaches and before shd_pe_create: no handle, the call owns its
+ * memory.  The reference refuses a graph unless isConnected && clusterCount
+ * == 1 (:800-806); that decision stays with the caller.
+ *
+ * Only nVertices, nEdges, directed, edgeFrom and edgeTo are read; the latency
+ * and loss pointers may be NULL (edge values are _topology_checkGraphEdges'
+ * job, which shd_pe_create does).
+ *
+ * Clusters as in igraph 0.7.1: strongly connected components of a directed
+ * graph, weak components of an undirected one (igraph ignores the mode there);
+ * self-loops and parallel edges are accepted and change nothing; isConnected
+ * == (clusterCount == 1) for every n >= 1.  membership (optional, nVertices
+ * entries): membership[v] = the smallest vertex id in v's cluster, whatever
+ * the schedule.  Completeness: per vertex the OUT-incident edge count,
+ * parallel edges each (directed: edges with from == v, a self-loop once;
+ * undirected: both endpoints, a self-loop twice, minus one iff v has at least
+ * one self-loop); complete iff every count >= nVertices.  isComplete equals
+ * shd_pe_is_complete of an engine created from the same description.
+ *
+ * nVertices <= 0, a NULL out or an endpoint outside [0, nVertices):
+ * SHD_PE_EINVAL; 2 * nEdges > INT32_MAX: SHD_PE_ETOOBIG (int32 counts). */
+typedef struct ShdPeGraphProps {
+    int32_t isDirected;      /* g->directed != 0 */
+    int32_t isConnected;     /* igraph_is_connected(IGRAPH_STRONG), topology.c:738 */
+    int32_t clusterCount;    /* igraph_clusters(IGRAPH_STRONG) count, :745 */
+    int32_t largestCluster;  /* vertices in the largest cluster (no reference counterpart) */
+    int32_t isComplete;      /* _topology_isComplete, :450-552 */
+    int32_t firstIncomplete; /* the vertex :523-526 reports: lowest v with count < n; -1 if complete */
+} ShdPeGraphProps;
+typedef struct ShdPeGraphPropsInfo {   /* optional, device call only */
+    int64_t sweeps;          /* edge sweeps launched (the counting sweep included) */
+    int64_t rounds;          /* decomposition rounds (trim / pivot / colouring; undirected: hook + jump) */
+    int32_t handedOff;       /* 1: sweep budget exhausted, answer computed by the host form */
+    int64_t usDevice, usCall;/* device events (up to the hand-off, if any); wall time incl. upload */
+} ShdPeGraphPropsInfo;
+/* On the CPU, one thread: a counting pass, union-find (undirected) or an
+ * iterative Tarjan over its own CSR (directed; no recursion). */
+int shd_pe_graph_props_host(const ShdPeGraphDesc* g, ShdPeGraphProps* out, int32_t* membership);
+/* On gfx950 device `device`: the edge list is uploaded as given (pageable
+ * arrays in chunks through page-locked staging) and every kernel is edge- or
+ * vertex-parallel; no CSR is built on either side.  sweepBudget <= 0 selects
+ * the default; when the edge sweeps of a call reach the budget the whole
+ * answer comes from shd_pe_graph_props_host and info->handedOff is 1 (same
+ * result by construction).  No gfx950 device: SHD_PE_ENODEV, never a silent
+ * host run. */
+int shd_pe_graph_props(const ShdPeGraphDesc* g, int32_t device, int32_t sweepBudget,
+                       ShdPeGraphProps* out, int32_t* membership, ShdPeGraphPropsInfo* info);
 
 #ifdef __cplusplus
 }

@@ -49,6 +49,7 @@ EXPORTS = [
     "shd_pe_attach_new", "shd_pe_attach_free", "shd_pe_attach_hosts", "shd_pe_attach_host",
     "shd_pe_attach_set_chunk", "shd_pe_attach_timing",
     "shd_pe_get_paths", "shd_pe_paths_info",
+    "shd_pe_graph_props", "shd_pe_graph_props_host",
 ]
 VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
 VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
@@ -107,6 +108,18 @@ class PathsOutC(C.Structure):
     """ShdPePathsOut"""
     _fields_ = [("offsets", C.c_void_p), ("verts", C.c_void_p), ("hopLat", C.c_void_p),
                 ("hopRel", C.c_void_p), ("status", C.c_void_p), ("cap", C.c_int64)]
+
+
+class GraphPropsC(C.Structure):
+    """ShdPeGraphProps"""
+    _fields_ = [("isDirected", C.c_int32), ("isConnected", C.c_int32), ("clusterCount", C.c_int32),
+                ("largestCluster", C.c_int32), ("isComplete", C.c_int32), ("firstIncomplete", C.c_int32)]
+
+
+class GraphPropsInfoC(C.Structure):
+    """ShdPeGraphPropsInfo"""
+    _fields_ = [("sweeps", C.c_int64), ("rounds", C.c_int64), ("handedOff", C.c_int32),
+                ("usDevice", C.c_int64), ("usCall", C.c_int64)]
 
 
 class EngineError(RuntimeError):
@@ -211,15 +224,18 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_attach_timing": (C.c_int, [vp, vp]),
         "shd_pe_get_paths": (C.c_int, [vp, vp, vp, i64, vp]),
         "shd_pe_paths_info": (C.c_int, [vp, vp, i32]),
+        "shd_pe_graph_props": (C.c_int, [vp, i32, i32, vp, vp, vp]),
+        "shd_pe_graph_props_host": (C.c_int, [vp, vp, vp]),
     }
-    # ABI-3 ... ABI-6 additions: an older build loaded through SHDPE_LIB (same-box
+    # ABI-3 ... ABI-7 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
     optional = {"shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_fill_rowstore_ex",
                 "shd_topology_fill", "shd_graphml_vertex_attrs", "shd_graphml_attr_code",
                 "shd_graphml_vertex_attr_string", "shd_pe_attach_new", "shd_pe_attach_free",
                 "shd_pe_attach_hosts", "shd_pe_attach_host", "shd_pe_attach_set_chunk",
                 "shd_pe_attach_timing", "shd_pe_get_paths",
-                "shd_pe_paths_info"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_pe_paths_info", "shd_pe_graph_props",
+                "shd_pe_graph_props_host"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -828,6 +844,42 @@ def parse_graphml(data, name: str = "topology", with_ids: bool = True):
                         vloss=vloss, ids=ids, prefers_direct=bool(pdp.value), name=name)
     finally:
         lib.shd_graphml_free(h)
+
+
+# ---- graph property check (_topology_checkGraphProperties, topology.c:724-809)
+def graph_props(top, device=None, sweep_budget: int = 0, membership: bool = False) -> dict:
+    """shd_pe_graph_props_host (device=None) / shd_pe_graph_props (a gfx950
+    ordinal; raises ENODEV without one, no fallback): connectivity, cluster
+    count, largest cluster and completeness of `top` (anything with n,
+    directed, src, dst; latencies are not read).  Returns the ShdPeGraphProps
+    fields as a dict, plus "membership" (int32[n]: the smallest vertex id of
+    each vertex's cluster) when asked for and, on the device, "info"
+    (ShdPeGraphPropsInfo: sweeps, rounds, handedOff, usDevice, usCall)."""
+    lib = load_library()
+    src = np.ascontiguousarray(top.src, dtype=np.int32)
+    dst = np.ascontiguousarray(top.dst, dtype=np.int32)
+    if src.ndim != 1 or src.shape != dst.shape:
+        raise ValueError("src/dst must be 1-D arrays of one length")
+    n = int(top.n)
+    d = GraphDesc(n, src.shape[0], int(bool(top.directed)), _p(src), _p(dst), None, None, None)
+    out = GraphPropsC()
+    mem = np.empty(max(n, 0), np.int32) if membership else None
+    if device is None:
+        rc = lib.shd_pe_graph_props_host(C.byref(d), C.byref(out), _p(mem))
+        what, info = "shd_pe_graph_props_host", None
+    else:
+        info = GraphPropsInfoC()
+        rc = lib.shd_pe_graph_props(C.byref(d), int(device), int(sweep_budget), C.byref(out), _p(mem),
+                                    C.byref(info))
+        what = "shd_pe_graph_props"
+    if rc:
+        raise EngineError(rc, what)
+    res = {f: int(getattr(out, f)) for f, _ in GraphPropsC._fields_}
+    if membership:
+        res["membership"] = mem
+    if info is not None:
+        res["info"] = {f: int(getattr(info, f)) for f, _ in GraphPropsInfoC._fields_}
+    return res
 
 
 # ---- host attachment (topology_attach, topology.c:2094-2430) ----------------
