@@ -36,7 +36,8 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 7   /* 7: graph property check (shd_pe_graph_props) */
+#define SHD_PE_ABI_VERSION 8   /* 7: graph property check (shd_pe_graph_props);
+                                  8: fill from row shards (shd_pe_fill_rowstore_shards) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -394,6 +395,40 @@ int shd_pe_fill_rowstore_ex(ShdPe* pe, struct ShdRowStore* st, int32_t fillFlags
                             int32_t* rowResult, double* msOut);
 int shd_pe_fill_rowstore(ShdPe* pe, struct ShdRowStore* st, int32_t* rowResult, double* msOut);
 
+/* The same fill from row shards, without a gather (ABI 8).  On an in-process
+ * sharded engine (nDevices > 1, repeated ordinals included) every shard packs
+ * the image rows of its own table rows on its own device and DMAs that
+ * segment to its place in the one host image (distinct devices: concurrently;
+ * the image is registered portable).  A slot (a, b > a) whose forward entry
+ * is not used wants entry (b, a); where row b is another shard's the slot is
+ * a NEED: it is sent to the owner of row b and answered (the fold's success,
+ * lat, rel) through pinned host staging, in rounds whose lists stay within
+ * needBudgetBytes (<= 0: 64 MiB; 25 B per need; a single image row past the
+ * budget gets a round to itself), and the answers are written into the
+ * landed image before the store adopts it.  No peer access, no full table on
+ * any device, and the engine's gathered state is never set.
+ * The store ends byte for byte as shd_pe_fill_rowstore_ex leaves it on the
+ * same engine after shd_pe_gather; fillFlags, rowResult and the refusals
+ * (SHD_PE_EINVAL for a non-empty store or unknown bits, SHD_PE_ETOOBIG for
+ * the prefer-direct LDS limit) are those of _ex.  With one shard, or once the
+ * engine is gathered, the call IS _ex (fromFullTable = 1).  An engine that is
+ * one of several processes' (shardCount > 1) and not gathered answers
+ * SHD_PE_ENOTOWNED: the other rows' store is another process's.
+ * The distinct-device path (concurrent PCIe transfers, portable registration)
+ * has run on logical shards of one device only: it is unmeasured. */
+typedef struct ShdPeFillShardsInfo {
+    int32_t shards;          /* table views packed: local shards with rows, or 1 when one full table served the call */
+    int32_t fromFullTable;   /* 1: G == 1 or the engine was gathered (the _ex path ran) */
+    int64_t needs;           /* slots whose reverse entry lives in another shard's rows */
+    int64_t needsStored;     /* of those, answered with a usable reverse entry */
+    int64_t needRounds;      /* need-list rounds (0 when needs == 0) */
+    int64_t deviceBytesPeak; /* largest per-shard sum of this call's device temporaries */
+    double  msCompute, msPack, msResolve, msDma;   /* wall ms, as msOut of _ex, plus the resolve */
+} ShdPeFillShardsInfo;
+int shd_pe_fill_rowstore_shards(ShdPe* pe, struct ShdRowStore* st, int32_t fillFlags,
+                                int64_t needBudgetBytes, int32_t* rowResult,
+                                ShdPeFillShardsInfo* info);      /* info optional */
+
 /* Wait for outstanding device work of this engine. */
 int shd_pe_synchronize(ShdPe* pe);
 
@@ -557,6 +592,9 @@ int64_t shd_topology_rows_computed(const ShdTopology* top);
  * a pair stored under its reverse key still takes the miss path once, which
  * re-probes that key.  msOut (optional, 3 entries) as shd_pe_fill_rowstore. */
 int shd_topology_fill(ShdTopology* top, double* msOut);
+/* The same through shd_pe_fill_rowstore_shards: a sharded in-process engine
+ * needs no gather first.  info (optional) as there. */
+int shd_topology_fill_shards(ShdTopology* top, int64_t needBudgetBytes, ShdPeFillShardsInfo* info);
 
 /* ------------------------------------------------------------------------
  * GraphML ingestion (host only, no GPU work).  Replaces

@@ -278,6 +278,23 @@ namespace shdpe {
 //                  through posOf[]: one row's arcs are read once, instead of
 //                  T binary searches per row.  Only slots of a direct branch
 //                  look the arc up (direct_values, k_pairs' arithmetic).
+//
+// The kernel packs a VIEW of the table (PackView): triangular rows [lo, hi),
+// read from a table that holds them at local row a - tab.rowStart, into an
+// image segment that starts at off[lo].  The whole table is the view [0, T).
+// A row shard (shd_pe_fill_rowstore_shards) is a view whose reverse entry
+// (b, a) with b >= hi lies in another shard's rows: wherever the rule above
+// would look at it, the slot is a NEED.  It gets what the rule's remaining
+// (direct) branches give, plus PACK_S_PENDING in its state byte, stays out of
+// the count / minimum accumulators, and is counted in needCount[a - lo] (one
+// plain store per workgroup).  The host resolves needs with the two kernels
+// below and pe_fill.cpp; no PENDING bit reaches a row store.
+//   k_pack_needs   one workgroup per row with needs: its PENDING slots as
+//                  (a, b) pairs at the row's prefix offset, in slot order
+//                  (wave64 ballot + popcount: no atomics, no scheduling in
+//                  the list's content)
+//   k_pack_answer  on the owner of row b, one thread per need: ok = the fold
+//                  (b, a) succeeded, with its lat / rel
 // ---------------------------------------------------------------------------
 constexpr int PACK_PLAIN = 0, PACK_COMPLETE = 1, PACK_ADJ = 2;
 
@@ -292,19 +309,23 @@ struct PackAdj {
 
 template <int MODE>
 __global__ __launch_bounds__(256) void k_pack_rowstore(
-    DevTable tab0, const int64_t* __restrict__ off, uint8_t* __restrict__ img,
-    unsigned long long* __restrict__ acc, std::conditional_t<MODE == PACK_ADJ, PackAdj, PackNone> pa) {
+    DevTable tab0, PackView pv, const int64_t* __restrict__ off, uint8_t* __restrict__ img,
+    unsigned long long* __restrict__ acc, int32_t* __restrict__ needCount,
+    std::conditional_t<MODE == PACK_ADJ, PackAdj, PackNone> pa) {
     const DevTable tab = global_view(tab0);
     __shared__ unsigned long long cnt[4], mnb[4];
+    __shared__ int ndc[4];
     const int64_t T = tab.T;
-    const int64_t a = blockIdx.x, len = T - a;
-    uint8_t* base = img + off[a] + SHD_ROWSTORE_IMAGE_HEADER;
+    const int64_t a = pv.lo + blockIdx.x, len = T - a, hi = pv.hi;
+    const size_t rowA = (size_t)(a - tab.rowStart) * (size_t)T;   // row a in the view's table
+    uint8_t* base = img + (off[a] - off[pv.lo]) + SHD_ROWSTORE_IMAGE_HEADER;
     double* L = reinterpret_cast<double*>(base);
     double* R = L + len;
     uint8_t* S = reinterpret_cast<uint8_t*>(R + len);
     constexpr uint8_t FAILED = F_UNREACHABLE | F_NOEDGE;
     constexpr uint8_t DIRECT = MODE == PACK_COMPLETE ? SHD_ROWSTORE_S_DIRECT : 0;
     unsigned long long c = 0, mn = INF_BITS;
+    int nd = 0;                                   // this thread's needs
     if constexpr (MODE == PACK_ADJ) {
         extern __shared__ uint32_t adjBits[];
         const DevGraph g = global_view(pa.g);
@@ -332,34 +353,41 @@ __global__ __launch_bounds__(256) void k_pack_rowstore(
         const bool nonDirect = !pa.complete, wantDirect = pa.direct != 0;
         for (int64_t k = threadIdx.x; k < len; k += 256) {
             const int64_t b = a + k;
-            const size_t fo = (size_t)a * T + b;
+            const size_t fo = rowA + b;
+            const size_t ro = (size_t)(b - tab.rowStart) * T + a;  // (read only where b < hi)
             const bool adjF = (Aout[b >> 5] >> (b & 31)) & 1u;     // u -> v
             const bool adjR = (Ain[b >> 5] >> (b & 31)) & 1u;      // v -> u
             double lat = 0.0, rel = 0.0;
             uint8_t s = 0;
+            const bool wantRev = nonDirect && k > 0 && !adjR;     // the rule may look at entry (b, a)
+            bool need = false;
             if (nonDirect && !adjF && !(tab.flags[fo] & FAILED)) {
                 lat = tab.lat[fo];
                 rel = tab.rel[fo];
                 s = SHD_ROWSTORE_S_STORED;
-            } else if (nonDirect && k > 0 && !adjR && !(tab.flags[(size_t)b * T + a] & FAILED)) {
-                const size_t ro = (size_t)b * T + a;
+            } else if (wantRev && b < hi && !(tab.flags[ro] & FAILED)) {
                 lat = tab.lat[ro];
                 rel = tab.rel[ro];
                 s = SHD_ROWSTORE_S_STORED | SHD_ROWSTORE_S_REVERSED;
-            } else if (wantDirect && (adjF || (k > 0 && adjR))) {
-                const int v = g.attached[b];
-                const int from = adjF ? u : v, to = adjF ? v : u;
-                int arc = -1;
-                if (find_arc(g, from, to, &arc)) {     // (always: the bitmaps came from these arcs)
-                    direct_values(g, from, to, arc, &lat, &rel);
-                    s = SHD_ROWSTORE_S_STORED | SHD_ROWSTORE_S_DIRECT |
-                        (adjF ? 0 : SHD_ROWSTORE_S_REVERSED);
+            } else {
+                need = wantRev && b >= hi;             // row b is behind the view: the direct entry meanwhile
+                if (wantDirect && (adjF || (k > 0 && adjR))) {
+                    const int v = g.attached[b];
+                    const int from = adjF ? u : v, to = adjF ? v : u;
+                    int arc = -1;
+                    if (find_arc(g, from, to, &arc)) {     // (always: the bitmaps came from these arcs)
+                        direct_values(g, from, to, arc, &lat, &rel);
+                        s = SHD_ROWSTORE_S_STORED | SHD_ROWSTORE_S_DIRECT |
+                            (adjF ? 0 : SHD_ROWSTORE_S_REVERSED);
+                    }
                 }
             }
             L[k] = lat;
             R[k] = rel;
-            S[k] = s;
-            if (s) {
+            S[k] = need ? (uint8_t)(s | PACK_S_PENDING) : s;
+            if (need) {
+                ++nd;
+            } else if (s) {
                 ++c;
                 const unsigned long long lb = (unsigned long long)__double_as_longlong(lat);
                 mn = lb < mn ? lb : mn;
@@ -368,7 +396,7 @@ __global__ __launch_bounds__(256) void k_pack_rowstore(
     } else {
         for (int64_t k = threadIdx.x; k < len; k += 256) {
             const int64_t b = a + k;
-            const size_t fo = (size_t)a * T + b;
+            const size_t fo = rowA + b;
             double lat = 0.0, rel = 0.0;
             uint8_t s = 0;
             if (!(tab.flags[fo] & FAILED)) {
@@ -376,17 +404,22 @@ __global__ __launch_bounds__(256) void k_pack_rowstore(
                 rel = tab.rel[fo];
                 s = SHD_ROWSTORE_S_STORED | DIRECT;
             } else if (k > 0) {
-                const size_t ro = (size_t)b * T + a;
-                if (!(tab.flags[ro] & FAILED)) {
-                    lat = tab.lat[ro];
-                    rel = tab.rel[ro];
-                    s = SHD_ROWSTORE_S_STORED | SHD_ROWSTORE_S_REVERSED | DIRECT;
+                if (b >= hi) {                   // a need: empty until answered
+                    s = PACK_S_PENDING;
+                    ++nd;
+                } else {
+                    const size_t ro = (size_t)(b - tab.rowStart) * T + a;
+                    if (!(tab.flags[ro] & FAILED)) {
+                        lat = tab.lat[ro];
+                        rel = tab.rel[ro];
+                        s = SHD_ROWSTORE_S_STORED | SHD_ROWSTORE_S_REVERSED | DIRECT;
+                    }
                 }
             }
             L[k] = lat;
             R[k] = rel;
             S[k] = s;
-            if (s) {
+            if (s & SHD_ROWSTORE_S_STORED) {
                 ++c;
                 const unsigned long long lb = (unsigned long long)__double_as_longlong(lat);
                 mn = lb < mn ? lb : mn;      // stored latencies are > 0: bit order = value order
@@ -395,21 +428,73 @@ __global__ __launch_bounds__(256) void k_pack_rowstore(
     }
     for (int d = 32; d >= 1; d >>= 1) {
         c += __shfl_xor(c, d, 64);
+        nd += __shfl_xor(nd, d, 64);
         const unsigned long long o = __shfl_xor(mn, d, 64);
         mn = o < mn ? o : mn;
     }
-    if ((threadIdx.x & 63) == 0) { cnt[threadIdx.x >> 6] = c; mnb[threadIdx.x >> 6] = mn; }
+    if ((threadIdx.x & 63) == 0) { cnt[threadIdx.x >> 6] = c; mnb[threadIdx.x >> 6] = mn; ndc[threadIdx.x >> 6] = nd; }
     __syncthreads();
     if (threadIdx.x == 0) {
         unsigned long long cc = 0, m = INF_BITS;
         for (int w = 0; w < 4; ++w) { cc += cnt[w]; m = mnb[w] < m ? mnb[w] : m; }
         if (cc) atomicAdd(&acc[0], cc);
         if (m != INF_BITS) atomicMin(&acc[1], m);
+        if (needCount) needCount[blockIdx.x] = ndc[0] + ndc[1] + ndc[2] + ndc[3];
     }
+}
+
+// The needs of image row rows[blockIdx.x] of the view (segment `img` from
+// off[pv.lo]) as (a, b) pairs at pairs[2 * pre[blockIdx.x] ...], ascending b:
+// its slots k >= hi - a with PACK_S_PENDING, which k_pack_rowstore left there
+// by the need rule.  Chunks of 256 slots; per chunk every wave ballots its 64
+// slots, the four popcounts give each wave its place, the lanes below a lane
+// its place in the wave.
+__global__ __launch_bounds__(256) void k_pack_needs(PackView pv, int64_t T, const int64_t* __restrict__ off,
+                                                    const uint8_t* __restrict__ img,
+                                                    const int32_t* __restrict__ rows,
+                                                    const int64_t* __restrict__ pre,
+                                                    int32_t* __restrict__ pairs) {
+    __shared__ int wc[4];
+    const int64_t a = rows[blockIdx.x], len = T - a;
+    const uint8_t* S = img + (off[a] - off[pv.lo]) + SHD_ROWSTORE_IMAGE_HEADER + (size_t)len * 16;
+    int32_t* out = pairs + 2 * pre[blockIdx.x];
+    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
+    int64_t done = 0;                            // needs written so far (uniform)
+    for (int64_t k0 = pv.hi - a; k0 < len; k0 += 256) {      // (hi > a: b >= hi means k >= hi - a >= 1)
+        const int64_t k = k0 + threadIdx.x;
+        const bool p = k < len && (S[k] & PACK_S_PENDING);
+        const unsigned long long m = __ballot(p);
+        if (lane == 0) wc[w] = __popcll(m);
+        __syncthreads();
+        int before = 0, all = 0;
+        for (int i = 0; i < 4; ++i) { before += i < w ? wc[i] : 0; all += wc[i]; }
+        if (p) {
+            const int64_t at = done + before + __popcll(m & ((1ull << lane) - 1ull));
+            out[2 * at] = (int32_t)a;
+            out[2 * at + 1] = (int32_t)(a + k);
+        }
+        done += all;
+        __syncthreads();                         // wc is rewritten by the next chunk
+    }
+}
+
+// One thread per need (a, b) of a list whose rows b this table view owns.
+__global__ __launch_bounds__(256) void k_pack_answer(DevTable tab0, const int32_t* __restrict__ pairs,
+                                                     int64_t n, uint8_t* __restrict__ ok,
+                                                     double* __restrict__ lat, double* __restrict__ rel) {
+    const DevTable tab = global_view(tab0);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int64_t a = pairs[2 * i], b = pairs[2 * i + 1];
+    const size_t ro = (size_t)(b - tab.rowStart) * (size_t)tab.T + (size_t)a;
+    ok[i] = (tab.flags[ro] & (F_UNREACHABLE | F_NOEDGE)) ? 0 : 1;
+    lat[i] = tab.lat[ro];
+    rel[i] = tab.rel[ro];
 }
 
 // per source row: 1 when no target's fold failed (F_NOEDGE; unreachable
 // targets do not count), topology.c:1815-1859's isAllSuccess
+// (out[i]: the table's local row i)
 __global__ __launch_bounds__(256) void k_rows_all_success(DevTable tab0, int32_t* __restrict__ out) {
     const DevTable tab = global_view(tab0);
     __shared__ int bad;
@@ -428,31 +513,47 @@ int pack_adj_lds_bytes(int64_t T, bool directed) {
     return b <= 64 * 1024 ? (int)b : -1;
 }
 
-int launch_pack_rowstore(const DevTable& tab, const int64_t* dOff, uint8_t* dImg,
-                         unsigned long long* dAcc, int mode, const DevGraph* g, const int32_t* dPosOf,
-                         bool direct, bool complete, void* stream) {
-    if (tab.T <= 0) return 0;
+int launch_pack_rowstore(const DevTable& tab, const PackView& pv, const int64_t* dOff, uint8_t* dImg,
+                         unsigned long long* dAcc, int32_t* dNeedCount, int mode, const DevGraph* g,
+                         const int32_t* dPosOf, bool direct, bool complete, void* stream) {
+    if (pv.hi <= pv.lo) return 0;
     const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
-    const dim3 grid((unsigned)tab.T), block(256);
+    const dim3 grid((unsigned)(pv.hi - pv.lo)), block(256);
     if (mode == PACK_ADJ) {
         if (!g || !dPosOf) return -1;
         const int lds = pack_adj_lds_bytes(tab.T, g->inCol != g->col);
         if (lds < 0) return -1;
         const PackAdj pa{*g, dPosOf, (int32_t)((tab.T + 31) / 32), direct ? 1 : 0, complete ? 1 : 0};
-        hipLaunchKernelGGL(k_pack_rowstore<PACK_ADJ>, grid, block, (size_t)lds, st, tab, dOff, dImg, dAcc, pa);
+        hipLaunchKernelGGL(k_pack_rowstore<PACK_ADJ>, grid, block, (size_t)lds, st, tab, pv, dOff, dImg, dAcc,
+                           dNeedCount, pa);
     } else if (mode == PACK_COMPLETE) {
-        hipLaunchKernelGGL(k_pack_rowstore<PACK_COMPLETE>, grid, block, 0, st, tab, dOff, dImg, dAcc,
-                           PackNone{});
+        hipLaunchKernelGGL(k_pack_rowstore<PACK_COMPLETE>, grid, block, 0, st, tab, pv, dOff, dImg, dAcc,
+                           dNeedCount, PackNone{});
     } else {
-        hipLaunchKernelGGL(k_pack_rowstore<PACK_PLAIN>, grid, block, 0, st, tab, dOff, dImg, dAcc,
-                           PackNone{});
+        hipLaunchKernelGGL(k_pack_rowstore<PACK_PLAIN>, grid, block, 0, st, tab, pv, dOff, dImg, dAcc,
+                           dNeedCount, PackNone{});
     }
     return 0;
 }
 
-void launch_rows_all_success(const DevTable& tab, int32_t* dOut, void* stream) {
-    if (tab.T <= 0) return;
-    hipLaunchKernelGGL(k_rows_all_success, dim3((unsigned)tab.T), dim3(256), 0,
+void launch_pack_needs(const PackView& pv, int64_t T, const int64_t* dOff, const uint8_t* dImg,
+                       const int32_t* dRows, const int64_t* dPre, int32_t nRows, int32_t* dPairs,
+                       void* stream) {
+    if (nRows <= 0) return;
+    hipLaunchKernelGGL(k_pack_needs, dim3((unsigned)nRows), dim3(256), 0, reinterpret_cast<hipStream_t>(stream),
+                       pv, T, dOff, dImg, dRows, dPre, dPairs);
+}
+
+void launch_pack_answer(const DevTable& tab, const int32_t* dPairs, int64_t n, uint8_t* dOk, double* dLat,
+                        double* dRel, void* stream) {
+    if (n <= 0) return;
+    hipLaunchKernelGGL(k_pack_answer, dim3((unsigned)((n + 255) / 256)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), tab, dPairs, n, dOk, dLat, dRel);
+}
+
+void launch_rows_all_success(const DevTable& tab, int32_t rows, int32_t* dOut, void* stream) {
+    if (tab.T <= 0 || rows <= 0) return;
+    hipLaunchKernelGGL(k_rows_all_success, dim3((unsigned)rows), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), tab, dOut);
 }
 

@@ -351,9 +351,14 @@ void launch_self_paths(const DevGraph& g, const int32_t* dVerts, int32_t count, 
 void launch_pairs(const DevGraph& g, const int32_t* dSrc, const int32_t* dDst, int64_t count,
                   int mode, double* dLat, double* dRel, uint8_t* dFlags, void* stream);
 void launch_incident_min(const DevGraph& g, const int32_t* dEdgeCount, int32_t* dOut, void* stream);
-// path-cache image of the whole table (rows 0..T-1 of `tab`, rowStart 0) in
-// the row store's layout (dOff: shd_rowstore_image_layout); dAcc[0] += stored
-// entries, dAcc[1] = min stored latency bits (init INF_BITS).  mode 0: the
+// path-cache image of a table view -- triangular rows [pv.lo, pv.hi), which
+// `tab` holds at local row a - tab.rowStart; the whole table is [0, T) -- in
+// the row store's layout (dOff: shd_rowstore_image_layout, all T + 1 entries;
+// dImg: the segment from dOff[pv.lo]); dAcc[0] += stored
+// entries, dAcc[1] = min stored latency bits (init INF_BITS).  A slot whose
+// reverse entry lies in a row >= pv.hi is a need: PACK_S_PENDING in its state
+// byte, not in dAcc, counted in dNeedCount[a - pv.lo] (null: a view with no
+// rows behind it, nothing counted).  mode 0: the
 // non-direct store rule alone; 1: a complete graph's direct table, entries
 // stored as direct; 2: the prefersDirectPaths rule (or, `complete`, a complete
 // graph whose table holds Dijkstra rows) with adjacency bitmaps in LDS -- g =
@@ -361,11 +366,23 @@ void launch_incident_min(const DevGraph& g, const int32_t* dEdgeCount, int32_t* 
 // `direct` = also store the direct entries.  -1: mode 2's bitmaps exceed LDS
 // (pack_adj_lds_bytes < 0) or its arguments are missing; nothing launched.
 int pack_adj_lds_bytes(int64_t T, bool directed);
-int launch_pack_rowstore(const DevTable& tab, const int64_t* dOff, uint8_t* dImg,
-                         unsigned long long* dAcc, int mode, const DevGraph* g, const int32_t* dPosOf,
-                         bool direct, bool complete, void* stream);
-// per table row: 1 = no F_NOEDGE target (isAllSuccess of topology.c:1815-1859)
-void launch_rows_all_success(const DevTable& tab, int32_t* dOut, void* stream);
+struct PackView {
+    int32_t lo, hi;
+};
+constexpr uint8_t PACK_S_PENDING = 0x80;   // beside SHD_ROWSTORE_S_*: never in an adopted image
+int launch_pack_rowstore(const DevTable& tab, const PackView& pv, const int64_t* dOff, uint8_t* dImg,
+                         unsigned long long* dAcc, int32_t* dNeedCount, int mode, const DevGraph* g,
+                         const int32_t* dPosOf, bool direct, bool complete, void* stream);
+// the needs of the view's rows dRows[0, nRows) (ascending, each with needs) as
+// (a, b) int32 pairs, row i's from pair dPre[i] of dPairs, ascending b
+void launch_pack_needs(const PackView& pv, int64_t T, const int64_t* dOff, const uint8_t* dImg,
+                       const int32_t* dRows, const int64_t* dPre, int32_t nRows, int32_t* dPairs,
+                       void* stream);
+// per need (a, b) of dPairs, row b in `tab`: ok = the fold (b, a) succeeded, its lat / rel
+void launch_pack_answer(const DevTable& tab, const int32_t* dPairs, int64_t n, uint8_t* dOk, double* dLat,
+                        double* dRel, void* stream);
+// per local row of `tab`: 1 = no F_NOEDGE target (isAllSuccess of topology.c:1815-1859)
+void launch_rows_all_success(const DevTable& tab, int32_t rows, int32_t* dOut, void* stream);
 // 64-bit fingerprint per table row (local rows firstLocal .. + rows), pe_aux.hip
 void launch_row_checksums(const DevTable& tab, int64_t firstLocal, int32_t rows, uint64_t* dOut,
                           void* stream);

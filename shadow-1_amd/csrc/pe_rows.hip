@@ -1,6 +1,7 @@
 // pe_rows.hip -- row transport of the MI355X Shadow path engine: everything
 // that moves finished table rows.  Out of the device: shd_pe_get_row(s),
-// shd_pe_copy_rows_device, shd_pe_row_checksums, shd_pe_fill_rowstore(_ex);
+// shd_pe_copy_rows_device, shd_pe_row_checksums, shd_pe_fill_rowstore(_ex),
+// shd_pe_fill_rowstore_shards;
 // between devices: shd_pe_gather, shd_pe_put_rows, shd_pe_comm_*.
 //
 // A table is the parallel field arrays of TABLE_FIELDS (pe_device.hpp), and a
@@ -17,6 +18,7 @@
 #include <thread>
 
 #include "pe_engine.hpp"
+#include "pe_fill.hpp"
 
 using namespace shdpe;
 
@@ -281,7 +283,8 @@ struct HostImage {
     ~HostImage();
 };
 
-static void host_image_prepare(HostImage* im, size_t bytes) {
+// (regFlags: hipHostRegisterPortable when several devices DMA into the image)
+static void host_image_prepare(HostImage* im, size_t bytes, unsigned regFlags) {
     const auto t0 = std::chrono::steady_clock::now();
     void* p = mmap(nullptr, bytes, PROT_READ | PROT_WRITE, MAP_PRIVATE | MAP_ANONYMOUS | MAP_NORESERVE, -1, 0);
     if (p == MAP_FAILED) return;
@@ -297,7 +300,7 @@ static void host_image_prepare(HostImage* im, size_t bytes) {
     im->p = p;
     im->bytes = bytes;
     const auto t1 = std::chrono::steady_clock::now();
-    im->registered = hipHostRegister(p, bytes, hipHostRegisterDefault) == hipSuccess;
+    im->registered = hipHostRegister(p, bytes, regFlags) == hipSuccess;
     const auto t2 = std::chrono::steady_clock::now();
     im->msTouch = std::chrono::duration<double, std::milli>(t1 - t0).count();
     im->msRegister = std::chrono::duration<double, std::milli>(t2 - t1).count();
@@ -317,6 +320,29 @@ static void host_image_free_cb(void* ctx, void* p) {
     delete static_cast<HostImage*>(ctx);
 }
 
+// posOf[] on the shard's device (the current one), once per shard; caller holds copyMu
+static int ensure_pos_of(ShdPe* pe, Shard* s) {
+    if (s->dPosOf) return SHD_PE_OK;
+    void* d = nullptr;
+    if (hipMalloc(&d, pe->posOf.size() * 4) != hipSuccess) return SHD_PE_ENOMEM;
+    if (hipMemcpy(d, pe->posOf.data(), pe->posOf.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
+        (void)hipFree(d);
+        return SHD_PE_EHIP;
+    }
+    s->dPosOf = static_cast<int32_t*>(d);
+    return SHD_PE_OK;
+}
+
+// The pack kernel's variant for a fill: 0 the non-direct rule alone (no flag,
+// or DIRECT_PAIRS without a pair topology.c:2019-2021 serves directly), 1 a
+// complete graph's direct table (k_direct_rows wrote the entries), 2 the
+// adjacency rule (prefersDirectPaths; a complete graph whose table holds
+// Dijkstra rows, forceMode)
+static int fill_pack_mode(const ShdPe* pe, int32_t fillFlags) {
+    if (pe->hg.isComplete) return pe->mode == 2 ? 1 : 2;
+    return (fillFlags & SHD_PE_FILL_PREFER_DIRECT) ? 2 : 0;
+}
+
 extern "C" int shd_pe_fill_rowstore_ex(ShdPe* pe, ShdRowStore* st, int32_t fillFlags,
                                        int32_t* rowResult, double* msOut) {
     if (!pe || !st) return SHD_PE_EINVAL;
@@ -324,14 +350,7 @@ extern "C" int shd_pe_fill_rowstore_ex(ShdPe* pe, ShdRowStore* st, int32_t fillF
     if (shd_rowstore_size(st) != 0) return SHD_PE_EINVAL;   // (adopt_image re-checks under its lock)
     const int32_t T = (int32_t)pe->attached.size();
     const bool wantDirect = (fillFlags & SHD_PE_FILL_DIRECT_PAIRS) != 0;
-    // the pack kernel's variant: 0 the non-direct rule alone (no flag, or
-    // DIRECT_PAIRS without a pair topology.c:2019-2021 serves directly), 1 a
-    // complete graph's direct table (k_direct_rows wrote the entries), 2 the
-    // adjacency rule (prefersDirectPaths; a complete graph whose table holds
-    // Dijkstra rows, forceMode)
-    int packMode = 0;
-    if (pe->hg.isComplete) packMode = pe->mode == 2 ? 1 : 2;
-    else if (fillFlags & SHD_PE_FILL_PREFER_DIRECT) packMode = 2;
+    const int packMode = fill_pack_mode(pe, fillFlags);
     if (packMode == 2 && pack_adj_lds_bytes(T, pe->hg.directed) < 0) return SHD_PE_ETOOBIG;
     static const char* const modeName[3] = {"plain", "complete-direct", "prefer-direct"};
     auto now = [] { return std::chrono::steady_clock::now(); };
@@ -344,7 +363,7 @@ extern "C" int shd_pe_fill_rowstore_ex(ShdPe* pe, ShdRowStore* st, int32_t fillF
     const auto t0 = now();
     std::unique_ptr<HostImage> him(new HostImage);
     std::thread prep;
-    if (pack) prep = std::thread(host_image_prepare, him.get(), bytes);   // beside the compute
+    if (pack) prep = std::thread(host_image_prepare, him.get(), bytes, (unsigned)hipHostRegisterDefault);   // beside the compute
     int rc = ensure_rows(pe, 0, T);
     const auto tc = now();
     if (prep.joinable()) prep.join();
@@ -362,15 +381,7 @@ extern "C" int shd_pe_fill_rowstore_ex(ShdPe* pe, ShdRowStore* st, int32_t fillF
     else if (pe->G == 1) tab = &s->tab;
     else return SHD_PE_ENOTOWNED;          // rows spread over shards: gather first
     if (hipSetDevice(s->device) != hipSuccess) return SHD_PE_EHIP;
-    if (pack && packMode == 2 && !s->dPosOf) {   // once per engine
-        void* d = nullptr;
-        if (hipMalloc(&d, pe->posOf.size() * 4) != hipSuccess) return SHD_PE_ENOMEM;
-        if (hipMemcpy(d, pe->posOf.data(), pe->posOf.size() * 4, hipMemcpyHostToDevice) != hipSuccess) {
-            (void)hipFree(d);
-            return SHD_PE_EHIP;
-        }
-        s->dPosOf = static_cast<int32_t*>(d);
-    }
+    if (pack && packMode == 2 && (rc = ensure_pos_of(pe, s))) return rc;
     void *dImg = nullptr, *dOff = nullptr, *dAcc = nullptr, *dAll = nullptr;
     void* const hImg = him->p;
     struct Free {   // device temporaries, every exit path (the host image: ~HostImage)
@@ -389,11 +400,12 @@ extern "C" int shd_pe_fill_rowstore_ex(ShdPe* pe, ShdRowStore* st, int32_t fillF
     hipError_t e = hipMemcpyAsync(dOff, off.data(), off.size() * 8, hipMemcpyHostToDevice, s->copyStream);
     if (e == hipSuccess) e = hipMemcpyAsync(dAcc, acc0, 16, hipMemcpyHostToDevice, s->copyStream);
     if (e == hipSuccess) {
-        if (pack && launch_pack_rowstore(*tab, (const int64_t*)dOff, (uint8_t*)dImg,
-                                         (unsigned long long*)dAcc, packMode, &s->dgAux, s->dPosOf,
+        // the whole table: the one view with no rows behind it, so no needs
+        if (pack && launch_pack_rowstore(*tab, PackView{0, T}, (const int64_t*)dOff, (uint8_t*)dImg,
+                                         (unsigned long long*)dAcc, nullptr, packMode, &s->dgAux, s->dPosOf,
                                          wantDirect, pe->hg.isComplete, s->copyStream))
             return SHD_PE_ETOOBIG;
-        launch_rows_all_success(*tab, (int32_t*)dAll, s->copyStream);
+        launch_rows_all_success(*tab, T, (int32_t*)dAll, s->copyStream);
         e = hipGetLastError();
     }
     if (e == hipSuccess) e = hipStreamSynchronize(s->copyStream);
@@ -419,6 +431,300 @@ extern "C" int shd_pe_fill_rowstore_ex(ShdPe* pe, ShdRowStore* st, int32_t fillF
 
 extern "C" int shd_pe_fill_rowstore(ShdPe* pe, ShdRowStore* st, int32_t* rowResult, double* msOut) {
     return shd_pe_fill_rowstore_ex(pe, st, 0, rowResult, msOut);
+}
+
+// ---------------------------------------------------------------------------
+// The same fill without a gather ("a per-GPU D2H of its own
+// shard replaces the gather"): every row shard of an in-process engine packs
+// its own triangular rows [lo, hi) from its own table on its own device and
+// DMAs the segment to its place off[lo] in the one host image.  A slot of row
+// a is decided by row a alone unless its forward entry is not used; then the
+// rule looks at entry (b, a), and for b >= hi that row is another shard's: a
+// need (k_pack_rowstore).  Needs go to the owner of row b and come back as
+// (ok, lat, rel) through pinned host staging -- no peer access, no full table
+// -- in rounds of at most needBudgetBytes, and pe_fill.cpp writes the answers
+// into the landed image before the store adopts it.
+// ---------------------------------------------------------------------------
+namespace {
+
+// One shard's device temporaries of a call, with their running sum; freed on
+// every exit path.
+struct DevTemps {
+    int device = 0;
+    std::vector<std::pair<void*, int64_t>> blocks;
+    int64_t cur = 0, peak = 0;
+    void* take(int64_t bytes) {
+        void* q = nullptr;
+        if (hipSetDevice(device) != hipSuccess || hipMalloc(&q, (size_t)std::max<int64_t>(bytes, 16)) != hipSuccess)
+            return nullptr;
+        blocks.push_back({q, bytes});
+        cur += bytes;
+        peak = std::max(peak, cur);
+        return q;
+    }
+    void release(size_t keep) {
+        while (blocks.size() > keep) {
+            (void)hipSetDevice(device);
+            (void)hipFree(blocks.back().first);
+            cur -= blocks.back().second;
+            blocks.pop_back();
+        }
+    }
+    ~DevTemps() { release(0); }
+};
+
+struct PinnedBlock {
+    void* p = nullptr;
+    ~PinnedBlock() { if (p) (void)hipHostFree(p); }
+};
+
+// What a shard keeps on its device from the pack to the end of its rounds.
+struct ShardFill {
+    Shard* s = nullptr;
+    PackView pv{0, 0};
+    int64_t segBytes = 0;
+    uint8_t* dImg = nullptr;
+    int64_t* dOff = nullptr;
+    unsigned long long* dAcc = nullptr;
+    int32_t *dAll = nullptr, *dNeed = nullptr;
+    unsigned long long acc[2] = {0ull, 0ull};
+    std::vector<int32_t> needCount, rounds;
+};
+
+}  // namespace
+
+extern "C" int shd_pe_fill_rowstore_shards(ShdPe* pe, ShdRowStore* st, int32_t fillFlags,
+                                           int64_t needBudgetBytes, int32_t* rowResult,
+                                           ShdPeFillShardsInfo* info) {
+    if (!pe || !st) return SHD_PE_EINVAL;
+    if (fillFlags & ~(SHD_PE_FILL_PREFER_DIRECT | SHD_PE_FILL_DIRECT_PAIRS)) return SHD_PE_EINVAL;
+    if (shd_rowstore_size(st) != 0) return SHD_PE_EINVAL;
+    const int32_t T = (int32_t)pe->attached.size();
+    const bool wantDirect = (fillFlags & SHD_PE_FILL_DIRECT_PAIRS) != 0;
+    const int packMode = fill_pack_mode(pe, fillFlags);
+    if (packMode == 2 && pack_adj_lds_bytes(T, pe->hg.directed) < 0) return SHD_PE_ETOOBIG;
+    const bool pack = !pe->hg.isComplete || wantDirect;
+    std::vector<int64_t> off((size_t)T + 1);
+    shd_rowstore_image_layout(T, off.data());
+    const size_t bytes = (size_t)off[(size_t)T];
+    ShdPeFillShardsInfo inf{};
+    bool full;
+    {
+        std::lock_guard<std::mutex> lk(pe->copyMu);
+        full = pe->G == 1 || pe->gathered;
+    }
+    if (full) {   // one table serves the call: the _ex path
+        double ms[3] = {0.0, 0.0, 0.0};
+        const int rc = shd_pe_fill_rowstore_ex(pe, st, fillFlags, rowResult, ms);
+        if (rc) return rc;
+        inf.shards = 1;
+        inf.fromFullTable = 1;
+        inf.deviceBytesPeak = (int64_t)(pack ? bytes : 0) + (int64_t)off.size() * 8 + 16 + (int64_t)T * 4;
+        inf.msCompute = ms[0];
+        inf.msPack = ms[1];
+        inf.msDma = ms[2];
+        if (info) *info = inf;
+        return SHD_PE_OK;
+    }
+    // rows of other processes' engines: their store is theirs
+    if (pe->opt.shardCount > 1 || (int)pe->shards.size() != pe->G) return SHD_PE_ENOTOWNED;
+    auto now = [] { return std::chrono::steady_clock::now(); };
+    auto ms = [](auto a, auto b) { return std::chrono::duration<double, std::milli>(b - a).count(); };
+    const auto t0 = now();
+    std::unique_ptr<HostImage> him(new HostImage);
+    std::thread prep;
+    if (pack) prep = std::thread(host_image_prepare, him.get(), bytes, (unsigned)hipHostRegisterPortable);
+    int rc = ensure_rows(pe, 0, T);
+    if (prep.joinable()) prep.join();
+    if (rc) return rc;
+    if (pack && !him->p) return SHD_PE_ENOMEM;
+    uint8_t* const hImg = static_cast<uint8_t*>(him->p);
+    std::lock_guard<std::mutex> lk(pe->copyMu);
+    const size_t G = pe->shards.size();
+    std::vector<DevTemps> temps(G);
+    std::vector<ShardFill> sf(G);
+    for (size_t g = 0; g < G; ++g) {
+        Shard* s = pe->shards[g].get();
+        ShardFill& f = sf[g];
+        f.s = s;
+        f.pv = PackView{s->rowStart, s->rowStart + s->rowCount};
+        temps[g].device = s->device;
+        if (!s->rowCount) continue;
+        if (!s->tableReady) return SHD_PE_ENOTOWNED;
+        inf.shards++;
+        HIPCHK(hipSetDevice(s->device));
+        if (pack && packMode == 2 && (rc = ensure_pos_of(pe, s))) return rc;
+        f.segBytes = off[(size_t)f.pv.hi] - off[(size_t)f.pv.lo];
+        if (pack) {
+            f.dImg = static_cast<uint8_t*>(temps[g].take(f.segBytes));
+            f.dOff = static_cast<int64_t*>(temps[g].take((int64_t)off.size() * 8));
+            f.dAcc = static_cast<unsigned long long*>(temps[g].take(16));
+            f.dNeed = static_cast<int32_t*>(temps[g].take((int64_t)s->rowCount * 4));
+        }
+        f.dAll = static_cast<int32_t*>(temps[g].take((int64_t)s->rowCount * 4));
+        if (!f.dAll || (pack && (!f.dImg || !f.dOff || !f.dAcc || !f.dNeed))) return SHD_PE_ENOMEM;
+    }
+    auto sync_all = [&]() -> int {
+        for (ShardFill& f : sf) {
+            if (!f.s->rowCount) continue;
+            HIPCHK(hipSetDevice(f.s->device));
+            HIPCHK(hipStreamSynchronize(f.s->copyStream));
+        }
+        return SHD_PE_OK;
+    };
+    // pack: every shard on its own device and copy stream
+    const auto t1 = now();
+    const unsigned long long acc0[2] = {0ull, 0x7FF0000000000000ull};
+    for (ShardFill& f : sf) {
+        Shard* s = f.s;
+        if (!s->rowCount) continue;
+        HIPCHK(hipSetDevice(s->device));
+        if (pack) {
+            HIPCHK(hipMemcpyAsync(f.dOff, off.data(), off.size() * 8, hipMemcpyHostToDevice, s->copyStream));
+            HIPCHK(hipMemcpyAsync(f.dAcc, acc0, 16, hipMemcpyHostToDevice, s->copyStream));
+            if (launch_pack_rowstore(s->tab, f.pv, f.dOff, f.dImg, f.dAcc, f.dNeed, packMode, &s->dgAux,
+                                     s->dPosOf, wantDirect, pe->hg.isComplete, s->copyStream))
+                return SHD_PE_ETOOBIG;
+        }
+        launch_rows_all_success(s->tab, s->rowCount, f.dAll, s->copyStream);
+        HIPCHK(hipGetLastError());
+    }
+    if ((rc = sync_all())) return rc;
+    // DMA: the segments to their place in the one image (distinct devices:
+    // concurrently), then the small results
+    const auto t2 = now();
+    if (pack)
+        for (ShardFill& f : sf) {
+            if (!f.s->rowCount) continue;
+            HIPCHK(hipSetDevice(f.s->device));
+            HIPCHK(hipMemcpyAsync(hImg + off[(size_t)f.pv.lo], f.dImg, (size_t)f.segBytes, hipMemcpyDeviceToHost,
+                                  f.s->copyStream));
+        }
+    for (ShardFill& f : sf) {
+        Shard* s = f.s;
+        if (!s->rowCount) continue;
+        HIPCHK(hipSetDevice(s->device));
+        if (pack) {
+            f.needCount.resize((size_t)s->rowCount);
+            HIPCHK(hipMemcpyAsync(f.acc, f.dAcc, 16, hipMemcpyDeviceToHost, s->copyStream));
+            HIPCHK(hipMemcpyAsync(f.needCount.data(), f.dNeed, (size_t)s->rowCount * 4, hipMemcpyDeviceToHost,
+                                  s->copyStream));
+        }
+        if (rowResult)
+            HIPCHK(hipMemcpyAsync(rowResult + f.pv.lo, f.dAll, (size_t)s->rowCount * 4, hipMemcpyDeviceToHost,
+                                  s->copyStream));
+    }
+    if ((rc = sync_all())) return rc;
+    const auto t3 = now();
+    // needs: lists in rounds, routed to the owners of their rows b, answered, applied
+    FillTotals tot;
+    int64_t maxRound = 0;
+    for (ShardFill& f : sf) {
+        if (f.needCount.empty()) continue;
+        fill_plan_rounds(f.needCount.data(), (int32_t)f.needCount.size(), needBudgetBytes, f.rounds);
+        for (size_t r = 0; r + 1 < f.rounds.size(); ++r) {
+            int64_t n = 0;
+            for (int32_t i = f.rounds[r]; i < f.rounds[r + 1]; ++i) n += f.needCount[(size_t)i];
+            maxRound = std::max(maxRound, n);
+            inf.needs += n;
+        }
+    }
+    PinnedBlock stg;
+    if (maxRound) {
+        // pairs as listed | pairs by owner | lat | rel | ok
+        if (hipHostMalloc(&stg.p, (size_t)maxRound * 33, hipHostMallocPortable) != hipSuccess) {
+            stg.p = nullptr;
+            return SHD_PE_ENOMEM;
+        }
+    }
+    NeedPair* const hPairs = static_cast<NeedPair*>(stg.p);
+    NeedPair* const hRouted = hPairs + maxRound;
+    double* const hLat = reinterpret_cast<double*>(hRouted + maxRound);
+    double* const hRel = hLat + maxRound;
+    uint8_t* const hOk = reinterpret_cast<uint8_t*>(hRel + maxRound);
+    std::vector<int32_t> rowsV;
+    std::vector<int64_t> preV, start, order;
+    std::vector<size_t> mark(G);
+    for (size_t g = 0; g < G; ++g) {
+        ShardFill& f = sf[g];
+        Shard* s = f.s;
+        for (size_t r = 0; r + 1 < f.rounds.size(); ++r) {
+            rowsV.clear();
+            preV.clear();
+            int64_t n = 0;
+            for (int32_t i = f.rounds[r]; i < f.rounds[r + 1]; ++i)
+                if (f.needCount[(size_t)i] > 0) {
+                    rowsV.push_back(f.pv.lo + i);
+                    preV.push_back(n);
+                    n += f.needCount[(size_t)i];
+                }
+            for (size_t o = 0; o < G; ++o) mark[o] = temps[o].blocks.size();
+            const int32_t nr = (int32_t)rowsV.size();
+            int32_t* dRows = static_cast<int32_t*>(temps[g].take((int64_t)nr * 4));
+            int64_t* dPre = static_cast<int64_t*>(temps[g].take((int64_t)nr * 8));
+            int32_t* dPairs = static_cast<int32_t*>(temps[g].take(n * 8));
+            if (!dRows || !dPre || !dPairs) return SHD_PE_ENOMEM;
+            HIPCHK(hipSetDevice(s->device));
+            HIPCHK(hipMemcpyAsync(dRows, rowsV.data(), (size_t)nr * 4, hipMemcpyHostToDevice, s->copyStream));
+            HIPCHK(hipMemcpyAsync(dPre, preV.data(), (size_t)nr * 8, hipMemcpyHostToDevice, s->copyStream));
+            launch_pack_needs(f.pv, T, f.dOff, f.dImg, dRows, dPre, nr, dPairs, s->copyStream);
+            HIPCHK(hipGetLastError());
+            HIPCHK(hipMemcpyAsync(hPairs, dPairs, (size_t)n * 8, hipMemcpyDeviceToHost, s->copyStream));
+            HIPCHK(hipStreamSynchronize(s->copyStream));
+            if (fill_route_needs(hPairs, n, pe->bounds.data(), (int32_t)G, start, order)) return SHD_PE_EHIP;
+            for (int64_t j = 0; j < n; ++j) hRouted[j] = hPairs[order[(size_t)j]];
+            for (size_t o = 0; o < G; ++o) {
+                const int64_t at = start[o], c = start[o + 1] - at;
+                if (!c) continue;
+                Shard* ow = pe->shards[o].get();
+                if (!ow->tableReady) return SHD_PE_ENOTOWNED;
+                int32_t* dP = static_cast<int32_t*>(temps[o].take(c * 8));
+                double* dLat = static_cast<double*>(temps[o].take(c * 8));
+                double* dRel = static_cast<double*>(temps[o].take(c * 8));
+                uint8_t* dOk = static_cast<uint8_t*>(temps[o].take(c));
+                if (!dP || !dLat || !dRel || !dOk) return SHD_PE_ENOMEM;
+                HIPCHK(hipSetDevice(ow->device));
+                HIPCHK(hipMemcpyAsync(dP, hRouted + at, (size_t)c * 8, hipMemcpyHostToDevice, ow->copyStream));
+                launch_pack_answer(ow->tab, dP, c, dOk, dLat, dRel, ow->copyStream);
+                HIPCHK(hipGetLastError());
+                HIPCHK(hipMemcpyAsync(hLat + at, dLat, (size_t)c * 8, hipMemcpyDeviceToHost, ow->copyStream));
+                HIPCHK(hipMemcpyAsync(hRel + at, dRel, (size_t)c * 8, hipMemcpyDeviceToHost, ow->copyStream));
+                HIPCHK(hipMemcpyAsync(hOk + at, dOk, (size_t)c, hipMemcpyDeviceToHost, ow->copyStream));
+            }
+            for (size_t o = 0; o < G; ++o) {
+                if (start[o + 1] == start[o]) continue;
+                HIPCHK(hipSetDevice(pe->shards[o]->device));
+                HIPCHK(hipStreamSynchronize(pe->shards[o]->copyStream));
+            }
+            if (fill_apply_answers(hImg, off.data(), T, hRouted, n, hOk, hLat, hRel, packMode == 1, &tot))
+                return SHD_PE_EHIP;   // a list that does not match the image's pending slots
+            for (size_t o = 0; o < G; ++o) temps[o].release(mark[o]);
+            inf.needRounds++;
+        }
+    }
+    const auto t4 = now();
+    inf.needsStored = tot.needsStored;
+    for (size_t g = 0; g < G; ++g) inf.deviceBytesPeak = std::max(inf.deviceBytesPeak, temps[g].peak);
+    if (pack) {
+        int64_t stored = tot.stored;
+        double mn = tot.minLatency;
+        for (ShardFill& f : sf) {
+            if (!f.s->rowCount) continue;
+            double m;
+            std::memcpy(&m, &f.acc[1], 8);
+            stored += (int64_t)f.acc[0];
+            mn = m < mn ? m : mn;
+        }
+        rc = shd_rowstore_adopt_image(st, hImg, (int64_t)bytes, host_image_free_cb, him.get(), stored, mn);
+        if (rc) return rc;
+        him.release();   // the store owns it now
+    }
+    inf.msCompute = ms(t0, t1);
+    inf.msPack = ms(t1, t2);
+    inf.msDma = ms(t2, t3);
+    inf.msResolve = ms(t3, t4);
+    if (info) *info = inf;
+    return SHD_PE_OK;
 }
 
 // ---------------------------------------------------------------------------

@@ -206,6 +206,18 @@ extern "C" int shd_topology_fill(ShdTopology* t, double* msOut) {
     return SHD_PE_OK;
 }
 
+// shd_topology_fill through the shard-by-shard entry point (no gather needed)
+extern "C" int shd_topology_fill_shards(ShdTopology* t, int64_t needBudgetBytes, ShdPeFillShardsInfo* info) {
+    if (!t) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(t->mu);
+    if (shd_rowstore_size(t->store) != 0) return SHD_PE_EINVAL;
+    const int32_t flags = SHD_PE_FILL_DIRECT_PAIRS | (t->prefersDirectPaths ? SHD_PE_FILL_PREFER_DIRECT : 0);
+    const int rc = shd_pe_fill_rowstore_shards(t->pe, t->store, flags, needBudgetBytes, nullptr, info);
+    if (rc) return rc;
+    t->allComputed = true;
+    return SHD_PE_OK;
+}
+
 extern "C" int64_t shd_topology_rows_computed(const ShdTopology* t) {
     return t ? t->rowsComputed.load(std::memory_order_relaxed) : 0;
 }

@@ -45,6 +45,7 @@ EXPORTS = [
     "shd_rowstore_foreach", "shd_rowstore_store_rows", "shd_pe_put_rows", "shd_pe_row_checksums",
     "shd_rowstore_image_layout", "shd_rowstore_adopt_image", "shd_pe_fill_rowstore",
     "shd_pe_fill_rowstore_ex", "shd_topology_fill",
+    "shd_pe_fill_rowstore_shards", "shd_topology_fill_shards",
     "shd_graphml_vertex_attrs", "shd_graphml_attr_code", "shd_graphml_vertex_attr_string",
     "shd_pe_attach_new", "shd_pe_attach_free", "shd_pe_attach_hosts", "shd_pe_attach_host",
     "shd_pe_attach_set_chunk", "shd_pe_attach_timing",
@@ -53,6 +54,17 @@ EXPORTS = [
 ]
 VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
 VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
+
+
+class FillShardsInfo(C.Structure):
+    """ShdPeFillShardsInfo."""
+    _fields_ = [("shards", C.c_int32), ("fromFullTable", C.c_int32), ("needs", C.c_int64),
+                ("needsStored", C.c_int64), ("needRounds", C.c_int64), ("deviceBytesPeak", C.c_int64),
+                ("msCompute", C.c_double), ("msPack", C.c_double), ("msResolve", C.c_double),
+                ("msDma", C.c_double)]
+
+    def as_dict(self) -> dict:
+        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 class GraphDesc(C.Structure):
@@ -213,6 +225,8 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_fill_rowstore": (C.c_int, [vp, vp, vp, vp]),
         "shd_pe_fill_rowstore_ex": (C.c_int, [vp, vp, i32, vp, vp]),
         "shd_topology_fill": (C.c_int, [vp, vp]),
+        "shd_pe_fill_rowstore_shards": (C.c_int, [vp, vp, i32, i64, vp, vp]),
+        "shd_topology_fill_shards": (C.c_int, [vp, i64, vp]),
         "shd_graphml_vertex_attrs": (C.c_int, [vp, vp]),
         "shd_graphml_attr_code": (i32, [vp, i32, C.c_char_p]),
         "shd_graphml_vertex_attr_string": (C.c_char_p, [vp, i32, i32]),
@@ -227,7 +241,7 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_graph_props": (C.c_int, [vp, i32, i32, vp, vp, vp]),
         "shd_pe_graph_props_host": (C.c_int, [vp, vp, vp]),
     }
-    # ABI-3 ... ABI-7 additions: an older build loaded through SHDPE_LIB (same-box
+    # ABI-3 ... ABI-8 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
     optional = {"shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_fill_rowstore_ex",
                 "shd_topology_fill", "shd_graphml_vertex_attrs", "shd_graphml_attr_code",
@@ -235,7 +249,8 @@ def load_library(path: str = LIB_PATH):
                 "shd_pe_attach_hosts", "shd_pe_attach_host", "shd_pe_attach_set_chunk",
                 "shd_pe_attach_timing", "shd_pe_get_paths",
                 "shd_pe_paths_info", "shd_pe_graph_props",
-                "shd_pe_graph_props_host"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_pe_graph_props_host", "shd_pe_fill_rowstore_shards",
+                "shd_topology_fill_shards"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -623,6 +638,22 @@ class Engine:
                       "shd_pe_fill_rowstore_ex")
         return res, {"alloc": ms[0], "pack": ms[1], "dma": ms[2]}
 
+    def fill_rowstore_shards(self, store, prefers_direct: bool = False, direct_pairs: bool = False,
+                             fill_flags: int | None = None, need_budget: int = 0) -> tuple:
+        """shd_pe_fill_rowstore_shards: fill_rowstore on a sharded in-process
+        engine without gather() -- every shard packs and transfers its own
+        rows, slots that want another shard's row are answered by its owner
+        in rounds of at most need_budget bytes (<= 0: 64 MiB).  Returns
+        (per-row store_row results, ShdPeFillShardsInfo as a dict)."""
+        res = np.empty(self.T, np.int32)
+        info = FillShardsInfo()
+        if fill_flags is None:
+            fill_flags = (FILL_PREFER_DIRECT if prefers_direct else 0) | (FILL_DIRECT_PAIRS if direct_pairs else 0)
+        self._chk(self._lib.shd_pe_fill_rowstore_shards(self.h, store.h, int(fill_flags), int(need_budget),
+                                                        _p(res), C.byref(info)),
+                  "shd_pe_fill_rowstore_shards")
+        return res, info.as_dict()
+
     def is_complete_device(self) -> bool:
         x = C.c_int32(0)
         self._chk(self._lib.shd_pe_is_complete_device(self.h, C.byref(x)),
@@ -779,6 +810,15 @@ class TopologyShim:
         if rc:
             raise EngineError(rc, "shd_topology_fill")
         return {"alloc": ms[0], "pack": ms[1], "dma": ms[2]}
+
+    def fill_shards(self, need_budget: int = 0) -> dict:
+        """shd_topology_fill_shards: fill() through the shard-by-shard fill (a
+        sharded in-process engine needs no gather); returns its info."""
+        info = FillShardsInfo()
+        rc = self._lib.shd_topology_fill_shards(self.h, int(need_budget), C.byref(info))
+        if rc:
+            raise EngineError(rc, "shd_topology_fill_shards")
+        return info.as_dict()
 
     def increment(self, s, d):
         return self._lib.shd_topology_increment_path_packet_counter(self.h, int(s), int(d))
