@@ -542,6 +542,7 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
         BatchRanks br = batch_ranks(g, pe->attached, pe->posOf, pe->tu.batchOrder);
         pe->rank.swap(br.rank);
         pe->rowOff.swap(br.rowOff);
+        pe->hubGroups = std::move(br.groups);
     }
     pe->rowDone.reset(new (std::nothrow) std::atomic<uint8_t>[T]);
     if (!pe->rowDone) { shd_pe_destroy(pe.release()); return SHD_PE_ENOMEM; }
@@ -811,7 +812,7 @@ static void print_batch_debug(ShdPe* pe, Shard* sh, const BatchLaunch& relax, co
 }
 
 // SHDPE_DUMP_BATCHES=<file>: per batch its rows (table positions, -1 pads),
-// hub offsets and kernel counters, for offline batch-cost models
+// hub offsets, kernel counters and hub-group distances, for offline batch-cost models
 // (tools/batch_cost.py)
 static void dump_batches(const ShdPe* pe, const std::vector<int32_t>& order,
                          const std::vector<int32_t>& dbg, int32_t nB, int32_t LB) {
@@ -825,6 +826,11 @@ static void dump_batches(const ShdPe* pe, const std::vector<int32_t>& order,
     const int64_t nOff = (int64_t)pe->rowOff.size();
     std::fwrite(&nOff, 8, 1, fp);
     std::fwrite(pe->rowOff.data(), 8, pe->rowOff.size(), fp);
+    // batch order 2: the hub-group distances and the latency unit of batch_order_cost
+    const int32_t nGroups = pe->hubGroups.G;
+    std::fwrite(&nGroups, 4, 1, fp);
+    std::fwrite(&pe->hg.meanArcLatency, 8, 1, fp);
+    std::fwrite(pe->hubGroups.dist.data(), 8, pe->hubGroups.dist.size(), fp);
     std::fclose(fp);
 }
 
@@ -1079,7 +1085,10 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     const BatchLaunch& relax = relax_launch(sh, trial);
     int32_t nB = 0;
     const std::vector<int32_t> order =
-        batchOrder ? *batchOrder : batch_order(pe->rank, pe->rowOff, relax.lb, pos, cnt, nB);
+        batchOrder ? *batchOrder
+        : !pe->hubGroups.empty()
+            ? batch_order_cost(pe->rank, pe->rowOff, pe->hubGroups, pe->hg.meanArcLatency, relax.lb, pos, cnt, nB)
+            : batch_order(pe->rank, pe->rowOff, relax.lb, pos, cnt, nB);
     nB = (int32_t)(order.size() / (size_t)relax.lb);
     HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
     if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));

@@ -14,6 +14,7 @@
 
 #include "pe_device.hpp"
 #include "pe_graph.hpp"
+#include "pe_plan.hpp"
 #include "shd_pathengine.h"
 
 namespace shdpe {
@@ -121,7 +122,8 @@ struct ShdPe {
     int mode = 1;
     bool batched = false;
     std::vector<int32_t> rank;       // table position -> batch order rank
-    std::vector<double> rowOff;      // table position -> distance to its batch hub (order 1)
+    std::vector<double> rowOff;      // table position -> distance to its batch hub (orders 1, 2)
+    shdpe::HubGroups hubGroups;      // batch order 2: what batch_order_cost predicts from
     std::vector<int32_t> devOf;      // caller vertex id -> device id (empty: identity)
     int G = 1;                       // global row shards
     std::vector<int32_t> bounds;     // G + 1 position bounds

@@ -3,10 +3,13 @@
 #include "pe_plan.hpp"
 
 #include <algorithm>
+#include <atomic>
 #include <climits>
 #include <cmath>
 #include <functional>
 #include <queue>
+#include <system_error>
+#include <thread>
 #include <utility>
 
 namespace shdpe {
@@ -78,34 +81,127 @@ HostGraph relabel_graph(const HostGraph& g, const std::vector<int32_t>& oldOf) {
     return r;
 }
 
+// Multi-source Dijkstra over the out-arcs from the hubs byDeg[first],
+// byDeg[first + step], ... below K: every vertex's distance to its closest
+// hub and that hub's rank (equal distances: the lower rank).
+static void hub_dijkstra(const HostGraph& g, const std::vector<int32_t>& byDeg, int32_t first, int32_t step,
+                         int32_t K, std::vector<double>& dist, std::vector<int32_t>& owner) {
+    dist.assign(g.n, INFINITY);
+    owner.assign(g.n, INT32_MAX);
+    typedef std::pair<double, int32_t> QE;
+    std::priority_queue<QE, std::vector<QE>, std::greater<QE>> q;
+    for (int32_t k = first; k < K; k += step) { dist[byDeg[k]] = 0.0; owner[byDeg[k]] = k; q.push({0.0, byDeg[k]}); }
+    while (!q.empty()) {
+        const QE top = q.top();
+        q.pop();
+        const int32_t u = top.second;
+        if (top.first > dist[u]) continue;
+        for (int32_t a = g.rowPtr[u]; a < g.rowPtr[u + 1]; ++a) {
+            const int32_t v = g.col[a];
+            const double nd = dist[u] + g.lat[a];
+            if (nd < dist[v] || (nd == dist[v] && owner[u] < owner[v])) {
+                dist[v] = nd;
+                owner[v] = owner[u];
+                q.push({nd, v});
+            }
+        }
+    }
+}
+
+static int32_t hub_count(const HostGraph& g) {
+    return (int32_t)std::max<int64_t>(1, std::min<int64_t>(256, g.n / 400));
+}
+
+HubGroups hub_group_distances(const HostGraph& g, const std::vector<int32_t>& attached, int threads) {
+    HubGroups out;
+    out.G = HUB_GROUPS;
+    const size_t T = attached.size();
+    out.dist.assign(T * HUB_GROUPS, INFINITY);
+    out.hub.assign(T * HUB_GROUPS, INT32_MAX);
+    const int32_t K = hub_count(g);
+    const int passes = (int)std::min<int32_t>(K, HUB_GROUPS);      // groups K.. are empty
+    const std::vector<int32_t> byDeg = degree_order(g);
+    if (threads <= 0) {
+        const unsigned hw = std::thread::hardware_concurrency();
+        threads = (int)std::min<unsigned>(16, hw ? hw : 1);
+    }
+    threads = std::max(1, std::min(threads, passes));
+    // every thread takes the next pass: a pass has its own distance and owner
+    // arrays and writes only its own column of the output, so who runs it
+    // (and a thread that could not be started) changes nothing
+    std::atomic<int> next{0};
+    auto run = [&]() {
+        std::vector<double> dist;
+        std::vector<int32_t> owner;
+        for (int j; (j = next.fetch_add(1)) < passes;) {
+            hub_dijkstra(g, byDeg, j, HUB_GROUPS, K, dist, owner);
+            for (size_t p = 0; p < T; ++p) {
+                out.dist[p * HUB_GROUPS + j] = dist[attached[p]];
+                out.hub[p * HUB_GROUPS + j] = owner[attached[p]];
+            }
+        }
+    };
+    std::vector<std::thread> pool;
+    try {
+        for (int t = 1; t < threads; ++t) pool.emplace_back(run);
+    } catch (const std::system_error&) {
+    }
+    run();
+    for (std::thread& th : pool) th.join();
+    return out;
+}
+
+// Order 2: positions by (nearest hub, nearest hub of another group, the gap
+// between their distances, the nearest's distance, position); sources that
+// no hub reaches have hub INT32_MAX and so come last.
+static void rank_by_hub_groups(BatchRanks& out, size_t T) {
+    const HubGroups& hg = out.groups;
+    struct Key { int32_t h1, h2; double gap, d1; int32_t p; };
+    std::vector<Key> key(T);
+    out.rowOff.assign(T, 0.0);
+    for (size_t p = 0; p < T; ++p) {
+        const double* d = &hg.dist[p * hg.G];
+        const int32_t* h = &hg.hub[p * hg.G];
+        int j1 = -1, j2 = -1;
+        auto closer = [&](int a, int b) { return b < 0 || d[a] < d[b] || (d[a] == d[b] && h[a] < h[b]); };
+        for (int j = 0; j < hg.G; ++j) {
+            if (!std::isfinite(d[j])) continue;
+            if (closer(j, j1)) { j2 = j1; j1 = j; }
+            else if (closer(j, j2)) j2 = j;
+        }
+        Key& k = key[p];
+        k.p = (int32_t)p;
+        k.h1 = j1 >= 0 ? h[j1] : INT32_MAX;
+        k.d1 = j1 >= 0 ? d[j1] : INFINITY;
+        k.h2 = j2 >= 0 ? h[j2] : INT32_MAX;
+        k.gap = j2 >= 0 ? d[j2] - d[j1] : INFINITY;
+        if (j1 >= 0) out.rowOff[p] = d[j1];
+    }
+    std::sort(key.begin(), key.end(), [](const Key& a, const Key& b) {
+        if (a.h1 != b.h1) return a.h1 < b.h1;
+        if (a.h2 != b.h2) return a.h2 < b.h2;
+        if (a.gap != b.gap) return a.gap < b.gap;
+        if (a.d1 != b.d1) return a.d1 < b.d1;
+        return a.p < b.p;
+    });
+    out.rank.assign(T, 0);
+    for (size_t i = 0; i < T; ++i) out.rank[key[i].p] = (int32_t)i;
+}
+
 BatchRanks batch_ranks(const HostGraph& g, const std::vector<int32_t>& attached,
                        const std::vector<int32_t>& posOf, int batchOrder) {
     BatchRanks out;
+    if (batchOrder == 2) {
+        out.groups = hub_group_distances(g, attached);
+        rank_by_hub_groups(out, attached.size());
+        return out;
+    }
     std::vector<int32_t> order;
     order.reserve(g.n);
     if (batchOrder == 1) {
-        const int32_t K = (int32_t)std::max<int64_t>(1, std::min<int64_t>(256, g.n / 400));
-        const std::vector<int32_t> byDeg = degree_order(g);
-        std::vector<double> dist(g.n, INFINITY);
-        std::vector<int32_t> owner(g.n, INT32_MAX);
-        typedef std::pair<double, int32_t> QE;
-        std::priority_queue<QE, std::vector<QE>, std::greater<QE>> q;
-        for (int32_t k = 0; k < K; ++k) { dist[byDeg[k]] = 0.0; owner[byDeg[k]] = k; q.push({0.0, byDeg[k]}); }
-        while (!q.empty()) {
-            const QE top = q.top();
-            q.pop();
-            const int32_t u = top.second;
-            if (top.first > dist[u]) continue;
-            for (int32_t a = g.rowPtr[u]; a < g.rowPtr[u + 1]; ++a) {
-                const int32_t v = g.col[a];
-                const double nd = dist[u] + g.lat[a];
-                if (nd < dist[v] || (nd == dist[v] && owner[u] < owner[v])) {
-                    dist[v] = nd;
-                    owner[v] = owner[u];
-                    q.push({nd, v});
-                }
-            }
-        }
+        std::vector<double> dist;
+        std::vector<int32_t> owner;
+        hub_dijkstra(g, degree_order(g), 0, 1, hub_count(g), dist, owner);
         for (int32_t v = 0; v < g.n; ++v) order.push_back(v);
         std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) {
             return owner[a] != owner[b] ? owner[a] < owner[b] : dist[a] < dist[b];
@@ -146,10 +242,11 @@ BatchRanks batch_ranks(const HostGraph& g, const std::vector<int32_t>& attached,
     return out;
 }
 
-std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
-                                 int LB, const int32_t* pos, int32_t cnt, int32_t& nB) {
-    // pos[] stably sorted by rank: (rank, index in pos[]) packed into one
-    // integer key, so the sort compares no more than the keys themselves
+// pos[] stably sorted by rank in rows of LB, -1 pads the last row
+static std::vector<int32_t> compose_batches(const std::vector<int32_t>& rank, int LB, const int32_t* pos,
+                                            int32_t cnt, int32_t& nB) {
+    // (rank, index in pos[]) packed into one integer key, so the sort
+    // compares no more than the keys themselves
     std::vector<uint64_t> key(cnt);
     for (int32_t i = 0; i < cnt; ++i)
         key[i] = (uint64_t)((uint32_t)rank[pos[i]] ^ 0x80000000u) << 32 | (uint32_t)i;
@@ -158,6 +255,22 @@ std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::ve
     for (int32_t i = 0; i < cnt; ++i) order[i] = pos[(uint32_t)key[i]];
     nB = (cnt + LB - 1) / LB;
     order.resize((size_t)nB * LB, -1);
+    return order;
+}
+
+// The batches of order[] in the sequence of the stably sorted key[] = (key, batch)
+static void sequence_batches(std::vector<int32_t>& order, int LB, std::vector<std::pair<double, int32_t>>& key) {
+    std::stable_sort(key.begin(), key.end());
+    std::vector<int32_t> re(order.size());
+    for (size_t i = 0; i < key.size(); ++i)
+        std::copy(order.begin() + (size_t)key[i].second * LB,
+                  order.begin() + (size_t)(key[i].second + 1) * LB, re.begin() + i * LB);
+    order.swap(re);
+}
+
+std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
+                                 int LB, const int32_t* pos, int32_t cnt, int32_t& nB) {
+    std::vector<int32_t> order = compose_batches(rank, LB, pos, cnt, nB);
     if (!rowOff.empty() && nB > 1) {
         // longest batches first (workgroups take batches in order, so the last round is
         // made of short ones): a batch's cost grows with its sources' mean distance to
@@ -172,12 +285,62 @@ std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::ve
             }
             key[b] = {c ? -s / c : 0.0, b};
         }
-        std::stable_sort(key.begin(), key.end());
-        std::vector<int32_t> re((size_t)nB * LB);
-        for (int32_t i = 0; i < nB; ++i)
-            std::copy(order.begin() + (size_t)key[i].second * LB,
-                      order.begin() + (size_t)(key[i].second + 1) * LB, re.begin() + (size_t)i * LB);
-        order.swap(re);
+        sequence_batches(order, LB, key);
+    }
+    return order;
+}
+
+// Predicted arc visits of a batch in passes over the arcs, least-squares fit
+// to tools/sim/batch_sim.c's count over the 1,024 order-2 batches of C4
+// (tools/sim/plan_eval.py c4 --fit; profiles/batch_plan_cost_sim.json holds
+// the fit and its correlation, 0.945).  Only the order of the costs is used.
+static const double COST_C0 = 0.892, COST_OFF = 0.200, COST_SPREAD = 3.363;
+
+std::vector<int32_t> batch_order_cost(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
+                                      const HubGroups& groups, double meanArcLatency, int LB,
+                                      const int32_t* pos, int32_t cnt, int32_t& nB, std::vector<double>* cost) {
+    std::vector<int32_t> order = compose_batches(rank, LB, pos, cnt, nB);
+    const double unit = meanArcLatency > 0.0 && std::isfinite(meanArcLatency) ? meanArcLatency : 1.0;
+    const int G = groups.G;
+    std::vector<std::pair<double, int32_t>> key(nB);
+    std::vector<double> sum(G), sumSq(G);
+    std::vector<int> cntOf(G);
+    for (int32_t b = 0; b < nB; ++b) {
+        std::fill(sum.begin(), sum.end(), 0.0);
+        std::fill(sumSq.begin(), sumSq.end(), 0.0);
+        std::fill(cntOf.begin(), cntOf.end(), 0);
+        double off = 0.0;
+        int lanes = 0;
+        for (int l = 0; l < LB; ++l) {
+            const int32_t p = order[(size_t)b * LB + l];
+            if (p < 0) continue;
+            ++lanes;
+            off += rowOff[p];
+            for (int j = 0; j < G; ++j) {
+                const double d = groups.dist[(size_t)p * G + j];
+                if (!std::isfinite(d)) continue;
+                const double x = (d - rowOff[p]) / unit;
+                sum[j] += x;
+                sumSq[j] += x * x;
+                ++cntOf[j];
+            }
+        }
+        double var = 0.0;
+        int terms = 0;
+        for (int j = 0; j < G; ++j) {
+            if (!cntOf[j]) continue;
+            var += std::max(0.0, sumSq[j] - sum[j] * sum[j] / cntOf[j]);
+            terms += cntOf[j];
+        }
+        const double spread = terms ? std::sqrt(var / terms) : 0.0;
+        const double meanOff = lanes ? off / lanes / unit : 0.0;
+        const double c = (COST_C0 + COST_OFF * meanOff + COST_SPREAD * spread) * lanes / LB;
+        key[b] = {-c, b};
+    }
+    if (nB > 1) sequence_batches(order, LB, key);
+    if (cost) {
+        cost->resize(nB);
+        for (int32_t b = 0; b < nB; ++b) (*cost)[b] = -key[b].first;
     }
     return order;
 }

@@ -56,3 +56,29 @@ def combined(relax, post, G=512):
         t,k=heapq.heappop(hq); s=max(t,fin); e=s+post[b]; end=max(end,e); heapq.heappush(hq,(e,k))
     return end
 print('sequential %.1fM  combined %.1fM  lower bound %.1fM'%((makespan(relax)+makespan(post))/1e6, combined(relax,post)/1e6, (relax.sum()+post.sum())/512/1e6))
+# batch order 2 (the dump carries the hub-group distances): batch_order_cost's
+# prediction (constants of pe_plan.cpp) against the measured cycles, and the
+# take as dumped (predicted-cost order) against the ideal and the true-cost order
+o+=8*nOff; nG=0
+if len(b)>o+12:
+    nG=int(np.frombuffer(b[o:o+4],np.int32)[0]); unit=np.frombuffer(b[o+4:o+12],np.float64)[0]; o+=12
+if len(b)>o and nG>0:
+    dist=np.frombuffer(b[o:o+8*nOff*nG],np.float64).reshape(nOff,nG)
+    C0,COFF,CSPREAD=0.892,0.200,3.363
+    x=np.where((order>=0)[:,:,None], (dist-off[:,None])[np.maximum(order,0)]/unit, np.nan)   # [nB][LB][nG]
+    x=np.where(np.isfinite(x),x,np.nan)
+    dev=x-np.nanmean(x,axis=1,keepdims=True)
+    spread=np.sqrt(np.nansum(dev**2,axis=(1,2))/np.maximum(1,np.isfinite(x).sum(axis=(1,2))))
+    moff=np.nanmean(offb,1)/unit
+    lanes=(order>=0).sum(1)
+    pred=(C0+COFF*moff+CSPREAD*spread)*lanes/LB
+    print('order 2: predicted cost corr relax %.3f post %.3f | spread alone %.3f %.3f | mean offset alone %.3f %.3f'%(
+        np.corrcoef(pred,relax)[0,1],np.corrcoef(pred,post)[0,1],np.corrcoef(spread,relax)[0,1],
+        np.corrcoef(spread,post)[0,1],np.corrcoef(moff,relax)[0,1],np.corrcoef(moff,post)[0,1]))
+    X=np.column_stack([np.ones(nB),moff,spread])
+    for nm,y in (('relax',relax),('post',post)):
+        coef,*_=np.linalg.lstsq(X,y/y.mean(),rcond=None)
+        print('  refit on',nm,'cycles / mean: c0 %.3f off %.3f spread %.3f, corr %.3f'%(*coef,np.corrcoef(X@coef,y)[0,1]))
+    for nm,y,G in (('relax',relax,256),('post',post,512)):
+        print('  %s P=%d: as dumped %.1fM  by true cost %.1fM  ideal %.1fM  (max/mean batch %.2f)'%(
+            nm,G,makespan(y,G)/1e6,makespan(np.sort(y)[::-1],G)/1e6,y.sum()/G/1e6,y.max()/y.mean()))
