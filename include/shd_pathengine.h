@@ -36,8 +36,9 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 8   /* 7: graph property check (shd_pe_graph_props);
-                                  8: fill from row shards (shd_pe_fill_rowstore_shards) */
+#define SHD_PE_ABI_VERSION 9   /* 7: graph property check (shd_pe_graph_props);
+                                  8: fill from row shards (shd_pe_fill_rowstore_shards);
+                                  9: shd_pe_pred_filter_counts */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -451,6 +452,11 @@ int shd_pe_get_stats(const ShdPe* pe, ShdPeStats* out);
 int shd_pe_get_stats_sized(const ShdPe* pe, void* out, int64_t outBytes);
 int64_t shd_pe_stats_size(void);
 int shd_pe_reset_stats(ShdPe* pe);
+/* SHD_PE_DEBUG_COUNTERS only (else both 0), cumulative like the stats and
+ * reset with them: the in-arcs of the entries the batched post kernel's
+ * on-demand predecessor pass claimed, and the in-arcs it gathered -- equal
+ * without the predecessor filter, fewer where the relax flagged in-arcs. */
+int shd_pe_pred_filter_counts(const ShdPe* pe, int64_t* claimed, int64_t* gathered);
 
 /* ---- batched helpers on the device ------------
  * The per-query lookups below, for many queries in one call: inputs and

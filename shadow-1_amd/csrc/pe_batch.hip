@@ -90,6 +90,9 @@ struct alignas(16) BCtrl {
     unsigned int dWhy;   // SHDPE_DIAG_WHY builds: why the batch's rows left the fast path
     long long t0, t1, t2, t3, t4;
     int pubCnt;          // cooperative relax: near bits this member published this phase
+    // SHD_PE_DEBUG_COUNTERS only: in-arcs of the entries the on-demand
+    // predecessor pass claimed, and the in-arcs it gathered (the filter)
+    unsigned int dClaim, dGath;
 };
 static_assert(sizeof(BCtrl) <= 128, "batch control block");
 constexpr int BCTRL_BYTES = 128;
@@ -374,6 +377,8 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
     // instantiation, so the plain relax keeps its code and register budget
     constexpr bool CO = PART == 3;
     constexpr bool NOTAB = PART == 4;
+    // the plain relax with LDS bitmaps flags in-arcs for the predecessor filter
+    constexpr bool HITS = PART == 1 && !GB;
     constexpr int PT = CO ? 1 : NOTAB ? 2 : PART;
     constexpr int BV = BCfg<WPE>::BV;
     constexpr int SMAX = BCfg<WPE>::SMAX;
@@ -444,6 +449,21 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         const int src = row >= 0 ? g.attached[row] : -1;
         if (gid == 0) laneRow[l] = row;
         if constexpr (PT != 0) D = as_global(bs.D + (size_t)b * SE);
+        // predecessor filter (split kernels): the batch's in-arc flags, one
+        // bit per in-arc slot -- the relax sets bit outToIn[a] when some active
+        // lane's pre-check of arc a finds dist[u] + w <= dist[x] (every arc
+        // that is tight, or violated, in the final state: DESIGN.md §5), the
+        // on-demand predecessor pass gathers the flagged in-arcs only.  The
+        // relax keeps the bits in LDS behind the pending bitmaps (hitLds: they
+        // fit) and writes them out once, at the end of the batch, with bit 1
+        // of the batch's flag word; without that bit the pass reads every
+        // in-arc.  (Flag stores to HBM from the relax loop cost it three times
+        // what the pass gains: DESIGN.md §7.)
+        uint32_t* AHw = nullptr;
+        if constexpr (PT != 0)
+            if (bs.arcHit) AHw = as_global(bs.arcHit) + (size_t)b * (size_t)(bs.mStride >> 5);
+        uint32_t* const hb = reinterpret_cast<uint32_t*>(smem + BCTRL_BYTES + 8 * nwp);
+        const bool hits = HITS && AHw != nullptr && bs.hitLds != 0;
         // ---- init: dist = +inf (clean) for all (v, lane); pending sets empty ----
         {
             ulonglong2* D2 = reinterpret_cast<ulonglong2*>(D);
@@ -453,6 +473,11 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 // (cooperative: each member its slice of the shared array)
                 const size_t i0 = cnt2 * coMember / coK, i1 = cnt2 * (coMember + 1) / coK;
                 for (size_t i = i0 + tid; i < i1; i += NT) D2[i] = inf2;
+                if (hits) {     // no in-arc flagged yet (mStride is a multiple of 128 bits)
+                    uint4* const H4 = reinterpret_cast<uint4*>(hb);
+                    const int cnt16 = (int)(bs.mStride >> 7);
+                    for (int i = tid; i < cnt16; i += NT) H4[i] = make_uint4(0u, 0u, 0u, 0u);
+                }
             }
             for (int w = tid; w < nwp; w += NT) { any0.st(w, 0u); any1.st(w, 0u); }
             if (tid == 0) {
@@ -468,6 +493,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 ctl->maxOff = 0.0;
                 ctl->dProcs = ctl->dArcs = ctl->dLanes = 0u;
                 ctl->dWhy = 0u;
+                ctl->dClaim = ctl->dGath = 0u;
                 ctl->pubCnt = 0;
             }
         }
@@ -508,7 +534,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         const int phaseCap = 8 * n + 1024;
         double bound = delta;
         unsigned long long myFar = INF_BITS;      // smallest far key this thread added
-        if constexpr (PT == 2) failed = as_global(bs.flags)[b] != 0;
+        if constexpr (PT == 2) failed = (as_global(bs.flags)[b] & 1) != 0;
 #ifdef SHDPE_DIAG_WHY
         uint32_t why = failed ? 128u : 0u;
         __shared__ int sDiagViol;
@@ -685,7 +711,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                         atomicAdd(&ctl->dLanes, (unsigned int)__popc(amask));
                     }
                     for (int t = a0 + gw * BK; t < a1; t += GPW * BK) {
-                        int xs[BK];
+                        int xs[BK], rs[BK];
                         double ws[BK];
                         unsigned long long dx[BK];
 #pragma unroll
@@ -695,6 +721,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                             const Arc A = g.arcs[ok ? a : 0];
                             xs[k] = ok ? A.col : -1;
                             ws[k] = A.lat;
+                            rs[k] = A.pad;
                         }
 #pragma unroll
                         for (int k = 0; k < BK; ++k)
@@ -702,10 +729,11 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
 #pragma unroll
                         for (int k = 0; k < BK; ++k) {
                             const int x = xs[k];
-                            bool impN = false, impF = false;
+                            bool impN = false, impF = false, hit = false;
                             if (x >= 0) {
                                 const double nd = b2d(dub1) + ws[k];
                                 const unsigned long long nb = d2b(nd);
+                                hit = act && nb <= dec(dx[k]);
                                 if (nb < dec(dx[k])) {
                                     relax_min<CO>(&D[(size_t)x * LB + l], enc_dirty(nb));
                                     const double kx = nd + sh;
@@ -715,12 +743,17 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                                 }
                             }
                             const uint64_t bn = __ballot(impN), bf = __ballot(impF);
+                            uint64_t bh = 0;
+                            if constexpr (HITS) bh = __ballot(hit);
                             if (l == 0) {
                                 if ((bn >> gbase) & LBMASK) anyC.set(x);
                                 if ((bf >> gbase) & LBMASK) {
                                     anyF.set(x);
                                     farAdd = 1;
                                 }
+                                // tight or improving in some lane: flag the in-arc
+                                if constexpr (HITS)
+                                    if (hits && ((bh >> gbase) & LBMASK)) atomicOr(&hb[rs[k] >> 5], 1u << (rs[k] & 31));
                             }
                         }
                     }
@@ -759,13 +792,14 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 r0 = uu >= 0 ? x0 : 0;
                 r1 = uu >= 0 ? x1 : 0;
             };
-            auto ld_arc = [&](int a, int aEnd, int& c, double& w) {
+            auto ld_arc = [&](int a, int aEnd, int& c, double& w, int& r) {
                 const bool ok = a < aEnd;
                 const Arc A = g.arcs[ok ? a : 0];
                 c = ok ? A.col : -1;
                 w = A.lat;
+                r = A.pad;      // the arc's slot in its head's in-list (same 16-B record)
             };
-            int uC[BV], u1[BV], u2[BV], a0C[BV], a1C[BV], a01[BV], a11[BV], mcC[BV];
+            int uC[BV], u1[BV], u2[BV], a0C[BV], a1C[BV], a01[BV], a11[BV], mcC[BV], mrC[BV];
             unsigned long long dbC[BV], db1[BV];
             double mlC[BV];
             {
@@ -783,13 +817,13 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 ld_head(u1[v], db1[v], a01[v], a11[v]);
             }
 #pragma unroll
-            for (int v = 0; v < BV; ++v) ld_arc(a0C[v] + l, a1C[v], mcC[v], mlC[v]);
+            for (int v = 0; v < BV; ++v) ld_arc(a0C[v] + l, a1C[v], mcC[v], mlC[v], mrC[v]);
             while (uC[0] >= 0) {
-                int mc1[BV], a02[BV], a12[BV], u3[BV];
+                int mc1[BV], mr1[BV], a02[BV], a12[BV], u3[BV];
                 double ml1[BV];
                 unsigned long long db2[BV];
 #pragma unroll
-                for (int v = 0; v < BV; ++v) ld_arc(a01[v] + l, a11[v], mc1[v], ml1[v]);
+                for (int v = 0; v < BV; ++v) ld_arc(a01[v] + l, a11[v], mc1[v], ml1[v], mr1[v]);
 #pragma unroll
                 for (int v = 0; v < BV; ++v) ld_head(u2[v], db2[v], a02[v], a12[v]);
                 {
@@ -825,15 +859,19 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 }
                 // relax the out-arcs for the dirty lanes below the bound
                 for (int c0 = 0; c0 < maxd; c0 += LB) {
-                    int mc[BV];
+                    int mc[BV], mr[BV];
                     double ml[BV];
 #pragma unroll
                     for (int v = 0; v < BV; ++v) {
                         mc[v] = mcC[v];
                         ml[v] = mlC[v];
-                        if (c0 > 0) ld_arc(a0C[v] + c0 + l, a0C[v] + deg[v], mc[v], ml[v]);   // degree > LB
+                        mr[v] = mrC[v];
+                        if (c0 > 0) ld_arc(a0C[v] + c0 + l, a0C[v] + deg[v], mc[v], ml[v], mr[v]);   // degree > LB
                     }
                     const int cn = min(LB, maxd - c0);
+                    uint32_t hacc[BV];      // the chunk's arcs with a hit in some lane
+#pragma unroll
+                    for (int v = 0; v < BV; ++v) hacc[v] = 0u;
                     for (int t = 0; t < cn; t += BKR) {
                         int xs[BV][BKR];
                         double ws[BV][BKR];
@@ -857,10 +895,11 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
 #pragma unroll
                             for (int k = 0; k < BKR; ++k) {
                                 const int x = xs[v][k];
-                                bool impN = false, impF = false;
+                                bool impN = false, impF = false, hit = false;
                                 if (x >= 0) {
                                     const double nd = b2d(dub[v]) + ws[v][k];
                                     const unsigned long long nb = d2b(nd);
+                                    hit = dub[v] != INF_BITS && nb <= dec(dx[v][k]);
                                     if (nb < dec(dx[v][k])) {
                                         relax_min<CO>(&D[(size_t)x * LB + l], enc_dirty(nb));
                                         const double kx = nd + sh;
@@ -877,13 +916,24 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                                         farAdd = 1;
                                     }
                                 }
+                                if constexpr (HITS) {      // (branch-free: `hits` gates the store below)
+                                    const uint64_t bh = __ballot(hit);
+                                    hacc[v] |= (bh >> gbase) & LBMASK ? 1u << ((t + k) & 31) : 0u;
+                                }
                             }
+                    }
+                    // tight or improving in some lane: the lane that holds the
+                    // arc's record flags its in-arc slot (once per chunk)
+                    if constexpr (HITS) {
+#pragma unroll
+                        for (int v = 0; v < BV; ++v)
+                            if (hits && ((hacc[v] >> l) & 1u)) atomicOr(&hb[mr[v] >> 5], 1u << (mr[v] & 31));
                     }
                 }
 #pragma unroll
                 for (int v = 0; v < BV; ++v) {
                     uC[v] = u1[v]; dbC[v] = db1[v]; a0C[v] = a01[v]; a1C[v] = a11[v];
-                    mcC[v] = mc1[v]; mlC[v] = ml1[v];
+                    mcC[v] = mc1[v]; mlC[v] = ml1[v]; mrC[v] = mr1[v];
                     u1[v] = u2[v]; db1[v] = db2[v]; a01[v] = a02[v]; a11[v] = a12[v];
                     u2[v] = u3[v];
                 }
@@ -939,6 +989,10 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
             const int stackB = NT * SMAX * 8, bitsB = GB ? 0 : 8 * nwp;
             const int hcap = min(4096, max(0, stackB - bitsB) / 4);
             int lo = 0, hi = n;
+            // the on-demand pass gathers only the in-arcs the relax flagged (a
+            // superset of the tight ones); the full pass reads every in-arc
+            bool filt = false;
+            if constexpr (PT == 2) filt = !fullPred && AHw != nullptr && (as_global(bs.flags)[b] & 2) != 0;
             if (!fullPred) {
                 for (int j = tid; j < g.T; j += NT) {
                     const int v = g.attached[j];
@@ -968,9 +1022,13 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 r0 = vv >= 0 ? x0 : 0;
                 r1 = vv >= 0 ? x1 : 0;
             };
+            // (filtered pass: an in-arc the relax did not flag reads as absent
+            // -- its flag bit is loaded beside its record, one or two words
+            // per group)
             auto ld_rec = [&](int a, int aEnd, int& c, double& w) {
-                const bool ok = a < aEnd;
+                bool ok = a < aEnd;
                 const int ac = ok ? a : 0;
+                if (filt) ok = ok && ((AHw[ac >> 5] >> (ac & 31)) & 1u) != 0;
                 if (undirected) {
                     const Arc A = g.arcs[ac];
                     c = A.col;
@@ -1021,6 +1079,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                     bu[v] = -1;
                     deg[v] = vC[v] >= 0 ? a1C[v] - a0C[v] : 0;   // group-uniform
                     hvy[v] = false;
+                    if (dbg && !fullPred && l == 0 && deg[v]) atomicAdd(&ctl->dClaim, (unsigned int)deg[v]);
                     if (deg[v] >= PRED_HEAVY) {                   // -> the round's wave pass
                         int slot = 0;
                         if (l == 0) slot = atomicAdd(&ctl->htail, 1);
@@ -1042,20 +1101,38 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                         ml[v] = mlC[v];
                         if (c0 > 0) ld_rec(a0C[v] + c0 + l, a0C[v] + deg[v], mc[v], ml[v]);
                     }
-                    const int cn = min(LB, maxd - c0);
-                    for (int t = 0; t < cn; t += BKQ) {
-                        int cu[BV][BKQ];
+                    // the chunk's records to gather: those present (in the
+                    // filtered pass, flagged), as a mask over the group's lanes;
+                    // the gather rounds walk its set bits in in-list order
+                    uint32_t hm[BV], hany = 0u;
+#pragma unroll
+                    for (int v = 0; v < BV; ++v) {
+                        const int rem = deg[v] - c0;
+                        const uint32_t dm = rem >= LB ? LBMASK : rem > 0 ? (1u << (rem & 31)) - 1u : 0u;
+                        hm[v] = (uint32_t)(__ballot(mc[v] >= 0) >> gbase) & dm;
+                        if (dbg && !fullPred && l == 0 && hm[v]) atomicAdd(&ctl->dGath, (unsigned int)__popc(hm[v]));
+                        hany |= hm[v];
+                    }
+                    while (hany) {
+                        int cu[BV][BKQ], jj[BV][BKQ];
                         double lw[BV][BKQ];
                         unsigned long long du[BV][BKQ];
+                        hany = 0u;
 #pragma unroll
-                        for (int v = 0; v < BV; ++v)
+                        for (int v = 0; v < BV; ++v) {
 #pragma unroll
                             for (int k = 0; k < BKQ; ++k) {
-                                const int srcL = gbase + min(t + k, LB - 1);
+                                const bool on = hm[v] != 0u;
+                                const int j = on ? __ffs(hm[v]) - 1 : 0;
+                                hm[v] &= hm[v] - 1u;
+                                const int srcL = gbase + j;
                                 const int c = __shfl(mc[v], srcL, 64);
                                 lw[v][k] = __shfl(ml[v], srcL, 64);
-                                cu[v][k] = t + k < cn && c0 + t + k < deg[v] ? c : -1;   // (a repeat would count as a tie)
+                                cu[v][k] = on ? c : -1;   // (a repeat would count as a tie)
+                                jj[v][k] = j;
                             }
+                            hany |= hm[v];
+                        }
 #pragma unroll
                         for (int v = 0; v < BV; ++v)
 #pragma unroll
@@ -1076,7 +1153,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                                     if (du[v][k] < best[v]) {
                                         best[v] = du[v][k];
                                         cnt[v] = 1;
-                                        ba[v] = a0C[v] + c0 + t + k;
+                                        ba[v] = a0C[v] + c0 + jj[v][k];
                                         bu[v] = cu[v][k];
                                     } else if (du[v][k] == best[v]) {
                                         ++cnt[v];
@@ -1143,8 +1220,9 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                         double ml;
                         {
                             const int a = a0 + c0 + l;
-                            const bool ok = a < a1;
+                            bool ok = a < a1;
                             const int ac = ok ? a : 0;
+                            if (filt) ok = ok && ((AHw[ac >> 5] >> (ac & 31)) & 1u) != 0;
                             if (undirected) {
                                 const Arc A = g.arcs[ac];
                                 mc = A.col;
@@ -1155,17 +1233,23 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                             }
                             mc = ok ? mc : -1;
                         }
-                        const int cn = min(LB, deg - c0);
-                        for (int t = 0; t < cn; t += BKQ) {
-                            int cu[BKQ];
+                        // (the same mask walk as the groups' scan, per wave chunk)
+                        uint32_t hm = (uint32_t)(__ballot(mc >= 0) >> gbase) & LBMASK;
+                        if (dbg && !fullPred && l == 0 && hm) atomicAdd(&ctl->dGath, (unsigned int)__popc(hm));
+                        while (hm) {
+                            int cu[BKQ], jj[BKQ];
                             double lw[BKQ];
                             unsigned long long du[BKQ];
 #pragma unroll
                             for (int k = 0; k < BKQ; ++k) {
-                                const int srcL = gbase + min(t + k, LB - 1);
+                                const bool on = hm != 0u;
+                                const int j = on ? __ffs(hm) - 1 : 0;
+                                hm &= hm - 1u;
+                                const int srcL = gbase + j;
                                 const int c = __shfl(mc, srcL, 64);
                                 lw[k] = __shfl(ml, srcL, 64);
-                                cu[k] = t + k < cn ? c : -1;
+                                cu[k] = on ? c : -1;
+                                jj[k] = j;
                             }
 #pragma unroll
                             for (int k = 0; k < BKQ; ++k) {
@@ -1183,7 +1267,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                                     if (du[k] < best) {
                                         best = du[k];
                                         cnt = 1;
-                                        ba = a0 + c0 + t + k;
+                                        ba = a0 + c0 + jj[k];
                                         bu = cu[k];
                                     } else if (du[k] == best) {
                                         ++cnt;
@@ -1263,7 +1347,17 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         ++repairs;
         }   // verification loop
         if constexpr (PT == 1) {
-            if (tid == 0 && coMember == 0) as_global(bs.flags)[b] = failed ? 1 : 0;
+            // the batch's in-arc flags, LDS -> HBM (bit 1 of the flag word: written)
+            if constexpr (HITS)
+                if (hits) {
+                    fence_wg();
+                    __syncthreads();
+                    const uint4* const H4 = reinterpret_cast<const uint4*>(hb);
+                    uint4* const G4 = reinterpret_cast<uint4*>(AHw);
+                    const int cnt16 = (int)(bs.mStride >> 7);
+                    for (int i = tid; i < cnt16; i += NT) G4[i] = H4[i];
+                }
+            if (tid == 0 && coMember == 0) as_global(bs.flags)[b] = (failed ? 1 : 0) | (hits ? 2 : 0);
             break;
         }
         if (dbg && tid == 0) ctl->t2 = (long long)clock64();
@@ -1650,6 +1744,10 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
             dbg[16 * b + 6] = (int)((ctl->t2 - ctl->t1) >> 10);
             dbg[16 * b + 7] = (int)((ctl->t3 - ctl->t2) >> 10);
             dbg[16 * b + 11] = (int)((ctl->t4 - ctl->t3) >> 10);
+            if (bs.predCnt) {       // the on-demand pass's in-arcs: claimed, gathered
+                atomicAdd(as_global(bs.predCnt), (unsigned long long)ctl->dClaim);
+                atomicAdd(as_global(bs.predCnt) + 1, (unsigned long long)ctl->dGath);
+            }
         }
         fence_wg();
         __syncthreads();
@@ -1879,6 +1977,15 @@ int batch_lds_bytes(int n, int wpe, bool gbits) {
 
 int64_t batch_bits_words(int n) { return 2 * (int64_t)((((n + 31) >> 5) + 3) & ~3); }
 
+// predecessor filter: the plain relax of this variant flags in-arcs when a
+// batch's bits fit in its LDS behind the pending bitmaps (C4: 75 KB in the
+// 4-wave variant's 128 KB, not in the 6- and 8-wave variants' 49 / 64 KB);
+// behind any other relax the post kernel reads every in-arc
+bool batch_relax_flags(const BatchScratch& bs, const BatchLaunch& cfg, int n) {
+    return bs.arcHit && !cfg.gbits && cfg.split && cfg.coop < 2 &&
+           (int64_t)BCTRL_BYTES + 4 * batch_bits_words(n) + bs.mStride / 8 <= (int64_t)cfg.ldsBytes;
+}
+
 template <int WPE, int PART>
 static const void* kptr(int lb, bool gb) {
     if (gb) return reinterpret_cast<const void*>(&k_batch_rows<16, WPE, true, PART>);
@@ -1932,12 +2039,14 @@ void launch_batch_rows(const DevGraph& g, const DevTable& tab, const BatchScratc
     const int grid = nBatches < cfg.grid ? nBatches : cfg.grid;
     if (grid <= 0) return;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    BatchScratch bsl = bs;
+    bsl.hitLds = part == 1 && batch_relax_flags(bs, cfg, g.n);
     if (cfg.wpe >= 8)
-        launch_wp<8>(g, tab, bs, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid, part);
+        launch_wp<8>(g, tab, bsl, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid, part);
     else if (cfg.wpe == 6)
-        launch_wp<6>(g, tab, bs, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid, part);
+        launch_wp<6>(g, tab, bsl, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid, part);
     else
-        launch_wp<4>(g, tab, bs, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid, part);
+        launch_wp<4>(g, tab, bsl, dBatchRows, nBatches, dRowAmbig, cfg, dDbg, tie, st, grid, part);
 }
 
 }  // namespace shdpe

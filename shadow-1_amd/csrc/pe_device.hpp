@@ -22,7 +22,7 @@ namespace shdpe {
 struct alignas(16) Arc {
     double lat;
     int32_t col;
-    int32_t pad;
+    int32_t pad;             // DevGraph::arcs: outToIn of the arc (its slot in the head's in-list)
 };
 
 // 12-byte packed arc (col, lat as two dwords): one global_load_dwordx3 per
@@ -164,6 +164,8 @@ struct Tuning {
     int pathsGroup = 0;        // shd_pe_get_paths: sources per emulation group (0: exactGrid)
     int pathsChunk = 0;        // ... requests per staging chunk (0: 65,536)
     int pathsFast = 1;         // ... 0: no batch / tie tier, every source by the grouped emulation
+    int predFilter = 1;        // on-demand predecessor pass reads only the in-arcs the relax
+                               // flagged (0: every in-arc, BatchScratch::arcHit stays null)
     int failWpe = 0;           // tests only: the relax variant of this wave count flags
                                // every batch failed (a miscompiled variant; shd_pe_tune
                                // must not pick it)
@@ -203,7 +205,8 @@ struct BatchScratch {
     int32_t* next;           // next batch to take (device counter, zeroed per launch)
     int64_t nStride;         // >= n, multiple of 64
     uint32_t* bits;          // [slot][2 * words] pending bitmaps when they exceed LDS (gbits)
-    int32_t* flags;          // split kernels: per batch of the round, 1 = phase cap hit
+    int32_t* flags;          // split kernels: per batch of the round, bit 0 = phase cap hit,
+                             // bit 1 = the relax wrote the batch's arcHit bits
     const double* rowOff;    // [T] per table position: the source's distance to its
                              // batch hub (bucket key offset; null = no offsets)
     // cooperative relax (PART 3 of k_batch_rows): K workgroups of one XCD
@@ -216,6 +219,19 @@ struct BatchScratch {
     unsigned long long* coPubS;   // [group][2][K][2] published near count | far flag, far min
     int32_t coK;             // members per group (PART 3 only)
     int32_t coSpin;          // barrier poll limit (s_sleep 1 each)
+    // predecessor filter (split kernels): one bit per in-arc slot -- inPtr /
+    // inCol order when directed, the head's own row when undirected -- set by
+    // the relax when some lane's pre-check of the arc found dist[u] + w <=
+    // dist[x]; the post kernel's on-demand predecessor pass gathers only the
+    // flagged in-arcs.  Null: no filter (every in-arc is gathered).  The
+    // relax collects a batch's bits in LDS and writes them out at its end
+    // (bit 1 of flags[batch]); launch_batch_rows sets hitLds when they fit
+    // behind the pending bitmaps in the variant's LDS.
+    uint32_t* arcHit;        // [batch of the round][mStride / 32]
+    int64_t mStride;         // bits per batch: >= in-arcs, multiple of 128
+    int32_t hitLds;          // set per launch (the relax of this variant flags in-arcs)
+    unsigned long long* predCnt;   // SHD_PE_DEBUG_COUNTERS only (else null): [0] in-arcs of the
+                             // entries the on-demand pass claimed, [1] in-arcs it gathered
 };
 
 struct BatchLaunch {
@@ -344,6 +360,8 @@ void launch_tie_export(const DevGraph& g, const BatchScratch& bs, int lb, const 
                        int round, uint8_t* dRowAmbig, int grid, int violSlot, void* stream);
 int batch_threads(int wpe);    // workgroup size of a variant (6 waves: 768, else 1024)
 int64_t batch_bits_words(int n);   // per slot, both bitmaps
+// whether the relax launched as `cfg` flags in-arcs for the predecessor filter
+bool batch_relax_flags(const BatchScratch& bs, const BatchLaunch& cfg, int n);
 // batched helpers (pe_aux.hip), all on `stream`
 void launch_self_paths(const DevGraph& g, const int32_t* dVerts, int32_t count, int64_t nEdges,
                        double* dLat, double* dRel, uint8_t* dFlags, void* stream);

@@ -87,6 +87,7 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_DEBUG", t.debug);
     gi("SHDPE_STREAM_WG_PER_CU", t.streamWgPerCU);
     gi("SHDPE_TIE_CORRUPT", t.tieCorrupt);
+    gi("SHDPE_PRED_FILTER", t.predFilter);
     gi("SHDPE_TUNE_FAIL_WPE", t.failWpe);
     gi("SHDPE_TUNE_LOG", t.tuneLog);
     gi("SHDPE_BATCH_COOP", t.batchCoop);
@@ -395,7 +396,9 @@ static int upload_graph(const HostGraph& g, const std::vector<int32_t>& attached
     up(d.attached, attached); up(d.isAttached, isAtt);
     {
         std::vector<Arc> arcs(g.col.size());
-        for (size_t a = 0; a < arcs.size(); ++a) arcs[a] = Arc{g.lat[a], g.col[a], 0};
+        // (pad = the arc's slot in its head's in-list: the batched relax flags
+        // that slot for the predecessor filter without a second load)
+        for (size_t a = 0; a < arcs.size(); ++a) arcs[a] = Arc{g.lat[a], g.col[a], g.outToIn[a]};
         up(d.arcs, arcs);
         std::vector<Arc3> a3(g.col.size());
         for (size_t a = 0; a < a3.size(); ++a) {
@@ -683,11 +686,15 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     // (at most 160 GiB of dist arrays: C4 one round of 13 GB, C5 one round
     // of 131 GB beside its 107 GB table -- 2 rounds under a 96 GiB cap were
     // 5% slower, profiles/r04_ab_notes.txt r04i)
+    // predecessor filter (split kernels): one flag bit per in-arc slot per
+    // batch of the round, counted with the round's dist arrays
+    const size_t mStride = ((size_t)pe->hg.nArcs() + 127) & ~(size_t)127;
+    const bool filter = plan.relax.split && pe->tu.predFilter != 0 && mStride > 0;
     size_t roundB = slots;
     if (plan.relax.split) {
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) freeB = (size_t)16 << 30;
-        const size_t perD = NS * LB * 8;
+        const size_t perD = NS * LB * 8 + (filter ? mStride / 8 : 0);
         const size_t rest = slots * (perSlot - NS * LB * 8);
         const size_t room = freeB > rest + ((size_t)12 << 30) ? freeB - rest - ((size_t)12 << 30) : perD;
         const size_t dBudget = std::min<size_t>(room, (size_t)160 << 30);
@@ -703,6 +710,13 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
         return rc;
     sh->bsc.next = sh->bsc.queue + slots * NS;
     sh->bsc.nStride = (int64_t)NS;
+    sh->bsc.arcHit = nullptr;
+    sh->bsc.mStride = (int64_t)mStride;
+    // (no room for the flags: no filter, the post kernel reads every in-arc)
+    sh->bsc.hitLds = 0;
+    if (filter && dev_alloc(sh, &sh->bsc.arcHit, roundB * (mStride / 32))) (void)hipGetLastError();
+    sh->bsc.predCnt = nullptr;
+    if (pe->tu.debug && (rc = dev_alloc(sh, &sh->bsc.predCnt, 2))) return rc;
     sh->bsc.bits = nullptr;
     if (bitBytes && (rc = dev_alloc(sh, &sh->bsc.bits, slots * bitBytes / 4))) return rc;
     sh->bsc.rowOff = nullptr;
@@ -1092,6 +1106,7 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     nB = (int32_t)(order.size() / (size_t)relax.lb);
     HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
     if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
+    if (sh->bsc.predCnt) HIPCHK(hipMemsetAsync(sh->bsc.predCnt, 0, 16, sh->stream));
     if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
     HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
     HIPCHK(hipEventRecord(sh->evA, sh->stream));
@@ -1113,6 +1128,16 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
         HIPCHK(hipMemcpy(dbg.data(), sh->dDbg, dbg.size() * 4, hipMemcpyDeviceToHost));
         print_batch_debug(pe, sh, relax, dbg.data(), nB);
         dump_batches(pe, order, dbg, nB, relax.lb);
+        if (sh->bsc.predCnt) {
+            unsigned long long pc[2] = {0, 0};
+            HIPCHK(hipMemcpy(pc, sh->bsc.predCnt, 16, hipMemcpyDeviceToHost));
+            sh->predClaimed += (int64_t)pc[0];
+            sh->predGathered += (int64_t)pc[1];
+            std::fprintf(stderr, "[shdpe] on-demand predecessor pass in-arcs/batch: claimed=%.0f gathered=%.0f "
+                         "(%.3f / %.3f x nArcs; filter %s)\n", (double)pc[0] / std::max(nB, 1),
+                         (double)pc[1] / std::max(nB, 1), (double)pc[0] / std::max(nB, 1) / (double)pe->hg.nArcs(),
+                         (double)pc[1] / std::max(nB, 1) / (double)pe->hg.nArcs(), sh->bsc.arcHit ? "on" : "off");
+        }
     }
     return SHD_PE_OK;
 }
@@ -1500,6 +1525,43 @@ static int tune_delta(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, Bat
     return SHD_PE_OK;
 }
 
+// Predecessor filter: the post kernel is faster behind a relax variant that
+// flags in-arcs (batch_relax_flags: the batch's bits fit in its LDS), so the
+// fastest relax alone is not the fastest pair.  When the picked relax does not
+// flag and another candidate's does, both pairs (with the picked post
+// variant) are timed alternately, A B A B, and the flagging relax is taken if
+// its pair's best sum is lower.
+static int tune_filter(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, const TuneSample* s,
+                       TunePick& p) {
+    const BatchPlan& plan = sh->plan;
+    const int n = pe->hg.n;
+    if (!sh->bsc.arcHit || batch_relax_flags(sh->bsc, plan.cand[p.relax], n)) return SHD_PE_OK;
+    int fk = -1;
+    for (int k = 0; k < plan.nc; ++k)
+        if (p.ok[k] && batch_relax_flags(sh->bsc, plan.cand[k], n) && (fk < 0 || s[k].msRelax < s[fk].msRelax))
+            fk = k;
+    if (fk < 0) return SHD_PE_OK;
+    double best[2] = {0.0, 0.0};
+    for (int rep = 0; rep < 4; ++rep) {
+        BatchTrial t;
+        t.relax = plan.cand[(rep & 1) ? fk : p.relax];
+        t.post = plan.cand[p.post];
+        t.timed = true;
+        TuneSample x;
+        const int rc = tune_run(pe, sh, pos, t, x);
+        if (rc) return rc;
+        const double sum = x.msRelax + x.msPost;
+        double& b = best[rep & 1];
+        if (sum > 0.0 && (b == 0.0 || sum < b)) b = sum;
+    }
+    if (pe->tu.debug || pe->tu.tuneLog)
+        std::fprintf(stderr, "[shdpe] shard %d tune: relax + post %.2f ms behind the %d-wave relax (in-arc flags) vs "
+                     "%.2f ms behind the %d-wave relax\n", sh->gindex, best[1], plan.cand[fk].wpe, best[0],
+                     plan.cand[p.relax].wpe);
+    if (best[1] > 0.0 && best[0] > 0.0 && best[1] < best[0]) p.relax = fk;
+    return SHD_PE_OK;
+}
+
 static void tune_log(const Shard* sh, const TuneSample* s, const TunePick& p, const double best[2]) {
     const BatchPlan& plan = sh->plan;
     for (int k = 0; k < plan.nc; ++k)
@@ -1533,8 +1595,9 @@ static int tune_shard(ShdPe* pe, Shard* sh) {
     double best[2] = {0.0, 0.0};
     if (!rc) {
         p = tune_pick(plan.cand, s, plan.nc);
+        if (p.perPart) rc = tune_filter(pe, sh, pos, s, p);
         relax = plan.cand[p.relax];
-        if (p.perPart) rc = tune_delta(pe, sh, pos, relax, plan.cand[p.post], best);
+        if (!rc && p.perPart) rc = tune_delta(pe, sh, pos, relax, plan.cand[p.post], best);
     }
     sh->stats = keep;               // the tune's computes are not the caller's
     if (rc) return rc;
@@ -2368,8 +2431,20 @@ extern "C" int shd_pe_reset_stats(ShdPe* pe) {
         st.batchWaves = keep.batchWaves;
         st.batchPostWaves = keep.batchPostWaves;
         sp->coopAborts = 0;
+        sp->predClaimed = sp->predGathered = 0;
     }
     pe->msGather = 0.0;
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_pred_filter_counts(const ShdPe* pe, int64_t* claimed, int64_t* gathered) {
+    if (!pe || !claimed || !gathered) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
+    *claimed = *gathered = 0;
+    for (auto& sp : pe->shards) {
+        *claimed += sp->predClaimed;
+        *gathered += sp->predGathered;
+    }
     return SHD_PE_OK;
 }
 

@@ -82,6 +82,7 @@ struct Shard {
     int64_t coopAborts = 0;         // cooperative relax launches refused by the runtime or aborted
                                     // at a barrier, counted together (round rerun plain):
                                     // relaxCoopAborts
+    int64_t predClaimed = 0, predGathered = 0;   // shd_pe_pred_filter_counts (debug counters)
     int32_t* dCoopAbort = nullptr;  // host-mapped copy target of the abort word
     bool tuned = false;
     BatchScratch bsc{};

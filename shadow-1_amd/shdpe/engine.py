@@ -29,7 +29,7 @@ EXPORTS = [
     "shd_pe_is_complete", "shd_pe_num_attached", "shd_pe_attached", "shd_pe_compute_all",
     "shd_pe_compute_rows", "shd_pe_compute_positions", "shd_pe_get_row", "shd_pe_get_rows",
     "shd_pe_copy_rows_device", "shd_pe_synchronize", "shd_pe_get_stats", "shd_pe_reset_stats",
-    "shd_pe_get_stats_sized", "shd_pe_stats_size",
+    "shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_pred_filter_counts",
     "shd_pe_stream_bandwidth", "shd_pe_num_shards", "shd_pe_shard_bounds", "shd_pe_plan_shards", "shd_pe_owned_range",
     "shd_pe_gather", "shd_pe_comm_unique_id", "shd_pe_comm_init",
     "shd_pe_direct_path", "shd_pe_self_path", "shd_pe_adjacent", "shd_pe_self_paths",
@@ -174,6 +174,7 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_get_stats_sized": (C.c_int, [vp, vp, C.c_int64]),
         "shd_pe_stats_size": (C.c_int64, []),
         "shd_pe_reset_stats": (C.c_int, [vp]),
+        "shd_pe_pred_filter_counts": (C.c_int, [vp, vp, vp]),
         "shd_pe_stream_bandwidth": (C.c_int, [vp, i64, i32, vp]),
         "shd_pe_num_shards": (i32, [vp]),
         "shd_pe_shard_bounds": (C.c_int, [vp, vp]),
@@ -243,7 +244,7 @@ def load_library(path: str = LIB_PATH):
     }
     # ABI-3 ... ABI-8 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
-    optional = {"shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_fill_rowstore_ex",
+    optional = {"shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_fill_rowstore_ex", "shd_pe_pred_filter_counts",
                 "shd_topology_fill", "shd_graphml_vertex_attrs", "shd_graphml_attr_code",
                 "shd_graphml_vertex_attr_string", "shd_pe_attach_new", "shd_pe_attach_free",
                 "shd_pe_attach_hosts", "shd_pe_attach_host", "shd_pe_attach_set_chunk",
@@ -572,7 +573,14 @@ class Engine:
     def stats(self) -> dict:
         s = Stats()
         self._chk(self._lib.shd_pe_get_stats(self.h, C.byref(s)), "shd_pe_get_stats")
-        return {f: getattr(s, f) for f, _ in Stats._fields_}
+        st = {f: getattr(s, f) for f, _ in Stats._fields_}
+        # the on-demand predecessor pass's in-arc counters (debug counters only, else 0)
+        claimed, gathered = C.c_int64(0), C.c_int64(0)
+        if hasattr(self._lib, "shd_pe_pred_filter_counts"):
+            self._chk(self._lib.shd_pe_pred_filter_counts(self.h, C.byref(claimed), C.byref(gathered)),
+                      "shd_pe_pred_filter_counts")
+        st["predArcsClaimed"], st["predArcsGathered"] = claimed.value, gathered.value
+        return st
 
     def reset_stats(self):
         self._chk(self._lib.shd_pe_reset_stats(self.h), "shd_pe_reset_stats")

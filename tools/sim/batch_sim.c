@@ -34,6 +34,13 @@ static const uint8_t* g_hub;
 double g_hubArcs, g_hubImp, g_hubProcs;
 void sim_set_hubs(const uint8_t* h) { g_hub = h; g_hubArcs = g_hubImp = g_hubProcs = 0; }
 void sim_hub_counts(double* o) { o[0] = g_hubArcs; o[1] = g_hubImp; o[2] = g_hubProcs; }
+// predecessor-filter probe (sim_set_flags, opt-in; NULL = off): arcFlag[a] is
+// set when a relaxation of arc a finds du + w <= D[x][l] in some active lane
+// BEFORE the update (the kernel's pre-check with <= for <), cleared at the
+// start of every batch; finalD receives the last batch's distances [n][LB]
+static uint8_t* g_arcFlag;
+static double* g_finalD;
+void sim_set_flags(uint8_t* arcFlag, double* finalD) { g_arcFlag = arcFlag; g_finalD = finalD; }
 static int cmp_key(const void* a, const void* b) {
     const double x = g_sortKey[*(const int32_t*)a], y = g_sortKey[*(const int32_t*)b];
     return x < y ? -1 : x > y ? 1 : 0;
@@ -77,6 +84,7 @@ int batch_sim(int32_t n, const int32_t* rowPtr, const int32_t* col, const double
         memset(hpend, 0, 8 * (size_t)n);
         memset(recP, 0, n);
         memset(recF, 0, n);
+        if (g_arcFlag) memset(g_arcFlag, 0, (size_t)rowPtr[n]);
         double farMin = INFINITY;
         double maxOff = 0;
         for (int l = 0; l < LB; ++l) {
@@ -140,6 +148,7 @@ int batch_sim(int32_t n, const int32_t* rowPtr, const int32_t* col, const double
                         for (int l = 0; l < LB; ++l) {
                             if (!((go >> l) & 1)) continue;
                             const double nb = du[l] + w;
+                            if (g_arcFlag && nb <= D[(size_t)x * LB + l]) g_arcFlag[a] = 1;
                             if (nb < D[(size_t)x * LB + l]) {
                                 D[(size_t)x * LB + l] = nb;
                                 const double kx = KEY(x, l, nb);
@@ -247,6 +256,7 @@ int batch_sim(int32_t n, const int32_t* rowPtr, const int32_t* col, const double
                     for (int l = 0; l < LB; ++l) {
                         if (!((act >> l) & 1)) continue;
                         const double nb = du[l] + w;
+                        if (g_arcFlag && nb <= D[(size_t)x * LB + l]) g_arcFlag[a] = 1;
                         if (nb < D[(size_t)x * LB + l]) {
                             D[(size_t)x * LB + l] = nb;
                             if (farMode && KEY(x, l, nb) >= bound) {
@@ -278,6 +288,7 @@ int batch_sim(int32_t n, const int32_t* rowPtr, const int32_t* col, const double
                 bound = nb;
             }
         }
+        if (g_finalD) memcpy(g_finalD, D, sizeof(double) * (size_t)n * LB);
     }
     free(D);
     free(pend);
