@@ -501,9 +501,9 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         __syncthreads();
         if constexpr (CO)      // every member's slice is +inf before any source entry
             if (!co_barrier(bs, coBar, coK, coEpoch, &sCo[4])) return;
-        // lane offset: the source's distance to its nearest hub (host plan);
-        // key = dist + (maxOff - off) lines the lanes up behind the hub
-        const double off = (row >= 0 && bs.rowOff) ? as_global(bs.rowOff)[row] : 0.0;
+        // lane offset: how far the source sits ahead of its batch mates (host
+        // plan, lane_offsets); key = dist + (maxOff - off) lines the lanes up
+        const double off = row >= 0 ? as_global(bs.laneOff)[(size_t)b * LB + l] : 0.0;
         if (gid == 0) atomicMax(reinterpret_cast<unsigned long long*>(&ctl->maxOff), d2b(off));
         if (PT != 2 && gid == 0 && src >= 0 && coMember == 0) {
             D[(size_t)src * LB + l] = enc_dirty(d2b(0.0));

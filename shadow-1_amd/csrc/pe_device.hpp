@@ -166,6 +166,8 @@ struct Tuning {
     int pathsFast = 1;         // ... 0: no batch / tie tier, every source by the grouped emulation
     int predFilter = 1;        // on-demand predecessor pass reads only the in-arcs the relax
                                // flagged (0: every in-arc, BatchScratch::arcHit stays null)
+    int laneOffset = 1;        // bucket key offsets of a batch's lanes: 1 the least-squares
+                               // shift over the hub groups, 0 the nearest-hub distance
     int failWpe = 0;           // tests only: the relax variant of this wave count flags
                                // every batch failed (a miscompiled variant; shd_pe_tune
                                // must not pick it)
@@ -207,8 +209,8 @@ struct BatchScratch {
     uint32_t* bits;          // [slot][2 * words] pending bitmaps when they exceed LDS (gbits)
     int32_t* flags;          // split kernels: per batch of the round, bit 0 = phase cap hit,
                              // bit 1 = the relax wrote the batch's arcHit bits
-    const double* rowOff;    // [T] per table position: the source's distance to its
-                             // batch hub (bucket key offset; null = no offsets)
+    const double* laneOff;   // [batch][LB] beside the launch's batchRows: the lane's bucket
+                             // key offset (pe_plan.hpp lane_offsets; pads 0), set per launch
     // cooperative relax (PART 3 of k_batch_rows): K workgroups of one XCD
     // share a batch; the group state below is zeroed by the host before
     // every launch

@@ -88,6 +88,7 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_STREAM_WG_PER_CU", t.streamWgPerCU);
     gi("SHDPE_TIE_CORRUPT", t.tieCorrupt);
     gi("SHDPE_PRED_FILTER", t.predFilter);
+    gi("SHDPE_LANE_OFFSET", t.laneOffset);
     gi("SHDPE_TUNE_FAIL_WPE", t.failWpe);
     gi("SHDPE_TUNE_LOG", t.tuneLog);
     gi("SHDPE_BATCH_COOP", t.batchCoop);
@@ -705,6 +706,7 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     if ((rc = dev_alloc(sh, &sh->bsc.D, roundB * NS * LB)) || (rc = dev_alloc(sh, &sh->bsc.L, slots * NS * LB)) ||
         (rc = dev_alloc(sh, &sh->bsc.queue, slots * NS + 16)) ||
         (rc = dev_alloc(sh, &sh->dBatchRows, (size_t)sh->rowsCap + 64)) ||
+        (rc = dev_alloc(sh, &sh->dLaneOff, (size_t)sh->rowsCap + 64)) ||
         (rc = dev_alloc(sh, &sh->dBatchAmb, (size_t)sh->rowsCap + 64)) ||
         (rc = dev_alloc(sh, &sh->bsc.flags, roundB + 16)))
         return rc;
@@ -719,12 +721,7 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     if (pe->tu.debug && (rc = dev_alloc(sh, &sh->bsc.predCnt, 2))) return rc;
     sh->bsc.bits = nullptr;
     if (bitBytes && (rc = dev_alloc(sh, &sh->bsc.bits, slots * bitBytes / 4))) return rc;
-    sh->bsc.rowOff = nullptr;
-    if (!pe->rowOff.empty()) {
-        double* ro;
-        if ((rc = dev_upload(sh, &ro, pe->rowOff))) return rc;
-        sh->bsc.rowOff = ro;
-    }
+    sh->bsc.laneOff = sh->dLaneOff;
     if (plan.coop >= 0) {
         // cooperative relax state: control words, one barrier line per group,
         // two publication buffers of near bits + scalars per member per group
@@ -826,9 +823,10 @@ static void print_batch_debug(ShdPe* pe, Shard* sh, const BatchLaunch& relax, co
 }
 
 // SHDPE_DUMP_BATCHES=<file>: per batch its rows (table positions, -1 pads),
-// hub offsets, kernel counters and hub-group distances, for offline batch-cost models
+// hub offsets, kernel counters, hub-group distances and, last, the offsets the
+// kernel ran with per (batch, lane), for offline batch-cost models
 // (tools/batch_cost.py)
-static void dump_batches(const ShdPe* pe, const std::vector<int32_t>& order,
+static void dump_batches(const ShdPe* pe, const std::vector<int32_t>& order, const std::vector<double>& laneOff,
                          const std::vector<int32_t>& dbg, int32_t nB, int32_t LB) {
     const char* f = std::getenv("SHDPE_DUMP_BATCHES");
     FILE* fp = f ? std::fopen(f, "wb") : nullptr;
@@ -845,6 +843,7 @@ static void dump_batches(const ShdPe* pe, const std::vector<int32_t>& order,
     std::fwrite(&nGroups, 4, 1, fp);
     std::fwrite(&pe->hg.meanArcLatency, 8, 1, fp);
     std::fwrite(pe->hubGroups.dist.data(), 8, pe->hubGroups.dist.size(), fp);
+    std::fwrite(laneOff.data(), 8, laneOff.size(), fp);     // [nB * LB], after what older readers read
     std::fclose(fp);
 }
 
@@ -920,14 +919,22 @@ static void corrupt_tie_slot(ShdPe* pe, Shard* sh, const std::vector<int32_t>& s
 // before the lock is released, for the abort check anyway).
 static std::mutex g_coopMu[64];
 
+// The batch scratch for a launch over the batches at `rows` (inside
+// dBatchRows): the lane offsets are those of the same entries of dLaneOff.
+static BatchScratch scratch_at(const Shard* sh, const int32_t* rows) {
+    BatchScratch bs = sh->bsc;
+    bs.laneOff = sh->dLaneOff + (rows - sh->dBatchRows);
+    return bs;
+}
+
 static int relax_coop(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int32_t* rows, int32_t rn,
                       uint8_t* amb, int32_t* dbg) {
     std::lock_guard<std::mutex> devLock(g_coopMu[sh->device & 63]);
     const size_t maxGroups = (size_t)sh->plan.cand[sh->plan.coop].grid;
     HIPCHK(hipMemsetAsync(sh->bsc.coCtl, 0, 128 + maxGroups * 128, sh->stream));
     HIPCHK(hipMemsetAsync(sh->bsc.flags, 0, (size_t)rn * 4, sh->stream));
-    const bool refused = launch_batch_relax_coop(sh->dg, sh->tab, sh->bsc, rows, rn, amb, relax, dbg, sh->dTie,
-                                                 sh->stream) != 0;
+    const bool refused = launch_batch_relax_coop(sh->dg, sh->tab, scratch_at(sh, rows), rows, rn, amb, relax, dbg,
+                                                 sh->dTie, sh->stream) != 0;
     bool rerun = refused;
     if (refused) {
         (void)hipGetLastError();                  // the refusal (the abort word was never copied)
@@ -945,7 +952,7 @@ static int relax_coop(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int3
         BatchLaunch plain = relax;
         plain.coop = 0;
         HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
-        launch_batch_rows(sh->dg, sh->tab, sh->bsc, rows, rn, amb, plain, dbg, sh->dTie, sh->stream, 1);
+        launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, rows), rows, rn, amb, plain, dbg, sh->dTie, sh->stream, 1);
         HIPCHK(hipGetLastError());
     }
     return SHD_PE_OK;
@@ -1053,7 +1060,8 @@ static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const Ba
                     return rc;
             } else {
                 HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
-                launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows + ro, rn, sh->dBatchAmb + ro,
+                launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, sh->dBatchRows + ro), sh->dBatchRows + ro, rn,
+                                  sh->dBatchAmb + ro,
                                   part == 1 ? relax : post, dbgR, sh->dTie, sh->stream,
                                   part == 1 ? 1 : postPart);
             }
@@ -1098,20 +1106,25 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     if ((rc = ensure_batch(pe, sh))) return rc;
     const BatchLaunch& relax = relax_launch(sh, trial);
     int32_t nB = 0;
+    const int offKind = pe->tu.laneOffset != 0;
+    const bool byCost = !batchOrder && !pe->hubGroups.empty();
+    std::vector<double> laneOff;     // per entry of `order`: they depend on who shares the batch
     const std::vector<int32_t> order =
         batchOrder ? *batchOrder
-        : !pe->hubGroups.empty()
-            ? batch_order_cost(pe->rank, pe->rowOff, pe->hubGroups, pe->hg.meanArcLatency, relax.lb, pos, cnt, nB)
-            : batch_order(pe->rank, pe->rowOff, relax.lb, pos, cnt, nB);
+        : byCost ? batch_order_cost(pe->rank, pe->rowOff, pe->hubGroups, pe->hg.meanArcLatency, relax.lb, pos, cnt,
+                                    nB, nullptr, &laneOff, offKind)
+                 : batch_order(pe->rank, pe->rowOff, relax.lb, pos, cnt, nB);
+    if (!byCost) laneOff = lane_offsets(pe->hubGroups, pe->rowOff, order, relax.lb, offKind);
     nB = (int32_t)(order.size() / (size_t)relax.lb);
     HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemcpyAsync(sh->dLaneOff, laneOff.data(), laneOff.size() * 8, hipMemcpyHostToDevice, sh->stream));
     if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
     if (sh->bsc.predCnt) HIPCHK(hipMemsetAsync(sh->bsc.predCnt, 0, 16, sh->stream));
     if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
     HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
     HIPCHK(hipEventRecord(sh->evA, sh->stream));
     if (!relax.split)
-        launch_batch_rows(sh->dg, sh->tab, sh->bsc, sh->dBatchRows, nB, sh->dBatchAmb, relax,
+        launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, sh->dBatchRows), sh->dBatchRows, nB, sh->dBatchAmb, relax,
                           sh->dDbg, sh->dTie, sh->stream, 0);
     else if ((rc = batch_rounds(pe, sh, relax, post_launch(sh, trial), nB, trial, roundHook)))
         return rc;
@@ -1127,7 +1140,7 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
         std::vector<int32_t> dbg((size_t)nB * 16);
         HIPCHK(hipMemcpy(dbg.data(), sh->dDbg, dbg.size() * 4, hipMemcpyDeviceToHost));
         print_batch_debug(pe, sh, relax, dbg.data(), nB);
-        dump_batches(pe, order, dbg, nB, relax.lb);
+        dump_batches(pe, order, laneOff, dbg, nB, relax.lb);
         if (sh->bsc.predCnt) {
             unsigned long long pc[2] = {0, 0};
             HIPCHK(hipMemcpy(pc, sh->bsc.predCnt, 16, hipMemcpyDeviceToHost));

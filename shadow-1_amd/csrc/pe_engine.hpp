@@ -90,6 +90,7 @@ struct Shard {
     int32_t batchRound = 0;         // split kernels: batches per round (persisted dist arrays)
     int32_t batchSlots = 0;         // scratch slots allocated (ensure_batch: no grid of the plan exceeds it)
     int32_t* dBatchRows = nullptr;
+    double* dLaneOff = nullptr;     // per entry of dBatchRows its lane's bucket key offset
     uint8_t* dBatchAmb = nullptr;
     TieBuf tie{};                   // early-stop tie rows (batched path)
     int32_t* dSlots = nullptr;      // per exact row its tie slot, -1 full emulation
@@ -123,8 +124,8 @@ struct ShdPe {
     int mode = 1;
     bool batched = false;
     std::vector<int32_t> rank;       // table position -> batch order rank
-    std::vector<double> rowOff;      // table position -> distance to its batch hub (orders 1, 2)
-    shdpe::HubGroups hubGroups;      // batch order 2: what batch_order_cost predicts from
+    std::vector<double> rowOff;      // table position -> distance to its nearest hub (orders 1, 2)
+    shdpe::HubGroups hubGroups;      // batch order 2: what batch_order_cost and lane_offsets work from
     std::vector<int32_t> devOf;      // caller vertex id -> device id (empty: identity)
     int G = 1;                       // global row shards
     std::vector<int32_t> bounds;     // G + 1 position bounds

@@ -259,13 +259,51 @@ static std::vector<int32_t> compose_batches(const std::vector<int32_t>& rank, in
 }
 
 // The batches of order[] in the sequence of the stably sorted key[] = (key, batch)
-static void sequence_batches(std::vector<int32_t>& order, int LB, std::vector<std::pair<double, int32_t>>& key) {
-    std::stable_sort(key.begin(), key.end());
-    std::vector<int32_t> re(order.size());
+template <class T>
+static void permute_batches(std::vector<T>& order, int LB, const std::vector<std::pair<double, int32_t>>& key) {
+    std::vector<T> re(order.size());
     for (size_t i = 0; i < key.size(); ++i)
         std::copy(order.begin() + (size_t)key[i].second * LB,
                   order.begin() + (size_t)(key[i].second + 1) * LB, re.begin() + i * LB);
     order.swap(re);
+}
+
+static void sequence_batches(std::vector<int32_t>& order, int LB, std::vector<std::pair<double, int32_t>>& key) {
+    std::stable_sort(key.begin(), key.end());
+    permute_batches(order, LB, key);
+}
+
+std::vector<double> lane_offsets(const HubGroups& groups, const std::vector<double>& rowOff,
+                                 const std::vector<int32_t>& order, int LB, int kind) {
+    std::vector<double> off(order.size(), 0.0);
+    const int G = groups.G;
+    std::vector<double> S(LB);
+    for (size_t b0 = 0; b0 + LB <= order.size(); b0 += LB) {
+        const int32_t* row = &order[b0];
+        // J: the groups that reach every real lane (ascending)
+        int nJ = 0;
+        std::fill(S.begin(), S.end(), 0.0);
+        for (int j = 0; kind == 1 && j < G; ++j) {
+            bool all = true;
+            for (int l = 0; l < LB && all; ++l)
+                all = row[l] < 0 || std::isfinite(groups.dist[(size_t)row[l] * G + j]);
+            if (!all) continue;
+            ++nJ;
+            for (int l = 0; l < LB; ++l)
+                if (row[l] >= 0) S[l] += groups.dist[(size_t)row[l] * G + j];
+        }
+        if (!nJ) {      // no common landmark (or kind 0): the nearest-hub distances
+            for (int l = 0; l < LB; ++l)
+                if (row[l] >= 0 && !rowOff.empty()) off[b0 + l] = rowOff[row[l]];
+            continue;
+        }
+        double mn = INFINITY;
+        for (int l = 0; l < LB; ++l)
+            if (row[l] >= 0) mn = std::min(mn, S[l]);
+        for (int l = 0; l < LB; ++l)
+            if (row[l] >= 0) off[b0 + l] = (S[l] - mn) / nJ;
+    }
+    return off;
 }
 
 std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
@@ -294,12 +332,18 @@ std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::ve
 // to tools/sim/batch_sim.c's count over the 1,024 order-2 batches of C4
 // (tools/sim/plan_eval.py c4 --fit; profiles/batch_plan_cost_sim.json holds
 // the fit and its correlation, 0.945).  Only the order of the costs is used.
+// The features stay those of the nearest-hub distance under least-squares
+// lane offsets too: with the spread taken as the residual those offsets leave
+// and the constants refitted, the correlation is 0.942 and the replayed take
+// ends where this sequence does (profiles/lane_offsets_sim.json).
 static const double COST_C0 = 0.892, COST_OFF = 0.200, COST_SPREAD = 3.363;
 
 std::vector<int32_t> batch_order_cost(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
                                       const HubGroups& groups, double meanArcLatency, int LB,
-                                      const int32_t* pos, int32_t cnt, int32_t& nB, std::vector<double>* cost) {
+                                      const int32_t* pos, int32_t cnt, int32_t& nB, std::vector<double>* cost,
+                                      std::vector<double>* laneOff, int offsetKind) {
     std::vector<int32_t> order = compose_batches(rank, LB, pos, cnt, nB);
+    std::vector<double> offs = lane_offsets(groups, rowOff, order, LB, offsetKind);
     const double unit = meanArcLatency > 0.0 && std::isfinite(meanArcLatency) ? meanArcLatency : 1.0;
     const int G = groups.G;
     std::vector<std::pair<double, int32_t>> key(nB);
@@ -337,7 +381,11 @@ std::vector<int32_t> batch_order_cost(const std::vector<int32_t>& rank, const st
         const double c = (COST_C0 + COST_OFF * meanOff + COST_SPREAD * spread) * lanes / LB;
         key[b] = {-c, b};
     }
-    if (nB > 1) sequence_batches(order, LB, key);
+    if (nB > 1) {
+        sequence_batches(order, LB, key);
+        permute_batches(offs, LB, key);
+    }
+    if (laneOff) laneOff->swap(offs);
     if (cost) {
         cost->resize(nB);
         for (int32_t b = 0; b < nB; ++b) (*cost)[b] = -key[b].first;

@@ -1,6 +1,7 @@
 // pe_plan.hpp -- what shd_pe_create decides on the host before anything is
 // uploaded: the device vertex ids (degree relabelling), the batch schedule
-// (ranks, hub offsets, batch order), the compute mode and the row-shard plan.
+// (ranks, hub distances, batch order and, per composed batch, the lanes'
+// bucket key offsets), the compute mode and the row-shard plan.
 // Free functions over HostGraph and plain vectors: no GPU types, no engine
 // state, so tests/native/plan.cpp drives them on the CPU under sanitizers.
 #pragma once
@@ -40,7 +41,8 @@ HostGraph relabel_graph(const HostGraph& g, const std::vector<int32_t>& oldOf);
 //            hub of another group, the gap between the two, distance to the
 //            nearest), so the sources of a batch also agree on the side of
 //            the cell they sit on.  rowOff is the nearest-hub distance as in
-//            order 1, and `groups` feeds batch_order_cost.
+//            order 1; `groups` feeds batch_order_cost and lane_offsets, which
+//            replaces rowOff as the bucket key offset batch by batch.
 // Scheduling only: results never depend on it (tools/sim/ models the
 // schedule: C4 arc visits 3.9 -> 2.2 x m per batch with offsets, dirty
 // lanes and a far set at delta = mean arc latency).
@@ -66,7 +68,7 @@ HubGroups hub_group_distances(const HostGraph& g, const std::vector<int32_t>& at
 
 struct BatchRanks {
     std::vector<int32_t> rank;     // table position -> batch order rank
-    std::vector<double> rowOff;    // table position -> distance to its batch hub (orders 1, 2)
+    std::vector<double> rowOff;    // table position -> distance to its nearest hub (orders 1, 2)
     HubGroups groups;              // order 2 only
 };
 BatchRanks batch_ranks(const HostGraph& g, const std::vector<int32_t>& attached,
@@ -77,6 +79,25 @@ BatchRanks batch_ranks(const HostGraph& g, const std::vector<int32_t>& attached,
 std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
                                  int LB, const int32_t* pos, int32_t cnt, int32_t& nB);
 
+// The bucket key offset of every lane of the composed batches order[nB * LB]
+// (table positions, -1 pads), at [b * LB + l]: k_batch_rows relaxes a lane's
+// entry in the bucket of dist + maxOff - off, maxOff the batch's largest.
+//   kind 0: the nearest-hub distance rowOff[p] (0 without rowOff: order 0);
+//   kind 1 (default): the least-squares shift over the hub groups.  With J
+//           the groups whose distance is finite for every real lane of the
+//           batch, the shifts s that minimise the squared differences of
+//           (d[l][j] - s_l) between the lanes, summed over J, are
+//             s_l = mean over J of (d[l][j] - mean over the lanes of d[.][j]),
+//           and the offset is s_l less the smallest of the batch: computed
+//           as (S_l - min S) / |J| with S_l the sum of d[l][j] over J, which
+//           is the same number (the lane means cancel) without their rounding.
+//           J empty (a lane no hub reaches, or no groups): kind 0's offsets.
+// Every offset is finite and >= 0, pads are 0, the smallest of a kind 1 batch
+// is exactly 0, and a lane's offset depends on its batch mates but not on
+// their sequence in the batch (sums run over the groups ascending, per lane).
+std::vector<double> lane_offsets(const HubGroups& groups, const std::vector<double>& rowOff,
+                                 const std::vector<int32_t>& order, int LB, int kind = 1);
+
 // The batches of batch_order (same composition: consecutive LB rows by rank,
 // the pads last), sequenced by non-increasing predicted relax cost, equal
 // costs in rank order.  A batch's cost, in units of one pass over the arcs:
@@ -85,11 +106,15 @@ std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::ve
 // the groups with a finite distance, of (group distance - rowOff) less its
 // mean over the batch's lanes in that group -- how far the sources are out of
 // step with each other -- both in units of meanArcLatency.  (The constants:
-// pe_plan.cpp.)  cost, if given, receives the nB costs in the order returned.
+// pe_plan.cpp.)  The lane offsets are lane_offsets(..., offsetKind) of the
+// composed batches, permuted with them: the sequence does not depend on the
+// kind.  laneOff, if given, receives them and cost the nB costs, both in the
+// order returned.
 std::vector<int32_t> batch_order_cost(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
                                       const HubGroups& groups, double meanArcLatency, int LB,
                                       const int32_t* pos, int32_t cnt, int32_t& nB,
-                                      std::vector<double>* cost = nullptr);
+                                      std::vector<double>* cost = nullptr,
+                                      std::vector<double>* laneOff = nullptr, int offsetKind = 1);
 
 // 1 sparse SSSP rows, 2 direct rows (complete graph), 3 dense min-plus.
 int select_mode(const HostGraph& g, int forceMode, double denseMin);

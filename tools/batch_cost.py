@@ -82,3 +82,15 @@ if len(b)>o and nG>0:
     for nm,y,G in (('relax',relax,256),('post',post,512)):
         print('  %s P=%d: as dumped %.1fM  by true cost %.1fM  ideal %.1fM  (max/mean batch %.2f)'%(
             nm,G,makespan(y,G)/1e6,makespan(np.sort(y)[::-1],G)/1e6,y.sum()/G/1e6,y.max()/y.mean()))
+    # the per-(batch, lane) offsets the kernel ran with (dumps since the
+    # least-squares lane offsets; older dumps end with the group distances)
+    o+=8*nOff*nG
+    if len(b)>=o+8*nB*LB:
+        lane=np.frombuffer(b[o:o+8*nB*LB],np.float64).reshape(nB,LB)
+        xl=np.where((order>=0)[:,:,None], (dist[np.maximum(order,0)]-lane[:,:,None])/unit, np.nan)
+        xl=np.where(np.isfinite(xl),xl,np.nan)
+        devl=xl-np.nanmean(xl,axis=1,keepdims=True)
+        resid=np.sqrt(np.nansum(devl**2,axis=(1,2))/np.maximum(1,np.isfinite(xl).sum(axis=(1,2))))
+        lsq=~np.isclose(np.where(order>=0,lane,0.0),np.where(order>=0,offb,0.0)).all(1)
+        print('lane offsets: %d of %d batches differ from the nearest-hub distance; residual spread under them corr relax %.3f post %.3f'%(
+            lsq.sum(),nB,np.corrcoef(resid,relax)[0,1],np.corrcoef(resid,post)[0,1]))
