@@ -146,11 +146,8 @@ typedef struct ShdPeStats {
     int64_t rowsTieRepaired;   /* early-stop tie rows whose exported slot failed the
                                   exact kernel's distance cross-check and were
                                   recomputed by the full emulation (0 when correct) */
-    int32_t batchCoop;         /* relax kernel in use: workgroups per batch (>= 2:
-                                  the cooperative relax of small shards; 0 plain) */
-    int64_t relaxCoopAborts;   /* cooperative relax launches refused or aborted (a
-                                  barrier wait ran too long); each round was
-                                  recomputed by the plain relax */
+    int32_t batchCoop;         /* reserved, always 0 (cooperative relax, retired) */
+    int64_t relaxCoopAborts;   /* reserved, always 0 (cooperative relax, retired) */
 } ShdPeStats;
 
 /* Defaults for ShdPeOptions. */

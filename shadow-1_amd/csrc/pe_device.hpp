@@ -156,11 +156,6 @@ struct Tuning {
     int tieCorrupt = 0;        // tests only: 1 / 2 scale one early-stop slot's exported
                                // distances after the relevance scan (exercises the tie-slot
                                // repair); 3 = k_tie_export treats its first slot as violated
-    int batchCoop = 0;         // cooperative relax: K workgroups per batch (>= 2 forces it,
-                               // 1 = a shd_pe_tune candidate, 0 = off)
-    int batchCoopWpe = 0;      // its variant (8 / 6 / 4 waves; 0 = the one with two
-                               // workgroups per CU)
-    int coopSpin = 1 << 22;    // its barrier poll limit (tests shrink it to force aborts)
     int pathsGroup = 0;        // shd_pe_get_paths: sources per emulation group (0: exactGrid)
     int pathsChunk = 0;        // ... requests per staging chunk (0: 65,536)
     int pathsFast = 1;         // ... 0: no batch / tie tier, every source by the grouped emulation
@@ -211,16 +206,6 @@ struct BatchScratch {
                              // bit 1 = the relax wrote the batch's arcHit bits
     const double* laneOff;   // [batch][LB] beside the launch's batchRows: the lane's bucket
                              // key offset (pe_plan.hpp lane_offsets; pads 0), set per launch
-    // cooperative relax (PART 3 of k_batch_rows): K workgroups of one XCD
-    // share a batch; the group state below is zeroed by the host before
-    // every launch
-    int32_t* coCtl;          // [0..15] workgroups registered per XCD, [16] registered,
-                             // [17] abort (a barrier wait ran past coSpin polls)
-    int32_t* coBars;         // [group * 32]: one barrier counter per group (own line)
-    uint32_t* coPub;         // [group][2][K][nwp] published near bits (two buffers)
-    unsigned long long* coPubS;   // [group][2][K][2] published near count | far flag, far min
-    int32_t coK;             // members per group (PART 3 only)
-    int32_t coSpin;          // barrier poll limit (s_sleep 1 each)
     // predecessor filter (split kernels): one bit per in-arc slot -- inPtr /
     // inCol order when directed, the head's own row when undirected -- set by
     // the relax when some lane's pre-check of the arc found dist[u] + w <=
@@ -245,8 +230,6 @@ struct BatchLaunch {
     double delta;            // bucket width
     int32_t gbits;           // 1: pending bitmaps in global scratch (n > ~655k vertices)
     int32_t split;           // 1: relax and post as two kernels over rounds of batches
-    int32_t coop;            // relax: K >= 2 workgroups (one XCD) per batch, PART 3 kernel
-                             // launched cooperatively (all resident); 0 / 1: off
 };
 
 // Tie export (pe_batch.hip -> k_exact_rows early stop -> k_tie_write): per
@@ -344,12 +327,6 @@ void launch_batch_rows(const DevGraph& g, const DevTable& tab, const BatchScratc
                        const BatchLaunch& cfg, int32_t* dDbg, const TieBuf* dTie, void* stream,
                        int part = 0);   // (part 4: the post kernel, part 2, storing no table row)
 const void* batch_kernel_ptr(int lb, int wpe, bool gbits, int part = 0);
-// cooperative relax (PART 3; LB 8 / 16, LDS bitmaps): 0 launched, -1 refused
-// (grid not resident / unsupported shape: run launch_batch_rows part 1)
-int launch_batch_relax_coop(const DevGraph& g, const DevTable& tab, const BatchScratch& bs,
-                            const int32_t* dBatchRows, int32_t nBatches, uint8_t* dRowAmbig,
-                            const BatchLaunch& cfg, int32_t* dDbg, const TieBuf* tie, void* stream);
-const void* batch_coop_kernel_ptr(int lb, int wpe);
 int batch_lds_bytes(int n, int wpe, bool gbits);
 // Deferred tie export of one round (after its post kernel): for every slot
 // the post kernel requested in round `round`, the tie data of the lane's row

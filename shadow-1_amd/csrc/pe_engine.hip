@@ -91,9 +91,6 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_LANE_OFFSET", t.laneOffset);
     gi("SHDPE_TUNE_FAIL_WPE", t.failWpe);
     gi("SHDPE_TUNE_LOG", t.tuneLog);
-    gi("SHDPE_BATCH_COOP", t.batchCoop);
-    gi("SHDPE_BATCH_COOP_WPE", t.batchCoopWpe);
-    gi("SHDPE_COOP_SPIN", t.coopSpin);
     gi("SHDPE_PATHS_GROUP", t.pathsGroup);
     gi("SHDPE_PATHS_CHUNK", t.pathsChunk);
     gi("SHDPE_PATHS_FAST", t.pathsFast);
@@ -209,54 +206,6 @@ static void configure_exact(ShdPe* pe, Shard* sh) {
     sh->exactGrid = sh->numCUs * (tu.exactPerCU > 0 ? tu.exactPerCU : exPerCU);
 }
 
-// configure_batch's cooperative candidate, added to the plan after the plain
-// picks (`b`: the plain relax pick; v4 / v6 / v8: the variants).
-// Cooperative relax (PART 3, K workgroups of one XCD per batch): for a
-// shard with fewer batches than the plain relax has workgroup slots --
-// the C4 8-GPU shard's 256 LB-8 batches leave one of the two 8-wave
-// slots of every CU idle -- the batch's listing rounds are shared by K
-// workgroups.  SHDPE_BATCH_COOP=K forces it, =1 makes it a candidate of
-// shd_pe_tune (off by default: slower than the plain relax wherever it
-// was measured).
-static void configure_batch_coop(ShdPe* pe, Shard* sh, const BatchLaunch& b, const BatchLaunch& v4,
-                                 const BatchLaunch& v6, const BatchLaunch& v8, bool ok6, bool ok8) {
-    const Tuning& tu = pe->tu;
-    const int LDS = LDS_BYTES;
-    BatchPlan& p = sh->plan;
-    if (!(pe->batched && b.split && !b.gbits && (b.lb == 8 || b.lb == 16) && tu.batchCoop >= 1)) return;
-    const int K = tu.batchCoop >= 2 ? std::min(tu.batchCoop, 8) : 2;
-    const int wpeC = tu.batchCoopWpe == 4 || tu.batchCoopWpe == 6 || tu.batchCoopWpe == 8
-                         ? tu.batchCoopWpe
-                         : ok8 ? 8 : ok6 ? 6 : 4;
-    BatchLaunch c2 = wpeC == 8 ? v8 : wpeC == 6 ? v6 : v4;
-    c2.split = 1;
-    const void* fn = batch_coop_kernel_ptr(b.lb, wpeC);
-    int per = 0;
-    if (!(c2.ldsBytes <= LDS &&
-          hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, c2.ldsBytes) == hipSuccess &&
-          hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, fn, c2.threads, c2.ldsBytes) == hipSuccess &&
-          per >= 1))
-        return;
-    c2.grid = sh->numCUs * per;
-    c2.coop = K;
-    const int64_t nB = ((int64_t)sh->rowCount + b.lb - 1) / b.lb;
-    if (tu.batchCoop >= 2) {
-        // forced: the relax variant in use and the only candidate; the post
-        // kernel stays the plain pick's
-        p = BatchPlan{};
-        p.cand[p.nc++] = c2;
-        p.coop = 0;
-        p.relax = c2;
-        p.post = b;
-    } else if (nB * K <= c2.grid && nB < b.grid) {
-        // a tune candidate only on request (SHDPE_BATCH_COOP=1): measured
-        // slower than the plain relax at every shard size (round 6, C4
-        // N=8: 17.1-22.6 vs 16.8 ms; profiles/r06_shard_times.txt)
-        p.coop = p.nc;
-        p.cand[p.nc++] = c2;
-    }
-}
-
 // The batched kernel's variants and the shard's plan of them.  False when
 // neither the 4- nor the 8-wave variant fits the LDS.
 static bool configure_batch(ShdPe* pe, Shard* sh) {
@@ -271,8 +220,8 @@ static bool configure_batch(ShdPe* pe, Shard* sh) {
     // N=4 (4,096 rows) LB 16 28.8 ms vs LB 8 31.0, N=8 (2,048 rows) LB 8 17.2
     // vs LB 16 25.4; round 4 (two 8-wave workgroups per CU, r04_shard_times)
     // had N=4 at LB 8.  LB 4 (32-B line pieces) stays a SHDPE_BATCH_LB option.  (The
-    // round-4 cooperative relax -- K workgroups per batch -- and the post
-    // kernel over lane slices are patches under tools/variants/)
+    // relax shared by K workgroups per batch and the post kernel over lane
+    // slices are patches under tools/variants/)
     b.lb = tu.batchLB;
     if (b.lb != 4 && b.lb != 8 && b.lb != 16 && b.lb != 32)
         b.lb = ((int64_t)sh->rowCount + 15) / 16 >= (int64_t)sh->numCUs ? 16 : 8;
@@ -329,7 +278,6 @@ static bool configure_batch(ShdPe* pe, Shard* sh) {
     if (!forced && ok6 && tu.batchSplit) p.cand[p.nc++] = v6.first;
     p.relax = p.post = b;
     if (!forced && first == 4 && ok6 && b.split && b.lb >= 16) p.post = v6.first;
-    configure_batch_coop(pe, sh, b, v4.first, v6.first, v8.first, ok6, ok8);
     return ok8 || ok4;
 }
 
@@ -372,7 +320,6 @@ static void destroy_shard(Shard* s) {
         if (e) (void)hipEventDestroy(e);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     if (s->copyStream) (void)hipStreamDestroy(s->copyStream);
-    if (s->dCoopAbort) (void)hipHostFree(s->dCoopAbort);
 }
 
 // Upload `g` as a DevGraph; `attached` is in g's vertex ids.  oldOf == null:
@@ -661,20 +608,7 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     const size_t nBatchesAll = ((size_t)sh->rowCount + LB - 1) / LB;
     size_t grid = 0;                               // the candidates' largest
     for (int k = 0; k < plan.nc; ++k) grid = std::max(grid, (size_t)plan.cand[k].grid);
-    // (a cooperative launch needs one slot per resident workgroup: its grid
-    // is the whole resident set, more workgroups than batches)
-    const size_t coGrid = plan.coop >= 0 ? (size_t)plan.cand[plan.coop].grid : 0;
-    const size_t slots = std::min<size_t>({grid, maxSlots, std::max<size_t>({(size_t)1, nBatchesAll, coGrid})});
-    if (coGrid > slots) {                          // scratch budget: no cooperative relax
-        plan.nc = plan.coop;                       // (the cooperative candidate is the last)
-        plan.coop = -1;
-        if (plan.relax.coop >= 2) {                // a forced one: the plain kernel of its post variant
-            plan.relax = plan.post;
-            plan.relax.coop = 0;
-            plan.cand[plan.nc++] = plan.relax;
-            plan_stats(pe, sh);
-        }
-    }
+    const size_t slots = std::min<size_t>({grid, maxSlots, std::max<size_t>(1, nBatchesAll)});
     // a workgroup indexes its scratch slot by blockIdx: no launch may have
     // more workgroups than slots, so every grid of the plan is lowered here
     sh->batchSlots = (int32_t)slots;
@@ -722,22 +656,6 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     sh->bsc.bits = nullptr;
     if (bitBytes && (rc = dev_alloc(sh, &sh->bsc.bits, slots * bitBytes / 4))) return rc;
     sh->bsc.laneOff = sh->dLaneOff;
-    if (plan.coop >= 0) {
-        // cooperative relax state: control words, one barrier line per group,
-        // two publication buffers of near bits + scalars per member per group
-        const size_t maxGroups = (size_t)plan.cand[plan.coop].grid;
-        const size_t K = (size_t)plan.cand[plan.coop].coop;
-        const size_t nwp = (size_t)batch_bits_words(pe->hg.n) / 2;
-        if ((rc = dev_alloc(sh, &sh->bsc.coCtl, 32 + maxGroups * 32)) ||
-            (rc = dev_alloc(sh, &sh->bsc.coPub, maxGroups * 2 * K * nwp)) ||
-            (rc = dev_alloc(sh, &sh->bsc.coPubS, maxGroups * 2 * K * 2)))
-            return rc;
-        sh->bsc.coBars = sh->bsc.coCtl + 32;
-        sh->bsc.coK = (int32_t)K;
-        sh->bsc.coSpin = pe->tu.coopSpin;
-        if (hipHostMalloc(reinterpret_cast<void**>(&sh->dCoopAbort), 4, hipHostMallocDefault) != hipSuccess)
-            return SHD_PE_ENOMEM;
-    }
     if ((rc = ensure_tie(pe, sh))) return rc;
     sh->batchReady = true;
     return SHD_PE_OK;
@@ -906,56 +824,12 @@ static void corrupt_tie_slot(ShdPe* pe, Shard* sh, const std::vector<int32_t>& s
     }
 }
 
-// One round's relax by the cooperative kernel (K workgroups of one XCD per
-// batch): its control state zeroed and the round's per-batch failure flags
-// cleared by the host first.  If the runtime refuses the launch (the grid is
-// not wholly resident) or a barrier wait aborted, the plain relax recomputes
-// the round from scratch (it re-initialises every dist array it relaxes and
-// writes every flag): the rows are never wrong and never missing.
-// A cooperative launch takes every workgroup slot of its device: two of them
-// at once (logical shards of one device, computed by concurrent host
-// threads) could each hold part of the device while waiting for the rest of
-// their own grid.  One at a time per device (the launch is synchronised
-// before the lock is released, for the abort check anyway).
-static std::mutex g_coopMu[64];
-
 // The batch scratch for a launch over the batches at `rows` (inside
 // dBatchRows): the lane offsets are those of the same entries of dLaneOff.
 static BatchScratch scratch_at(const Shard* sh, const int32_t* rows) {
     BatchScratch bs = sh->bsc;
     bs.laneOff = sh->dLaneOff + (rows - sh->dBatchRows);
     return bs;
-}
-
-static int relax_coop(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const int32_t* rows, int32_t rn,
-                      uint8_t* amb, int32_t* dbg) {
-    std::lock_guard<std::mutex> devLock(g_coopMu[sh->device & 63]);
-    const size_t maxGroups = (size_t)sh->plan.cand[sh->plan.coop].grid;
-    HIPCHK(hipMemsetAsync(sh->bsc.coCtl, 0, 128 + maxGroups * 128, sh->stream));
-    HIPCHK(hipMemsetAsync(sh->bsc.flags, 0, (size_t)rn * 4, sh->stream));
-    const bool refused = launch_batch_relax_coop(sh->dg, sh->tab, scratch_at(sh, rows), rows, rn, amb, relax, dbg,
-                                                 sh->dTie, sh->stream) != 0;
-    bool rerun = refused;
-    if (refused) {
-        (void)hipGetLastError();                  // the refusal (the abort word was never copied)
-    } else {
-        HIPCHK(hipGetLastError());
-        HIPCHK(hipMemcpyAsync(sh->dCoopAbort, sh->bsc.coCtl + 17, 4, hipMemcpyDeviceToHost, sh->stream));
-        HIPCHK(hipStreamSynchronize(sh->stream));
-        rerun = *sh->dCoopAbort != 0;
-    }
-    if (rerun) {
-        ++sh->coopAborts;
-        if (pe->tu.debug || pe->tu.tuneLog)
-            std::fprintf(stderr, "[shdpe] shard %d: cooperative relax %s; round recomputed by the plain relax\n",
-                         sh->gindex, refused ? "refused" : "aborted");
-        BatchLaunch plain = relax;
-        plain.coop = 0;
-        HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
-        launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, rows), rows, rn, amb, plain, dbg, sh->dTie, sh->stream, 1);
-        HIPCHK(hipGetLastError());
-    }
-    return SHD_PE_OK;
 }
 
 // One chunk's rows for the exact stage, as the chunk's relax stage leaves them.
@@ -1055,16 +929,10 @@ static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const Ba
         if (timed) HIPCHK(hipEventRecord(sh->evP[0], sh->stream));
         for (int part = 1; part <= 2; ++part) {
             int32_t* const dbgR = sh->dDbg ? sh->dDbg + 16 * r0 : nullptr;
-            if (part == 1 && relax.coop >= 2 && sh->plan.coop >= 0) {
-                if ((rc = relax_coop(pe, sh, relax, sh->dBatchRows + ro, rn, sh->dBatchAmb + ro, dbgR)))
-                    return rc;
-            } else {
-                HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
-                launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, sh->dBatchRows + ro), sh->dBatchRows + ro, rn,
-                                  sh->dBatchAmb + ro,
-                                  part == 1 ? relax : post, dbgR, sh->dTie, sh->stream,
-                                  part == 1 ? 1 : postPart);
-            }
+            HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
+            launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, sh->dBatchRows + ro), sh->dBatchRows + ro, rn,
+                              sh->dBatchAmb + ro, part == 1 ? relax : post, dbgR, sh->dTie, sh->stream,
+                              part == 1 ? 1 : postPart);
             // tests only (SHDPE_TUNE_FAIL_WPE): the relax variant of that wave
             // count flags every batch failed, as a miscompiled variant would
             if (part == 1 && pe->tu.failWpe && relax.wpe == pe->tu.failWpe)
@@ -1578,8 +1446,8 @@ static int tune_filter(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, co
 static void tune_log(const Shard* sh, const TuneSample* s, const TunePick& p, const double best[2]) {
     const BatchPlan& plan = sh->plan;
     for (int k = 0; k < plan.nc; ++k)
-        std::fprintf(stderr, "[shdpe] shard %d tune: %d waves%s %.2f ms (relax %.2f post %.2f) exact rows %ld%s%s%s\n",
-                     sh->gindex, plan.cand[k].wpe, plan.cand[k].coop >= 2 ? " cooperative" : "", s[k].ms,
+        std::fprintf(stderr, "[shdpe] shard %d tune: %d waves %.2f ms (relax %.2f post %.2f) exact rows %ld%s%s%s\n",
+                     sh->gindex, plan.cand[k].wpe, s[k].ms,
                      s[k].msRelax, s[k].msPost, (long)s[k].exact, p.ok[k] ? "" : " (excluded)",
                      k == p.relax ? " <relax" : "", k == p.post ? " <post" : "");
     if (best[1] > 0.0)
@@ -1951,9 +1819,8 @@ static int paths_tier_batch(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w, Exa
         return SHD_PE_OK;
     if ((rc = ensure_batch(pe, sh))) return rc;
     if (!sh->plan.relax.split) return SHD_PE_OK;
-    BatchTrial trial;   // the plan's picks; for a cooperative relax the post variant's plain kernel (as ensure_batch)
-    trial.relax = sh->plan.relax.coop >= 2 ? sh->plan.post : sh->plan.relax;
-    trial.relax.coop = 0;
+    BatchTrial trial;   // the plan's picks
+    trial.relax = sh->plan.relax;
     trial.post = sh->plan.post;
     trial.noTable = true;
     const int32_t LB = trial.relax.lb;
@@ -2384,10 +2251,6 @@ extern "C" int shd_pe_get_stats(const ShdPe* pe, ShdPeStats* out) {
     // compute updates the per-shard stats under mu: snapshot under it too
     // (a call during a compute returns once that compute is done)
     std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
-    for (auto& sp : pe->shards) {                // live per-shard counters into the stats
-        sp->stats.relaxCoopAborts = sp->coopAborts;
-        sp->stats.batchCoop = sp->plan.relax.coop >= 2 ? sp->plan.relax.coop : 0;
-    }
     ShdPeStats t = pe->shards[0]->stats;
     for (size_t i = 1; i < pe->shards.size(); ++i) {
         const ShdPeStats& s = pe->shards[i]->stats;
@@ -2395,7 +2258,6 @@ extern "C" int shd_pe_get_stats(const ShdPe* pe, ShdPeStats* out) {
         t.rowsExact += s.rowsExact;
         t.rowsTieEarly += s.rowsTieEarly;
         t.rowsTieRepaired += s.rowsTieRepaired;
-        t.relaxCoopAborts += s.relaxCoopAborts;
         t.arcsRelaxed += s.arcsRelaxed;
         t.msSparseKernel += s.msSparseKernel;
         t.msExactKernel += s.msExactKernel;
@@ -2443,7 +2305,6 @@ extern "C" int shd_pe_reset_stats(ShdPe* pe) {
         st.batchLanes = keep.batchLanes;
         st.batchWaves = keep.batchWaves;
         st.batchPostWaves = keep.batchPostWaves;
-        sp->coopAborts = 0;
         sp->predClaimed = sp->predGathered = 0;
     }
     pe->msGather = 0.0;

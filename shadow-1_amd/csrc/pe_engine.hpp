@@ -26,12 +26,11 @@ namespace shdpe {
 // from relax / post or from a BatchTrial of the tune.
 struct BatchPlan {
     BatchLaunch cand[4];            // what shd_pe_tune times, in its order: the untuned relax
-                                    // pick, the other of 4 / 8 waves, 6 waves, the cooperative
+                                    // pick, the other of 4 / 8 waves, 6 waves
     int nc = 0;
-    int coop = -1;                  // cand[coop] is the cooperative relax (coop >= 2); -1: none
     BatchLaunch relax{};            // picks in use: the relax launch (with the delta chosen) ...
     BatchLaunch post{};             // ... and, split kernels, the post launch
-    bool tunable() const { return nc > 1 || coop >= 0; }
+    bool tunable() const { return nc > 1; }
 };
 
 // One timed run of shd_pe_tune: the launches to use instead of the plan's
@@ -79,11 +78,7 @@ struct Shard {
     SparseLaunch cfg{};
     int exactGrid = 0, exactHc = 1;
     BatchPlan plan{};
-    int64_t coopAborts = 0;         // cooperative relax launches refused by the runtime or aborted
-                                    // at a barrier, counted together (round rerun plain):
-                                    // relaxCoopAborts
     int64_t predClaimed = 0, predGathered = 0;   // shd_pe_pred_filter_counts (debug counters)
-    int32_t* dCoopAbort = nullptr;  // host-mapped copy target of the abort word
     bool tuned = false;
     BatchScratch bsc{};
     bool batchReady = false;
