@@ -36,9 +36,11 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 9   /* 7: graph property check (shd_pe_graph_props);
+#define SHD_PE_ABI_VERSION 10  /* 7: graph property check (shd_pe_graph_props);
                                   8: fill from row shards (shd_pe_fill_rowstore_shards);
-                                  9: shd_pe_pred_filter_counts */
+                                  9: shd_pe_pred_filter_counts;
+                                  10: shd_pe_create_built (graph build on the device),
+                                      shd_pe_graph_digest */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -161,6 +163,57 @@ void shd_pe_default_options(ShdPeOptions* opt);
  * the order of the unique attached vertices. */
 int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attached,
                   int32_t nAttached, const ShdPeOptions* opt, ShdPe** out);
+
+/* ABI 10: the same engine with a choice of who builds its graph.  The device
+ * build goes from the edge list (uploaded once, 24 B per edge, through
+ * page-locked staging) to the device arrays with kernels and reads the host
+ * copy back; for topologies of ~10^8 edges, where the host build and its
+ * 52 B-per-arc upload are the cost of create.  Every array, on the host and
+ * on the device, is byte-identical to the host build's, so every later call
+ * answers the same.  shd_pe_create(...) is
+ * shd_pe_create_built(..., SHD_PE_BUILD_HOST, NULL, ...).  An unknown
+ * graphBuild is SHD_PE_EINVAL before any other work.  No gfx950 device:
+ * SHD_PE_ENODEV, never a silent host run (the device build looks for the
+ * device before it reads the graph, the host build after). */
+#define SHD_PE_BUILD_HOST   0   /* shd_pe_create's build */
+#define SHD_PE_BUILD_DEVICE 1   /* device build; hands off to the host form where it must */
+#define SHD_PE_BUILD_AUTO   2   /* device build from a measured edge count up (3,126,250:
+                                   a complete graph of 2,500 vertices), else host */
+typedef struct ShdPeBuildInfo {          /* optional */
+    int32_t built;        /* SHD_PE_BUILD_HOST or _DEVICE: what made the graph */
+    int32_t handedOff;    /* 1: device build asked for or chosen, host form made it */
+    int32_t handOffWhy;   /* 0 none, 1 parallel edges (the merge rules stay on the host),
+                             2 vertex count past the kernels' limit (131072; also an edge
+                             count past 2^31 - 1) */
+    int64_t deviceBytesPeak;             /* temporaries of the build, outputs excluded */
+    double  msUpload, msKernels, msReadback, msHostBuild, msCreate;   /* wall ms; msReadback
+                             includes the arc latency statistics pass over the read-back arcs */
+} ShdPeBuildInfo;
+int shd_pe_create_built(const ShdPeGraphDesc* graph, const int32_t* attached, int32_t nAttached,
+                        const ShdPeOptions* opt, int32_t graphBuild, ShdPeBuildInfo* info,
+                        ShdPe** out);
+/* Under SHD_PE_DEBUG_ENV, SHDPE_BUILD_MAXN lowers the vertex limit of the
+ * device build (tests reach the hand-off at a small shape). */
+
+/* Test and diagnosis helper: one 64-bit digest per graph array of local shard
+ * `shard`.  Each digest is the wrapping sum over the array's elements of
+ * splitmix64(bits ^ index * 0x9e3779b97f4a7c15), bits zero-extended; absent
+ * arrays digest to 0.  The host arrays are summed on the host, the device
+ * arrays by a kernel where they sit.  *count receives the number of entries
+ * (64); SHD_PE_EINVAL when cap is smaller.  The order:
+ *    0..17  HostGraph: rowPtr col lat rel outToIn inPtr inCol inLat inRel
+ *           foldLat selfPathRel vrel selfLat selfRel selfMinLat selfMinRel
+ *           hasSelf edgeCount
+ *   18      HostGraph's scalars as seven 64-bit words: n, directed, nEdges,
+ *           latFold, isComplete, meanArcLatency, minArcLatency
+ *   19..40  the shard's graph in the caller's vertex ids (aux kernels), as
+ *           DevGraph declares it: rowPtr col lat arcs (two 64-bit words per
+ *           arc) arc3 (three 32-bit words per arc) rel inPtr inCol inLat inRel
+ *           outToIn vrel selfLat selfRel hasSelf selfMinLat selfMinRel
+ *           attached isAttached heavyBits flat srel
+ *   41..63  the path kernels' graph where the batched path relabelled it
+ *           (else zeros): the same 22 arrays, then oldId */
+int shd_pe_graph_digest(ShdPe* pe, int32_t shard, uint64_t* out, int32_t cap, int32_t* count);
 
 void shd_pe_destroy(ShdPe* pe);
 

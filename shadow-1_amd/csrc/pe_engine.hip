@@ -31,6 +31,7 @@
 #include <thread>
 #include <vector>
 
+#include "pe_build.hpp"
 #include "pe_engine.hpp"
 #include "pe_plan.hpp"
 
@@ -396,7 +397,9 @@ static int open_device(Shard* sh) {
 
 // Device state of one shard: graph upload, stream, events, kernel config.
 // `rl` (null: none) is what the path kernels get instead of the caller's ids.
-static int init_shard(ShdPe* pe, Shard* sh, const Relabelled* rl) {
+// `built` (null: none) is the device build's graph: the first shard on its
+// device adopts the arrays as its dgAux instead of uploading HostGraph.
+static int init_shard(ShdPe* pe, Shard* sh, const Relabelled* rl, BuiltGraph* built) {
     const HostGraph& g = pe->hg;
     int rc = open_device(sh);
     if (rc) return rc;
@@ -408,7 +411,15 @@ static int init_shard(ShdPe* pe, Shard* sh, const Relabelled* rl) {
         hipEventCreate(&sh->evP[2]) != hipSuccess)
         return SHD_PE_ENODEV;
     if ((rc = configure(pe, sh))) return rc;
-    if ((rc = upload_graph(g, pe->attached, nullptr, sh, &sh->dgAux))) return rc;
+    if (built && !built->adopted && !built->allocs.empty() && built->device == sh->device) {
+        sh->allocs.insert(sh->allocs.end(), built->allocs.begin(), built->allocs.end());
+        built->adopted = true;
+        sh->dgAux = built->dg;
+        if ((rc = finish_built_graph(pe->attached, sh->cfg.heavyDeg, sh->stream, &sh->dgAux, &sh->allocs)))
+            return rc;
+    } else if ((rc = upload_graph(g, pe->attached, nullptr, sh, &sh->dgAux))) {
+        return rc;
+    }
     sh->dg = sh->dgAux;
     if (rl && (rc = upload_graph(rl->g, rl->attached, &rl->oldOf, sh, &sh->dg))) return rc;
     sh->stats.mode = pe->mode;
@@ -419,10 +430,57 @@ static int init_shard(ShdPe* pe, Shard* sh, const Relabelled* rl) {
     return SHD_PE_OK;
 }
 
-extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attached,
-                             int32_t nAttached, const ShdPeOptions* opt, ShdPe** out) {
+// The HIP ordinals of the engine's shards, each in range.
+static int resolve_devices(const ShdPeOptions& o, std::vector<int>& devs) {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SHD_PE_ENODEV;
+    devs.resize(o.nDevices);
+    for (int i = 0; i < o.nDevices; ++i) {
+        devs[i] = o.devices ? o.devices[i] : o.device + i;
+        if (devs[i] < 0 || devs[i] >= ndev) return SHD_PE_ENODEV;
+    }
+    return SHD_PE_OK;
+}
+
+static double wall_ms(std::chrono::steady_clock::time_point t0) {
+    return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+}
+
+// The engine's graph by the device build on the first shard's device, or by
+// the host form where the device build hands off.
+static int build_graph_on_device(const ShdPeGraphDesc* graph, const ShdPeOptions& o, const std::vector<int>& devs,
+                                 HostGraph* hg, BuiltGraph* built, ShdPeBuildInfo* info) {
+    Shard probe;
+    probe.device = devs[0];
+    int rc = open_device(&probe);
+    if (rc) return rc;
+    int32_t maxN = BUILD_MAX_N;
+    if (o.debugFlags & SHD_PE_DEBUG_ENV) {
+        const char* e = std::getenv("SHDPE_BUILD_MAXN");
+        if (e && *e && std::atoi(e) > 0) maxN = std::min(maxN, (int32_t)std::atoi(e));
+    }
+    if ((rc = device_build_graph(graph, devs[0], maxN, hg, built, info))) return rc;
+    info->built = info->handedOff ? SHD_PE_BUILD_HOST : SHD_PE_BUILD_DEVICE;
+    if (!info->handedOff) return SHD_PE_OK;
+    built->release();                    // device memory released before the host run
+    *hg = HostGraph{};
+    const auto t0 = std::chrono::steady_clock::now();
+    rc = build_host_graph(graph, hg);
+    info->msHostBuild = wall_ms(t0);
+    return rc;
+}
+
+// Create, both entry points: everything after the graph exists is shared.
+static int create_engine(const ShdPeGraphDesc* graph, const int32_t* attached, int32_t nAttached,
+                         const ShdPeOptions* opt, int32_t graphBuild, ShdPeBuildInfo* infoOut, ShdPe** out) {
+    if (graphBuild != SHD_PE_BUILD_HOST && graphBuild != SHD_PE_BUILD_DEVICE && graphBuild != SHD_PE_BUILD_AUTO)
+        return SHD_PE_EINVAL;
+    ShdPeBuildInfo info;
+    std::memset(&info, 0, sizeof(info));
+    if (infoOut) *infoOut = info;
     if (!out || !graph || nAttached <= 0 || !attached) return SHD_PE_EINVAL;
     *out = nullptr;
+    const auto tCreate = std::chrono::steady_clock::now();
     std::unique_ptr<ShdPe> pe(new (std::nothrow) ShdPe());
     if (!pe) return SHD_PE_ENOMEM;
     if (opt) pe->opt = *opt; else shd_pe_default_options(&pe->opt);
@@ -431,7 +489,22 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
     if (o.shardCount <= 0) o.shardCount = 1;
     if (o.shardIndex < 0 || o.shardIndex >= o.shardCount || o.nDevices > 64) return SHD_PE_EINVAL;
     read_tuning(pe->tu, o.debugFlags);
-    int rc = build_host_graph(graph, &pe->hg);
+    const bool onDevice = graphBuild == SHD_PE_BUILD_DEVICE ||
+                          (graphBuild == SHD_PE_BUILD_AUTO && graph->nEdges >= BUILD_AUTO_MIN_EDGES);
+    std::vector<int> devs;
+    BuiltGraph built;                    // declared before the shards' uploads: what no shard adopts is freed on return
+    int rc;
+    if (onDevice) {
+        // the device comes first here: without one there is no build to run
+        if ((rc = resolve_devices(o, devs))) return rc;
+        rc = build_graph_on_device(graph, o, devs, &pe->hg, &built, &info);
+    } else {
+        const auto t0 = std::chrono::steady_clock::now();
+        rc = build_host_graph(graph, &pe->hg);
+        info.built = SHD_PE_BUILD_HOST;
+        info.msHostBuild = wall_ms(t0);
+    }
+    if (infoOut) *infoOut = info;
     if (rc) return rc;
     const HostGraph& g = pe->hg;
     pe->posOf.assign(g.n, -1);
@@ -445,13 +518,7 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
     }
     const int32_t T = (int32_t)pe->attached.size();
     // ---- devices ----
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return SHD_PE_ENODEV;
-    std::vector<int> devs(o.nDevices);
-    for (int i = 0; i < o.nDevices; ++i) {
-        devs[i] = o.devices ? o.devices[i] : o.device + i;
-        if (devs[i] < 0 || devs[i] >= ndev) return SHD_PE_ENODEV;
-    }
+    if (devs.empty() && (rc = resolve_devices(o, devs))) return rc;
     pe->mode = select_mode(pe->hg, o.forceMode, pe->tu.denseMin);
     pe->G = o.shardCount * o.nDevices;
     pe->firstShard = o.shardIndex * o.nDevices;
@@ -485,7 +552,7 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
         sh->rowStart = pe->bounds[sh->gindex];
         sh->rowCount = pe->bounds[sh->gindex + 1] - sh->rowStart;
         sh->fullOwner = std::find(devs.begin(), devs.begin() + i, devs[i]) == devs.begin() + i;
-        rc = init_shard(pe.get(), sh.get(), relabel ? &rl : nullptr);
+        rc = init_shard(pe.get(), sh.get(), relabel ? &rl : nullptr, &built);
         pe->shards.push_back(std::move(sh));
         if (rc) { shd_pe_destroy(pe.release()); return rc; }
     }
@@ -498,8 +565,75 @@ extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attache
     pe->rowDone.reset(new (std::nothrow) std::atomic<uint8_t>[T]);
     if (!pe->rowDone) { shd_pe_destroy(pe.release()); return SHD_PE_ENOMEM; }
     for (int32_t i = 0; i < T; ++i) pe->rowDone[i].store(0, std::memory_order_relaxed);
+    if (infoOut) {
+        info.msCreate = wall_ms(tCreate);
+        *infoOut = info;
+    }
     *out = pe.release();
     return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_create(const ShdPeGraphDesc* graph, const int32_t* attached,
+                             int32_t nAttached, const ShdPeOptions* opt, ShdPe** out) {
+    return create_engine(graph, attached, nAttached, opt, SHD_PE_BUILD_HOST, nullptr, out);
+}
+
+extern "C" int shd_pe_create_built(const ShdPeGraphDesc* graph, const int32_t* attached, int32_t nAttached,
+                                   const ShdPeOptions* opt, int32_t graphBuild, ShdPeBuildInfo* info,
+                                   ShdPe** out) {
+    return create_engine(graph, attached, nAttached, opt, graphBuild, info, out);
+}
+
+// shd_pe_graph_digest: see the header for the order of the entries.
+// (undirected: the IN arrays alias the OUT arrays and digest like them)
+static int digest_dev_graph(Shard* sh, const DevGraph& d, int64_t nArcs, bool withOldId, uint64_t* dAcc,
+                            uint64_t* out) {
+    const int64_t n = d.n, np1 = d.n + 1;
+    struct A { const void* p; int w; int64_t c; };
+    const A arr[] = {
+        {d.rowPtr, 4, np1}, {d.col, 4, nArcs}, {d.lat, 8, nArcs}, {d.arcs, 8, 2 * nArcs}, {d.arc3, 4, 3 * nArcs},
+        {d.rel, 8, nArcs}, {d.inPtr, 4, np1}, {d.inCol, 4, nArcs}, {d.inLat, 8, nArcs}, {d.inRel, 8, nArcs},
+        {d.outToIn, 4, nArcs}, {d.vrel, 8, n}, {d.selfLat, 8, n}, {d.selfRel, 8, n}, {d.hasSelf, 1, n},
+        {d.selfMinLat, 8, n}, {d.selfMinRel, 8, n}, {d.attached, 4, d.T}, {d.isAttached, 1, n},
+        {d.heavyBits, 4, (n + 31) / 32}, {d.flat, 8, nArcs}, {d.srel, 8, nArcs}, {d.oldId, 4, n}};
+    const int count = withOldId ? 23 : 22;
+    for (int i = 0; i < count; ++i) {
+        const int rc = device_array_digest(arr[i].p, arr[i].w, arr[i].c, dAcc, sh->stream, &out[i]);
+        if (rc) return rc;
+    }
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_graph_digest(ShdPe* pe, int32_t shard, uint64_t* out, int32_t cap, int32_t* count) {
+    constexpr int32_t N_ENTRIES = 64;
+    if (count) *count = N_ENTRIES;
+    if (!pe || !out || shard < 0 || shard >= (int32_t)pe->shards.size() || cap < N_ENTRIES) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lock(pe->mu);
+    for (int i = 0; i < N_ENTRIES; ++i) out[i] = 0;
+    const HostGraph& g = pe->hg;
+    auto hd = [&](const auto& v) { return host_array_digest(v.data(), (int)sizeof(v[0]), (int64_t)v.size()); };
+    int k = 0;
+    out[k++] = hd(g.rowPtr); out[k++] = hd(g.col); out[k++] = hd(g.lat); out[k++] = hd(g.rel);
+    out[k++] = hd(g.outToIn); out[k++] = hd(g.inPtr); out[k++] = hd(g.inCol); out[k++] = hd(g.inLat);
+    out[k++] = hd(g.inRel); out[k++] = hd(g.foldLat); out[k++] = hd(g.selfPathRel); out[k++] = hd(g.vrel);
+    out[k++] = hd(g.selfLat); out[k++] = hd(g.selfRel); out[k++] = hd(g.selfMinLat); out[k++] = hd(g.selfMinRel);
+    out[k++] = hd(g.hasSelf); out[k++] = hd(g.edgeCount);
+    {
+        uint64_t s[7] = {(uint64_t)g.n, (uint64_t)g.directed, (uint64_t)g.nEdges, g.latFold ? 1u : 0u,
+                         g.isComplete ? 1u : 0u, 0, 0};
+        std::memcpy(&s[5], &g.meanArcLatency, 8);
+        std::memcpy(&s[6], &g.minArcLatency, 8);
+        out[k++] = host_array_digest(s, 8, 7);
+    }
+    Shard* sh = pe->shards[shard].get();
+    HIPCHK(hipSetDevice(sh->device));
+    uint64_t* dAcc = nullptr;
+    if (hipMalloc((void**)&dAcc, 8) != hipSuccess) return SHD_PE_ENOMEM;
+    int rc = digest_dev_graph(sh, sh->dgAux, g.nArcs(), false, dAcc, &out[k]);
+    k += 22;
+    if (!rc && sh->dg.rowPtr != sh->dgAux.rowPtr) rc = digest_dev_graph(sh, sh->dg, g.nArcs(), true, dAcc, &out[k]);
+    (void)hipFree(dAcc);
+    return rc;
 }
 
 // The field arrays of a table of `rows` rows at position 0 (pred only with

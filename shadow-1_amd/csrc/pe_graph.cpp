@@ -334,6 +334,12 @@ int build_host_graph(const ShdPeGraphDesc* d, HostGraph* g) {
         else if (!complete) break;
     }
     g->isComplete = complete;
+    arc_latency_stats(g);
+    return SHD_PE_OK;
+}
+
+void arc_latency_stats(HostGraph* g) {
+    const int64_t nArcsM = g->nArcs();
     // mean arc latency (bucket width): fixed 64-chunk partial sums added in
     // order, so the value does not depend on the thread count
     std::vector<double> part(64, 0.0), pmin(64, INFINITY);
@@ -348,7 +354,6 @@ int build_host_graph(const ShdPeGraphDesc* d, HostGraph* g) {
     for (double x : pmin) mn = std::min(mn, x);
     g->minArcLatency = nArcsM ? mn : 0.0;
     g->meanArcLatency = nArcsM ? sum / (double)nArcsM : 1.0;
-    return SHD_PE_OK;
 }
 
 int host_direct_path(const HostGraph& g, int32_t s, int32_t t, double* lat, double* rel) {

@@ -68,6 +68,9 @@ struct HostGraph {
 
 // Validate + build (topology.c:1041-1124 checks, igraph_add_edges order).
 int build_host_graph(const ShdPeGraphDesc* d, HostGraph* g);
+// meanArcLatency / minArcLatency from g->lat: the last pass of build_host_graph,
+// and of the device build (pe_build.hip) over the arcs it read back
+void arc_latency_stats(HostGraph* g);
 
 // _topology_lookupDirectPath (topology.c:1877-1927)
 int host_direct_path(const HostGraph& g, int32_t s, int32_t t, double* lat, double* rel);

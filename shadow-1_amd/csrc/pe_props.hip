@@ -42,6 +42,7 @@
 #include <cstdlib>
 #include <cstring>
 
+#include "pe_stage.hpp"
 #include "shd_pathengine.h"
 
 namespace shdpe {
@@ -350,14 +351,12 @@ __global__ __launch_bounds__(PROPS_BLOCK) void k_props_summary(const int32_t* __
 }
 
 // ---- host side ---------------------------------------------------------------
-constexpr size_t PROPS_STAGE_BYTES = (size_t)16 << 20;
-
 struct PropsRun {
     int32_t device = 0, n = 0;
     int64_t m = 0;
     hipStream_t stream = nullptr;
-    hipEvent_t ev0 = nullptr, ev1 = nullptr, evStage[2] = {nullptr, nullptr};
-    void* stage[2] = {nullptr, nullptr};
+    hipEvent_t ev0 = nullptr, ev1 = nullptr;
+    Stager stage;                             // the edge endpoints' way up (pe_stage.hpp)
     int32_t *dFrom = nullptr, *dTo = nullptr;
     int32_t *dCnt = nullptr, *dM = nullptr, *dA = nullptr, *dB = nullptr, *dW = nullptr;
     uint8_t *dSelf = nullptr, *dLive = nullptr, *dIn = nullptr, *dOut = nullptr;
@@ -373,9 +372,8 @@ struct PropsRun {
         for (void* p : {(void*)dFrom, (void*)dTo, (void*)dCnt, (void*)dM, (void*)dA, (void*)dB, (void*)dW,
                         (void*)dSelf, (void*)dLive, (void*)dIn, (void*)dOut})
             if (p) (void)hipFree(p);
-        for (void* p : {stage[0], stage[1], (void*)hW})
-            if (p) (void)hipHostFree(p);
-        for (hipEvent_t e : {ev0, ev1, evStage[0], evStage[1]})
+        if (hW) (void)hipHostFree(hW);
+        for (hipEvent_t e : {ev0, ev1})
             if (e) (void)hipEventDestroy(e);
         (void)hipStreamDestroy(stream);
     }
@@ -396,38 +394,6 @@ static int props_alloc(T** p, size_t count) {
     if (hipMalloc((void**)p, std::max<size_t>(count, 1) * sizeof(T)) != hipSuccess) {
         *p = nullptr;
         return SHD_PE_ENOMEM;
-    }
-    return SHD_PE_OK;
-}
-
-// the edge endpoints as given: a page-locked array goes by DMA directly, a
-// pageable one in chunks through two page-locked staging buffers
-static int props_upload(PropsRun& r, int32_t* dst, const int32_t* src, size_t bytes) {
-    if (bytes == 0) return SHD_PE_OK;
-    hipPointerAttribute_t attr;
-    const bool locked = hipPointerGetAttributes(&attr, src) == hipSuccess && attr.type == hipMemoryTypeHost;
-    (void)hipGetLastError();                   // an unregistered pointer may report an error: not one of ours
-    if (locked) {
-        PRCHK(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, r.stream));
-        return SHD_PE_OK;
-    }
-    // both endpoint arrays have `bytes` bytes: the buffers of the first serve the second; a
-    // second buffer only where there is a second chunk (page-locking is the call's fixed cost)
-    const size_t chunk = std::min(PROPS_STAGE_BYTES, bytes);
-    for (int b = 0; b < (bytes > chunk ? 2 : 1); ++b) {
-        if (!r.stage[b] && hipHostMalloc(&r.stage[b], chunk) != hipSuccess) {
-            r.stage[b] = nullptr;
-            return SHD_PE_ENOMEM;
-        }
-        if (!r.evStage[b]) PRCHK(hipEventCreateWithFlags(&r.evStage[b], hipEventDisableTiming));
-    }
-    int b = 0;
-    for (size_t off = 0; off < bytes; off += chunk, b = (bytes > chunk ? b ^ 1 : 0)) {
-        const size_t len = std::min(chunk, bytes - off);
-        PRCHK(hipEventSynchronize(r.evStage[b]));         // the buffer's previous DMA (done at once if none)
-        std::memcpy(r.stage[b], (const char*)src + off, len);
-        PRCHK(hipMemcpyAsync((char*)dst + off, r.stage[b], len, hipMemcpyHostToDevice, r.stream));
-        PRCHK(hipEventRecord(r.evStage[b], r.stream));
     }
     return SHD_PE_OK;
 }
@@ -534,6 +500,7 @@ static int props_device(PropsRun& r, const ShdPeGraphDesc* g, ShdPeGraphProps* o
     const bool directed = g->directed != 0;
     const size_t nb = (size_t)n;
     PRCHK(hipStreamCreateWithFlags(&r.stream, hipStreamNonBlocking));
+    r.stage.stream = r.stream;
     PRCHK(hipEventCreate(&r.ev0));
     PRCHK(hipEventCreate(&r.ev1));
     PRRC(props_alloc(&r.dFrom, (size_t)m));
@@ -556,8 +523,8 @@ static int props_device(PropsRun& r, const ShdPeGraphDesc* g, ShdPeGraphProps* o
     r.vGrid = (unsigned)((nb + PROPS_BLOCK - 1) / PROPS_BLOCK);
     r.eGrid = (unsigned)std::max<int64_t>(1, std::min<int64_t>((m + PROPS_BLOCK - 1) / PROPS_BLOCK, PROPS_MAX_GRID));
 
-    PRRC(props_upload(r, r.dFrom, g->edgeFrom, (size_t)m * 4));
-    PRRC(props_upload(r, r.dTo, g->edgeTo, (size_t)m * 4));
+    PRRC(r.stage.upload(r.dFrom, g->edgeFrom, (size_t)m * 4));
+    PRRC(r.stage.upload(r.dTo, g->edgeTo, (size_t)m * 4));
     std::memset(r.hW, 0, W_COUNT * sizeof(int32_t));
     r.hW[W_LIVE] = n;
     r.hW[W_FIRSTINC] = INT_MAX;

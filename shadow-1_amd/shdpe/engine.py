@@ -23,6 +23,8 @@ F_UNREACHABLE, F_NOEDGE, F_ZEROLAT, F_DIRECT, F_EXACT = 0x01, 0x02, 0x04, 0x08, 
 F_FAILED = F_UNREACHABLE | F_NOEDGE
 F_INVALID = 0x80
 FILL_PREFER_DIRECT, FILL_DIRECT_PAIRS = 0x1, 0x2
+BUILD_HOST, BUILD_DEVICE, BUILD_AUTO = 0, 1, 2
+GRAPH_DIGEST_ENTRIES = 64
 
 EXPORTS = [
     "shd_pe_default_options", "shd_pe_create", "shd_pe_destroy", "shd_pe_strerror",
@@ -51,6 +53,7 @@ EXPORTS = [
     "shd_pe_attach_set_chunk", "shd_pe_attach_timing",
     "shd_pe_get_paths", "shd_pe_paths_info",
     "shd_pe_graph_props", "shd_pe_graph_props_host",
+    "shd_pe_create_built", "shd_pe_graph_digest",
 ]
 VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
 VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
@@ -132,6 +135,13 @@ class GraphPropsInfoC(C.Structure):
     """ShdPeGraphPropsInfo"""
     _fields_ = [("sweeps", C.c_int64), ("rounds", C.c_int64), ("handedOff", C.c_int32),
                 ("usDevice", C.c_int64), ("usCall", C.c_int64)]
+
+
+class BuildInfoC(C.Structure):
+    """ShdPeBuildInfo"""
+    _fields_ = [("built", C.c_int32), ("handedOff", C.c_int32), ("handOffWhy", C.c_int32),
+                ("deviceBytesPeak", C.c_int64), ("msUpload", C.c_double), ("msKernels", C.c_double),
+                ("msReadback", C.c_double), ("msHostBuild", C.c_double), ("msCreate", C.c_double)]
 
 
 class EngineError(RuntimeError):
@@ -241,6 +251,8 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_paths_info": (C.c_int, [vp, vp, i32]),
         "shd_pe_graph_props": (C.c_int, [vp, i32, i32, vp, vp, vp]),
         "shd_pe_graph_props_host": (C.c_int, [vp, vp, vp]),
+        "shd_pe_create_built": (C.c_int, [vp, vp, i32, vp, i32, vp, vp]),
+        "shd_pe_graph_digest": (C.c_int, [vp, i32, vp, i32, vp]),
     }
     # ABI-3 ... ABI-8 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
@@ -251,7 +263,8 @@ def load_library(path: str = LIB_PATH):
                 "shd_pe_attach_timing", "shd_pe_get_paths",
                 "shd_pe_paths_info", "shd_pe_graph_props",
                 "shd_pe_graph_props_host", "shd_pe_fill_rowstore_shards",
-                "shd_topology_fill_shards"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_topology_fill_shards", "shd_pe_create_built",
+                "shd_pe_graph_digest"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -353,10 +366,13 @@ class Engine:
 
     def __init__(self, top, attached, device: int = 0, delta: float = 0.0,
                  store_pred: bool = True, force_mode: int = 0, devices=None,
-                 shard_index: int = 0, shard_count: int = 1, debug_flags: int = 0):
+                 shard_index: int = 0, shard_count: int = 1, debug_flags: int = 0,
+                 graph_build: int | None = None):
         """devices: list of HIP ordinals, one row shard each (repeats = logical
         shards on one device); shard_index/shard_count: this process's engine
-        among several (multi-process row shards)."""
+        among several (multi-process row shards); graph_build: None is
+        shd_pe_create, BUILD_HOST / BUILD_DEVICE / BUILD_AUTO go through
+        shd_pe_create_built (build_info() then tells what made the graph)."""
         lib = load_library()
         self._lib = lib
         self.top = top
@@ -372,9 +388,16 @@ class Engine:
             o.nDevices, o.devices = int(self._devs.shape[0]), _p(self._devs)
         att = np.ascontiguousarray(attached, dtype=np.int32)
         h = C.c_void_p()
-        rc = lib.shd_pe_create(C.byref(d), _p(att), att.shape[0], C.byref(o), C.byref(h))
+        self._build_info = BuildInfoC()
+        if graph_build is None:
+            rc = lib.shd_pe_create(C.byref(d), _p(att), att.shape[0], C.byref(o), C.byref(h))
+            what = "shd_pe_create"
+        else:
+            rc = lib.shd_pe_create_built(C.byref(d), _p(att), att.shape[0], C.byref(o), int(graph_build),
+                                         C.byref(self._build_info), C.byref(h))
+            what = "shd_pe_create_built"
         if rc:
-            raise EngineError(rc, "shd_pe_create")
+            raise EngineError(rc, what)
         self.h = h
         self.store_pred = store_pred
         T = lib.shd_pe_num_attached(h)
@@ -384,6 +407,19 @@ class Engine:
         st, cnt = C.c_int32(), C.c_int32()
         lib.shd_pe_owned_range(h, C.byref(st), C.byref(cnt))
         self.owned = (st.value, cnt.value)
+
+    def build_info(self) -> dict:
+        """ShdPeBuildInfo of this engine's create (all zero after shd_pe_create)."""
+        return {k: getattr(self._build_info, k) for k, _ in BuildInfoC._fields_}
+
+    def graph_digest(self, shard: int = 0) -> np.ndarray:
+        """shd_pe_graph_digest: one 64-bit digest per graph array of a local
+        shard, HostGraph's arrays first, then the device arrays."""
+        out = np.zeros(GRAPH_DIGEST_ENTRIES, np.uint64)
+        cnt = C.c_int32()
+        self._chk(self._lib.shd_pe_graph_digest(self.h, int(shard), _p(out), out.shape[0], C.byref(cnt)),
+                  "shd_pe_graph_digest")
+        return out[:cnt.value]
 
     def shard_bounds(self):
         G = self._lib.shd_pe_num_shards(self.h)
