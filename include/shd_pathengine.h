@@ -36,11 +36,12 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 10  /* 7: graph property check (shd_pe_graph_props);
+#define SHD_PE_ABI_VERSION 11  /* 7: graph property check (shd_pe_graph_props);
                                   8: fill from row shards (shd_pe_fill_rowstore_shards);
                                   9: shd_pe_pred_filter_counts;
                                   10: shd_pe_create_built (graph build on the device),
-                                      shd_pe_graph_digest */
+                                      shd_pe_graph_digest;
+                                  11: shd_pe_post_split_info */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -507,6 +508,13 @@ int shd_pe_reset_stats(ShdPe* pe);
  * on-demand predecessor pass claimed, and the in-arcs it gathered -- equal
  * without the predecessor filter, fewer where the relax flagged in-arcs. */
 int shd_pe_pred_filter_counts(const ShdPe* pe, int64_t* claimed, int64_t* gathered);
+/* The batched post kernel of this process's first shard: *split = 1 when it
+ * runs as two kernels (predecessor part, label part), 0 as one; *labelWaves =
+ * the label part's waves per SIMD (0 when not split; ShdPeStats.batchPostWaves
+ * then names the predecessor part's); *redoBatches = batches, over all
+ * shards, that the label part handed to the one post kernel's second attempt
+ * since the last shd_pe_reset_stats. */
+int shd_pe_post_split_info(const ShdPe* pe, int32_t* split, int32_t* labelWaves, int64_t* redoBatches);
 
 /* ---- batched helpers on the device ------------
  * The per-query lookups below, for many queries in one call: inputs and

@@ -89,15 +89,22 @@ struct alignas(16) BCtrl {
     unsigned int dProcs, dArcs, dLanes;
     unsigned int dWhy;   // SHDPE_DIAG_WHY builds: why the batch's rows left the fast path
     long long t0, t1, t2, t3, t4;
-    int spare;           // unused, zeroed with the block: without it the init's stores merge
-                         // differently and every instantiation's register allocation moves
-                         // (3 fewer VGPR spills each: a change to measure on its own)
     // SHD_PE_DEBUG_COUNTERS only: in-arcs of the entries the on-demand
     // predecessor pass claimed, and the in-arcs it gathered (the filter)
     unsigned int dClaim, dGath;
 };
 static_assert(sizeof(BCtrl) <= 128, "batch control block");
 constexpr int BCTRL_BYTES = 128;
+
+// PART 5 (predecessor part): entries of its heavy list, behind the pending
+// bitmaps in an LDS of its own size (batch_lds_bytes): 4,096, fewer when the
+// bitmaps leave less of the CU's 160 KB (1 KB of which stays free for the
+// kernel's static __shared__ arrays -- tieSlot, laneRow, tieThr, nextB, 516 B
+// at LB 32: a dynamic size that fills the whole LDS makes the launch invalid)
+__host__ __device__ constexpr int pred_heavy_cap(int nwp, bool gbits) {
+    const int room = (160 * 1024 - 1024 - BCTRL_BYTES - (gbits ? 0 : 8 * nwp)) / 4;
+    return room < 0 ? 0 : room < 4096 ? room : 4096;
+}
 
 // SHDPE_DIAG_WHY (diagnostic builds only, tools/build_variant.sh -D...): per
 // batch, the reasons its rows went to the exact kernel, in dbg[16 b + 1]:
@@ -278,7 +285,17 @@ __device__ __noinline__ double fold_rel_batch(const double* __restrict__ vrel,
 // export -- each with its own register budget.  PART 4: PART 2 without the row
 // writer's stores (the pass of shd_pe_get_paths, which wants the round's
 // distances, ambiguity bytes and tie export only): its own instantiation, so
-// the post kernel keeps its code.
+// the post kernel keeps its code.  PART 5 / 6: PART 2's first attempt cut in
+// two kernels at the one place where only the batch's `failed` bit crosses
+// (flags[batch]): PART 5 runs the on-demand predecessor pass and the Bellman
+// verdict, PART 6 the label walks, the row writer and the deferred tie-export
+// request, each with its own register budget and its own LDS (pred_heavy_cap /
+// the walk stacks).  Their label records are per BATCH (bs.LB holds a round's),
+// not per workgroup.  A batch that needs PART 2's second attempt (a tree
+// deeper than WALK_BUDGET, a tie batch without a deferred-export buffer)
+// writes no row in PART 6 and is appended to bs.redo; PART 2 launched with
+// bs.redoRun then runs over that list and starts at the full pass.  The order
+// between the kernels is the stream's.
 template <int LB, int WPE, bool GB, int PART>
 __global__ __launch_bounds__(BT_THREADS) __attribute__((amdgpu_waves_per_eu(WPE)))
 void k_batch_rows(DevGraph g0, DevTable tab0,
@@ -288,9 +305,10 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                                                            double delta, int32_t* dbg,
                                                            const TieBuf* __restrict__ tieDesc) {
     constexpr bool NOTAB = PART == 4;
+    constexpr bool PRED = PART == 5, LABEL = PART == 6;
     // the plain relax with LDS bitmaps flags in-arcs for the predecessor filter
     constexpr bool HITS = PART == 1 && !GB;
-    constexpr int PT = NOTAB ? 2 : PART;
+    constexpr int PT = NOTAB || PRED || LABEL ? 2 : PART;
     constexpr int BV = BCfg<WPE>::BV;
     constexpr int SMAX = BCfg<WPE>::SMAX;
     // the light-vertex relax loop and the predecessor pass are software-
@@ -338,12 +356,18 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
     for (;;) {
         if (tid == 0) nextB = atomicAdd(bs.next, 1);
         __syncthreads();
-        const int b = nextB;
-        if (b >= nBatches) break;
+        int b = nextB;
+        if (PART == 2 && bs.redoRun) {     // the redo launch: the batches PART 6 listed
+            if (b >= as_global(bs.redo)[0]) break;
+            b = as_global(bs.redo)[REDO_LIST + b];
+        } else if (b >= nBatches) {
+            break;
+        }
         const int row = batchRows[(size_t)b * LB + l];
         const int src = row >= 0 ? g.attached[row] : -1;
         if (gid == 0) laneRow[l] = row;
         if constexpr (PT != 0) D = as_global(bs.D + (size_t)b * SE);
+        if constexpr (PRED || LABEL) LBL = as_global(bs.LB + (size_t)b * SE);
         // predecessor filter (split kernels): the batch's in-arc flags, one
         // bit per in-arc slot -- the relax sets bit outToIn[a] when some active
         // lane's pre-check of arc a finds dist[u] + w <= dist[x] (every arc
@@ -372,7 +396,8 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                     for (int i = tid; i < cnt16; i += NT) H4[i] = make_uint4(0u, 0u, 0u, 0u);
                 }
             }
-            for (int w = tid; w < nwp; w += NT) { any0.st(w, 0u); any1.st(w, 0u); }
+            if constexpr (!LABEL)
+                for (int w = tid; w < nwp; w += NT) { any0.st(w, 0u); any1.st(w, 0u); }
             if (tid == 0) {
                 ctl->qtail = 0;
                 ctl->qhead = 0;
@@ -387,7 +412,6 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 ctl->dProcs = ctl->dArcs = ctl->dLanes = 0u;
                 ctl->dWhy = 0u;
                 ctl->dClaim = ctl->dGath = 0u;
-                ctl->spare = 0;
             }
         }
         fence_wg();
@@ -434,8 +458,9 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
 #endif
         uint32_t needMask = 0u;
         bool lastFull = true;     // the final attempt ran the full predecessor pass
-        for (int attempt = 0;; ++attempt) {
-        const bool fullPred = PT != 2 || attempt > 0;
+        // (the redo launch starts at the full pass: what attempt 1 does)
+        for (int attempt = PART == 2 && bs.redoRun ? 1 : 0;; ++attempt) {
+        const bool fullPred = !(PRED || LABEL) && (PT != 2 || attempt > 0);
         if (attempt > 0) DIAG_WHY(64u);
         if (attempt > 0) {
             if (tid == 0) {
@@ -794,6 +819,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         }   // PT != 2
         if (dbg && tid == 0) ctl->t1 = (long long)clock64();
         if constexpr (PT == 1) break;
+        if constexpr (LABEL) break;      // (the predecessor part ran, PART 5)
 
         // ================= 2. Bellman check + predecessor pass ===============
         // (a) every entry must satisfy dist[v] <= dist[u] + w for all in-arcs
@@ -817,7 +843,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
             // the bitmaps (free until the label walks), capped by that room.
             int* const heavyList = reinterpret_cast<int*>(smem + BCTRL_BYTES + (GB ? 0 : 8 * nwp));
             const int stackB = NT * SMAX * 8, bitsB = GB ? 0 : 8 * nwp;
-            const int hcap = min(4096, max(0, stackB - bitsB) / 4);
+            const int hcap = PRED ? pred_heavy_cap(nwp, GB) : min(4096, max(0, stackB - bitsB) / 4);
             int lo = 0, hi = n;
             // the on-demand pass gathers only the in-arcs the relax flagged (a
             // superset of the tight ones); the full pass reads every in-arc
@@ -1191,6 +1217,11 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
             break;
         }
         if (dbg && tid == 0) ctl->t2 = (long long)clock64();
+        if constexpr (PRED) {
+            // the one value that crosses to the label part: a violation fails the batch
+            if (tid == 0 && failed) as_global(bs.flags)[b] |= 1;
+            break;
+        }
 
         // ================= 3. labels on demand + row writer ==================
         // Only entries on some target's path need hops and reliability (27%
@@ -1340,7 +1371,18 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         // 16 rows x 8-32 B per wave instruction; from the tile each wave
         // stores a run of consecutive columns of one row (non-temporal:
         // the table is never re-read here)
-        if (!failed && !retry) {
+        // the label part: a batch that goes to the redo launch (the condition of
+        // the second attempt below, known once the walks are done) writes no row
+        bool redo = false;
+        if constexpr (LABEL) {
+            if (relAmb) atomicOr(&ctl->ambMask, 1u << l);
+            fence_wg();
+            __syncthreads();
+            const bool tieBuf = tieDesc != nullptr &&
+                                __builtin_amdgcn_readfirstlane((int)(ld_wg(&tieDesc->req) != nullptr)) != 0;
+            redo = !failed && (retry || (uni((int)ctl->ambMask) != 0 && !tieBuf));
+        }
+        if (!failed && !retry && !redo) {
             const int T = (int)tab.T;
             // (2 x NT entries of 21 B: inside the walk stacks' SMAX x NT x 8 B)
             double* const tLat = reinterpret_cast<double*>(smem + BCTRL_BYTES);
@@ -1469,10 +1511,37 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         // kernel was 43 vs 31 ms, a tie batch's in-line pass on its tail)
         const bool deferTie = PT == 2 && tieDesc != nullptr &&
                               __builtin_amdgcn_readfirstlane((int)(ld_wg(&tieDesc->req) != nullptr)) != 0;
+        if constexpr (LABEL) {
+            if (redo && tid == 0) {      // -> PART 2 over bs.redo, after this kernel
+                int32_t* const rd = as_global(bs.redo);
+                rd[REDO_LIST + atomicAdd(&rd[0], 1)] = b;
+                atomicAdd(&rd[1], 1);
+            }
+            needMask = redo ? 0u : needMask;
+            lastFull = false;
+            break;
+        }
         if (!fullPred && !failed && (retry || (needMask && !deferTie))) continue;
         lastFull = fullPred;
         break;
         }   // attempts
+        if constexpr (PRED) {
+            __syncthreads();
+#ifdef SHDPE_DIAG_WHY
+            if (why) atomicOr(&ctl->dWhy, why);
+            __syncthreads();
+#endif
+            if (dbg && tid == 0) {
+                atomicOr(&dbg[16 * b + 1], (int)ctl->dWhy);
+                dbg[16 * b + 6] = (int)((ctl->t2 - ctl->t1) >> 10);
+                if (bs.predCnt) {       // the on-demand pass's in-arcs: claimed, gathered
+                    atomicAdd(as_global(bs.predCnt), (unsigned long long)ctl->dClaim);
+                    atomicAdd(as_global(bs.predCnt) + 1, (unsigned long long)ctl->dGath);
+                }
+            }
+            __syncthreads();
+            continue;
+        }
         if constexpr (PT == 1) {
             __syncthreads();
             if (dbg && tid == 0) {
@@ -1567,12 +1636,15 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 atomicAdd(&dbg[16 * b + 9], (int)(ctl->dArcs >> 4));
                 atomicAdd(&dbg[16 * b + 10], (int)ctl->dLanes);
             }
-            dbg[16 * b + 1] = (int)ctl->dWhy;
+            // (the label part adds to the predecessor part's slots, and leaves it slot 6)
+            if (LABEL) atomicOr(&dbg[16 * b + 1], (int)ctl->dWhy);
+            else dbg[16 * b + 1] = (int)ctl->dWhy;
             dbg[16 * b + 3] = (int)needMask;
-            dbg[16 * b + 6] = (int)((ctl->t2 - ctl->t1) >> 10);
+            if (!LABEL) dbg[16 * b + 6] = (int)((ctl->t2 - ctl->t1) >> 10);
             dbg[16 * b + 7] = (int)((ctl->t3 - ctl->t2) >> 10);
             dbg[16 * b + 11] = (int)((ctl->t4 - ctl->t3) >> 10);
-            if (bs.predCnt) {       // the on-demand pass's in-arcs: claimed, gathered
+            // (the redo launch's batches were counted by the predecessor part)
+            if (!LABEL && bs.predCnt && !(PART == 2 && bs.redoRun)) {       // the on-demand pass's in-arcs: claimed, gathered
                 atomicAdd(as_global(bs.predCnt), (unsigned long long)ctl->dClaim);
                 atomicAdd(as_global(bs.predCnt) + 1, (unsigned long long)ctl->dGath);
             }
@@ -1724,11 +1796,18 @@ void launch_paths_walk_dist(const DevGraph& g, const BatchScratch& bs, const Pat
 
 int batch_threads(int wpe) { return wpe == 6 ? 768 : BT_THREADS; }
 
-int batch_lds_bytes(int n, int wpe, bool gbits) {
+// LDS of a variant's part.  The predecessor part (5) holds the pending and
+// claim bitmaps and its heavy list, the label part (6) the walk stacks (the
+// writer's tile lies inside them); the whole-batch kernel and the unsplit post
+// kernel (0, 2, 4) reuse the bitmaps' room for the stacks, so they take the
+// larger of the two, and the relax (1) keeps that size: its in-arc flag bits
+// live behind the bitmaps in it (batch_relax_flags).
+int batch_lds_bytes(int n, int wpe, bool gbits, int part) {
     const int nwp = (((n + 31) >> 5) + 3) & ~3;
-    // label walks reuse the relax bitmaps' LDS for their stacks
     const int stack = batch_threads(wpe) * (wpe >= 6 ? BCfg<8>::SMAX : BCfg<4>::SMAX) * 8;
     const int bits = gbits ? 0 : 2 * 4 * nwp;
+    if (part == 5) return BCTRL_BYTES + bits + 4 * pred_heavy_cap(nwp, gbits);
+    if (part == 6) return BCTRL_BYTES + stack;
     return BCTRL_BYTES + (bits > stack ? bits : stack);
 }
 
@@ -1745,7 +1824,8 @@ bool batch_relax_flags(const BatchScratch& bs, const BatchLaunch& cfg, int n) {
 
 // Every instantiation of k_batch_rows, by (lb, wpe, gbits, part): LB 4 / 8 /
 // 16 / 32 with LDS bitmaps and LB 16 with global ones (graphs whose bitmaps
-// exceed LDS: the engine forces LB 16), at 4 / 6 / 8 waves, PART 0 / 1 / 2 / 4.
+// exceed LDS: the engine forces LB 16), at 4 / 6 / 8 waves, PART 0 / 1 / 2 / 4 /
+// 5, and PART 6 (no bitmaps: one instantiation serves both).
 using BatchKernel = void (*)(DevGraph, DevTable, BatchScratch, const int32_t*, int32_t, uint8_t*, double,
                              int32_t*, const TieBuf*);
 struct BatchVariant {
@@ -1756,12 +1836,16 @@ struct BatchVariant {
 };
 #define BATCH_PARTS(LB, WPE, GB)                                                              \
     {LB, WPE, GB, 0, &k_batch_rows<LB, WPE, GB, 0>}, {LB, WPE, GB, 1, &k_batch_rows<LB, WPE, GB, 1>}, \
-    {LB, WPE, GB, 2, &k_batch_rows<LB, WPE, GB, 2>}, {LB, WPE, GB, 4, &k_batch_rows<LB, WPE, GB, 4>}
+    {LB, WPE, GB, 2, &k_batch_rows<LB, WPE, GB, 2>}, {LB, WPE, GB, 4, &k_batch_rows<LB, WPE, GB, 4>}, \
+    {LB, WPE, GB, 5, &k_batch_rows<LB, WPE, GB, 5>}
+#define BATCH_LABEL(LB, WPE) {LB, WPE, false, 6, &k_batch_rows<LB, WPE, false, 6>}
 #define BATCH_WIDTHS(WPE)                                                                     \
     BATCH_PARTS(4, WPE, false), BATCH_PARTS(8, WPE, false), BATCH_PARTS(16, WPE, false),      \
-    BATCH_PARTS(32, WPE, false), BATCH_PARTS(16, WPE, true)
+    BATCH_PARTS(32, WPE, false), BATCH_PARTS(16, WPE, true), BATCH_LABEL(4, WPE),             \
+    BATCH_LABEL(8, WPE), BATCH_LABEL(16, WPE), BATCH_LABEL(32, WPE)
 static const BatchVariant BATCH_VARIANTS[] = {BATCH_WIDTHS(4), BATCH_WIDTHS(6), BATCH_WIDTHS(8)};
 #undef BATCH_WIDTHS
+#undef BATCH_LABEL
 #undef BATCH_PARTS
 
 // the variant that serves a request: any other width runs LB 16, any other
@@ -1769,7 +1853,8 @@ static const BatchVariant BATCH_VARIANTS[] = {BATCH_WIDTHS(4), BATCH_WIDTHS(6), 
 static BatchKernel batch_kernel(int lb, int wpe, bool gbits, int part) {
     lb = gbits || (lb != 4 && lb != 8 && lb != 32) ? 16 : lb;
     wpe = wpe >= 8 ? 8 : wpe == 6 ? 6 : 4;
-    part = part == 1 || part == 2 || part == 4 ? part : 0;
+    part = part == 1 || part == 2 || part == 4 || part == 5 || part == 6 ? part : 0;
+    if (part == 6) gbits = false;
     for (const BatchVariant& v : BATCH_VARIANTS)
         if (v.lb == lb && v.wpe == wpe && v.gbits == gbits && v.part == part) return v.fn;
     return nullptr;     // not reached: the table holds every normalised key
@@ -1788,6 +1873,8 @@ void launch_batch_rows(const DevGraph& g, const DevTable& tab, const BatchScratc
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     BatchScratch bsl = bs;
     bsl.hitLds = part == 1 && batch_relax_flags(bs, cfg, g.n);
+    // (the redo launch: PART 2 over the list the label part left, bs.redoRun set by the caller)
+    bsl.redoRun = part == 2 && bs.redoRun && bs.redo ? 1 : 0;
     const BatchKernel fn = batch_kernel(cfg.lb, cfg.wpe, cfg.gbits != 0, part);
     (void)hipFuncSetAttribute(reinterpret_cast<const void*>(fn), hipFuncAttributeMaxDynamicSharedMemorySize,
                               cfg.ldsBytes);

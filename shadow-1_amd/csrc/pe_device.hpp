@@ -161,7 +161,10 @@ struct Tuning {
     int pathsFast = 1;         // ... 0: no batch / tie tier, every source by the grouped emulation
     int predFilter = 1;        // on-demand predecessor pass reads only the in-arcs the relax
                                // flagged (0: every in-arc, BatchScratch::arcHit stays null)
-    int laneOffset = 1;        // bucket key offsets of a batch's lanes: 1 the least-squares
+    int postSplit = -1;        // split kernels: the post kernel as two (predecessor part,
+                               // label part): 1 / 0 forced; -1: one kernel until
+                               // shd_pe_tune times both and keeps the faster
+    int laneOffset = 1;       // bucket key offsets of a batch's lanes: 1 the least-squares
                                // shift over the hub groups, 0 the nearest-hub distance
     int failWpe = 0;           // tests only: the relax variant of this wave count flags
                                // every batch failed (a miscompiled variant; shd_pe_tune
@@ -219,7 +222,18 @@ struct BatchScratch {
     int32_t hitLds;          // set per launch (the relax of this variant flags in-arcs)
     unsigned long long* predCnt;   // SHD_PE_DEBUG_COUNTERS only (else null): [0] in-arcs of the
                              // entries the on-demand pass claimed, [1] in-arcs it gathered
+    // post kernel in two parts (PART 5 / 6): LB holds one label array per
+    // batch of the round ([batch][nStride][LB]; null while the shard runs the
+    // one post kernel), and the label part lists the batches that need the
+    // unsplit kernel's second attempt: redo[0] = their count in this round
+    // (zeroed before each label launch), redo[1] = the count over the call,
+    // redo[REDO_LIST ...] = their batch indices.  redoRun (set per launch):
+    // PART 2 runs over that list, from the full predecessor pass.
+    BLabel* LB;
+    int32_t* redo;
+    int32_t redoRun;
 };
+constexpr int REDO_LIST = 16;
 
 struct BatchLaunch {
     int32_t lb;              // sources per batch (8, 16 or 32)
@@ -327,7 +341,9 @@ void launch_batch_rows(const DevGraph& g, const DevTable& tab, const BatchScratc
                        const BatchLaunch& cfg, int32_t* dDbg, const TieBuf* dTie, void* stream,
                        int part = 0);   // (part 4: the post kernel, part 2, storing no table row)
 const void* batch_kernel_ptr(int lb, int wpe, bool gbits, int part = 0);
-int batch_lds_bytes(int n, int wpe, bool gbits);
+// dynamic LDS of a variant's part (5: bitmaps + heavy list, 6: walk stacks, any
+// other: the larger of bitmaps and stacks)
+int batch_lds_bytes(int n, int wpe, bool gbits, int part = 0);
 // Deferred tie export of one round (after its post kernel): for every slot
 // the post kernel requested in round `round`, the tie data of the lane's row
 // -- every vertex's distance, its igraph parent (first tight in-arc of

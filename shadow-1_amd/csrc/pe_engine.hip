@@ -89,6 +89,7 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_STREAM_WG_PER_CU", t.streamWgPerCU);
     gi("SHDPE_TIE_CORRUPT", t.tieCorrupt);
     gi("SHDPE_PRED_FILTER", t.predFilter);
+    gi("SHDPE_POST_SPLIT", t.postSplit);
     gi("SHDPE_LANE_OFFSET", t.laneOffset);
     gi("SHDPE_TUNE_FAIL_WPE", t.failWpe);
     gi("SHDPE_TUNE_LOG", t.tuneLog);
@@ -232,13 +233,15 @@ static bool configure_batch(ShdPe* pe, Shard* sh) {
     // control block, else in each slot's global scratch (gbits, LB 16)
     b.gbits = pe->batched && batch_lds_bytes((int)n, 8, false) > LDS ? 1 : 0;
     if (b.gbits) b.lb = 16;
-    auto occupancy = [&](int wpe, int threads) {
-        const int lds = batch_lds_bytes((int)n, wpe, b.gbits != 0);
+    // (per part: the post kernel's two parts have their own LDS sizes, so the
+    // occupancy -- and with it the grid -- is each part's own)
+    auto occupancy = [&](int wpe, int threads, int part) {
+        const int lds = batch_lds_bytes((int)n, wpe, b.gbits != 0, part);
         int per = 0;
         if (lds > LDS ||
-            hipFuncSetAttribute(batch_kernel_ptr(b.lb, wpe, b.gbits != 0),
+            hipFuncSetAttribute(batch_kernel_ptr(b.lb, wpe, b.gbits != 0, part),
                                 hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess ||
-            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, batch_kernel_ptr(b.lb, wpe, b.gbits != 0),
+            hipOccupancyMaxActiveBlocksPerMultiprocessor(&per, batch_kernel_ptr(b.lb, wpe, b.gbits != 0, part),
                                                          threads, lds) != hipSuccess)
             per = 0;
         return per;
@@ -252,12 +255,12 @@ static bool configure_batch(ShdPe* pe, Shard* sh) {
     // picked the 4-wave relax on every box (and the 6-wave post kernel for
     // batches of 16, the 4-wave one for 8), so an untuned engine -- the
     // drop-in computes once -- starts there.
-    auto make = [&](int wpe) {
+    auto make = [&](int wpe, int part = 0) {
         BatchLaunch c = b;
         c.wpe = wpe;
         if (wpe == 6) c.threads = batch_threads(6);   // two 768-thread workgroups per CU
-        c.ldsBytes = batch_lds_bytes((int)n, wpe, b.gbits != 0);
-        const int per = c.ldsBytes <= LDS ? occupancy(wpe, c.threads) : 0;
+        c.ldsBytes = batch_lds_bytes((int)n, wpe, b.gbits != 0, part);
+        const int per = c.ldsBytes <= LDS ? occupancy(wpe, c.threads, part) : 0;
         c.grid = sh->numCUs * std::max(per, 1);
         if (tu.batchGrid > 0 && tu.batchGrid < c.grid) c.grid = tu.batchGrid;
         c.delta = pe->opt.delta > 0 ? pe->opt.delta : g.meanArcLatency * tu.batchDeltaFactor;
@@ -279,6 +282,34 @@ static bool configure_batch(ShdPe* pe, Shard* sh) {
     if (!forced && ok6 && tu.batchSplit) p.cand[p.nc++] = v6.first;
     p.relax = p.post = b;
     if (!forced && first == 4 && ok6 && b.split && b.lb >= 16) p.post = v6.first;
+    // the post kernel in two parts (PART 5 / 6): every candidate as either
+    // part, with the part's own LDS and grid.  An untuned engine runs the one
+    // post kernel: the two parts are shd_pe_tune's choice, timed against it on
+    // the shard's own rows (measured at C4 only: DESIGN §7), or forced with
+    // SHDPE_POST_SPLIT=1 -- then the predecessor part runs the post pick's
+    // variant and the label part what the tune picked at C4; ensure_batch
+    // drops the split when the per-batch label arrays do not fit.
+    // (partsOk: every part of every candidate can be launched -- the
+    // occupancy query accepts its LDS size; else the one post kernel stays)
+    p.partsOk = true;
+    for (int k = 0; k < p.nc; ++k) {
+        const auto pr = make(p.cand[k].wpe, 5), lb = make(p.cand[k].wpe, 6);
+        p.candPred[k] = pr.first;
+        p.candLabel[k] = lb.first;
+        p.candPred[k].split = p.candLabel[k].split = p.cand[k].split;
+        p.partsOk = p.partsOk && pr.second >= 1 && lb.second >= 1;
+    }
+    p.redo = p.post;
+    p.postSplit = b.split && tu.postSplit == 1 && p.partsOk;
+    if (p.postSplit) {
+        // (C4's tune, profiles/post_split_phase_cycles_head.txt: the 6-wave
+        // predecessor part 17.0 ms against 18.9 / 22.7 at 4 / 8 waves, the 8-wave
+        // label part 11.0 ms against 14.4 / 11.5 at 4 / 6)
+        const int wpe = p.post.wpe;
+        p.post = make(wpe, 5).first;
+        p.label = make(!forced && wpe == 6 && ok8 ? 8 : wpe, 6).first;
+        p.post.split = p.label.split = 1;
+    }
     return ok8 || ok4;
 }
 
@@ -316,8 +347,10 @@ static void destroy_shard(Shard* s) {
     if (s->stream) (void)hipStreamSynchronize(s->stream);
     if (s->comm) (void)ncclCommDestroy(s->comm);
     for (void* p : s->allocs) (void)hipFree(p);
+    if (s->bsc.LB) (void)hipFree(s->bsc.LB);
+    if (s->bsc.redo) (void)hipFree(s->bsc.redo);
     if (s->dPosOf) (void)hipFree(s->dPosOf);
-    for (hipEvent_t e : {s->ev0, s->ev1, s->evA, s->evB, s->evP[0], s->evP[1], s->evP[2]})
+    for (hipEvent_t e : {s->ev0, s->ev1, s->evA, s->evB, s->evP[0], s->evP[1], s->evP[2], s->evP[3]})
         if (e) (void)hipEventDestroy(e);
     if (s->stream) (void)hipStreamDestroy(s->stream);
     if (s->copyStream) (void)hipStreamDestroy(s->copyStream);
@@ -408,7 +441,7 @@ static int init_shard(ShdPe* pe, Shard* sh, const Relabelled* rl, BuiltGraph* bu
         hipEventCreate(&sh->ev0) != hipSuccess || hipEventCreate(&sh->ev1) != hipSuccess ||
         hipEventCreate(&sh->evA) != hipSuccess || hipEventCreate(&sh->evB) != hipSuccess ||
         hipEventCreate(&sh->evP[0]) != hipSuccess || hipEventCreate(&sh->evP[1]) != hipSuccess ||
-        hipEventCreate(&sh->evP[2]) != hipSuccess)
+        hipEventCreate(&sh->evP[2]) != hipSuccess || hipEventCreate(&sh->evP[3]) != hipSuccess)
         return SHD_PE_ENODEV;
     if ((rc = configure(pe, sh))) return rc;
     if (built && !built->adopted && !built->allocs.empty() && built->device == sh->device) {
@@ -729,6 +762,48 @@ static int ensure_tie(ShdPe* pe, Shard* sh) {
     return SHD_PE_OK;
 }
 
+// Post kernel in two parts: the label records cross from the predecessor part
+// to the label part, so they need one array per batch of the round like the
+// dist arrays, at 16 B per entry beside the dist arrays' 8 (C4: 26 GB beside
+// 13).  Allocated only for a shard that runs the two parts -- shd_pe_tune
+// while it times them, and afterwards if it keeps them; SHDPE_POST_SPLIT=1 --
+// and only where they fit under the scratch budget (batchScratchGB, 64 GiB)
+// with 12 GiB left free for what is allocated later; released when the tune
+// keeps the one post kernel.  False: the shard runs the one post kernel (C5:
+// its round of 131 GB of dist arrays would need 262 GB of label arrays).
+static void release_label_arrays(Shard* sh) {
+    if (sh->bsc.LB) (void)hipFree(sh->bsc.LB);
+    if (sh->bsc.redo) (void)hipFree(sh->bsc.redo);
+    sh->bsc.LB = nullptr;
+    sh->bsc.redo = nullptr;
+    sh->postSplitOk = false;
+}
+
+static bool ensure_label_arrays(ShdPe* pe, Shard* sh) {
+    if (sh->postSplitOk) return true;
+    const BatchPlan& plan = sh->plan;
+    if (!sh->batchReady || !plan.relax.split || !plan.partsOk || pe->tu.postSplit == 0) return false;
+    // (the tune's choice, not SHDPE_POST_SPLIT=1: only shards with at least a
+    // batch per resident workgroup of the 6- / 8-wave variants.  Below that
+    // every kernel is one batch long and a third kernel only adds a tail: the
+    // C4 N=8 shard, 256 batches of 8, was 15.3-15.4 ms on the two parts the
+    // tune's event times preferred, against 15.1-15.2 ms)
+    const size_t nBatchesAll = ((size_t)sh->rowCount + (size_t)plan.relax.lb - 1) / (size_t)plan.relax.lb;
+    if (pe->tu.postSplit != 1 && nBatchesAll < 2 * (size_t)sh->numCUs) return false;
+    const size_t bytes = (size_t)sh->batchRound * (size_t)sh->bsc.nStride * (size_t)plan.relax.lb * sizeof(BLabel);
+    size_t freeB = 0, totalB = 0;
+    if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) return false;
+    if ((double)bytes > pe->tu.batchScratchGB * (double)(1ull << 30) || freeB < bytes + ((size_t)12 << 30)) return false;
+    if (hipMalloc(reinterpret_cast<void**>(&sh->bsc.LB), bytes) != hipSuccess ||
+        hipMalloc(reinterpret_cast<void**>(&sh->bsc.redo), ((size_t)sh->batchRound + REDO_LIST) * 4) != hipSuccess) {
+        (void)hipGetLastError();
+        release_label_arrays(sh);
+        return false;
+    }
+    sh->postSplitOk = true;
+    return true;
+}
+
 static int ensure_batch(ShdPe* pe, Shard* sh) {
     if (sh->batchReady) return SHD_PE_OK;
     const size_t NS = ((size_t)pe->hg.n + 63) & ~(size_t)63;
@@ -749,6 +824,12 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     for (int k = 0; k < plan.nc; ++k) plan.cand[k].grid = std::min(plan.cand[k].grid, sh->batchSlots);
     plan.relax.grid = std::min(plan.relax.grid, sh->batchSlots);
     plan.post.grid = std::min(plan.post.grid, sh->batchSlots);
+    plan.label.grid = std::min(plan.label.grid, sh->batchSlots);
+    plan.redo.grid = std::min(plan.redo.grid, sh->batchSlots);
+    for (int k = 0; k < plan.nc; ++k) {
+        plan.candPred[k].grid = std::min(plan.candPred[k].grid, sh->batchSlots);
+        plan.candLabel[k].grid = std::min(plan.candLabel[k].grid, sh->batchSlots);
+    }
     int rc;
     // split kernels: one persisted dist array per batch of a round (relax ->
     // post), the rest per resident workgroup; rounds sized by free memory
@@ -787,11 +868,19 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     if (filter && dev_alloc(sh, &sh->bsc.arcHit, roundB * (mStride / 32))) (void)hipGetLastError();
     sh->bsc.predCnt = nullptr;
     if (pe->tu.debug && (rc = dev_alloc(sh, &sh->bsc.predCnt, 2))) return rc;
+    sh->bsc.LB = nullptr;
+    sh->bsc.redo = nullptr;
+    sh->bsc.redoRun = 0;
     sh->bsc.bits = nullptr;
     if (bitBytes && (rc = dev_alloc(sh, &sh->bsc.bits, slots * bitBytes / 4))) return rc;
     sh->bsc.laneOff = sh->dLaneOff;
     if ((rc = ensure_tie(pe, sh))) return rc;
     sh->batchReady = true;
+    // SHDPE_POST_SPLIT=1: the two parts without a tune, where their label arrays fit
+    if (plan.postSplit && !ensure_label_arrays(pe, sh)) {
+        plan.postSplit = false;
+        plan.post = plan.redo;
+    }
     return SHD_PE_OK;
 }
 
@@ -1051,40 +1140,68 @@ static int relax_dense(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, Ex
 // bytes are still in place, with the round's first batch and batch count.
 using RoundHook = std::function<int(int32_t r0, int32_t rn)>;
 
-static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const BatchLaunch& post, int32_t nB,
+// The post launches of a round: the one post kernel, or its two parts and the
+// redo launch (BatchPlan).
+struct PostLaunches {
+    BatchLaunch post{}, label{}, redo{};
+    bool split = false;
+};
+
+static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const PostLaunches& pl, int32_t nB,
                         BatchTrial* trial, const RoundHook* roundHook = nullptr) {
     const int LB = relax.lb;
     const bool timed = trial && trial->timed;
-    const int postPart = trial && trial->noTable ? 4 : 2;   // (4: the post kernel without its row stores)
+    const bool noTable = trial && trial->noTable;
+    // (shd_pe_get_paths' pass stores no row: PART 4, the one post kernel)
+    const bool split = pl.split && !noTable && sh->postSplitOk && sh->bsc.LB && sh->bsc.redo;
     int rc;
     for (int32_t r0 = 0; r0 < nB; r0 += sh->batchRound) {
         const int32_t rn = std::min(sh->batchRound, nB - r0);
         const size_t ro = (size_t)r0 * LB;
+        int32_t* const dbgR = sh->dDbg ? sh->dDbg + 16 * r0 : nullptr;
+        const BatchScratch bs = scratch_at(sh, sh->dBatchRows + ro);
+        auto launch = [&](const BatchLaunch& cfg, int part, const BatchScratch& b) {
+            if (hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream) != hipSuccess) return SHD_PE_EHIP;
+            launch_batch_rows(sh->dg, sh->tab, b, sh->dBatchRows + ro, rn, sh->dBatchAmb + ro, cfg, dbgR, sh->dTie,
+                              sh->stream, part);
+            return SHD_PE_OK;
+        };
         if (timed) HIPCHK(hipEventRecord(sh->evP[0], sh->stream));
-        for (int part = 1; part <= 2; ++part) {
-            int32_t* const dbgR = sh->dDbg ? sh->dDbg + 16 * r0 : nullptr;
-            HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
-            launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, sh->dBatchRows + ro), sh->dBatchRows + ro, rn,
-                              sh->dBatchAmb + ro, part == 1 ? relax : post, dbgR, sh->dTie, sh->stream,
-                              part == 1 ? 1 : postPart);
-            // tests only (SHDPE_TUNE_FAIL_WPE): the relax variant of that wave
-            // count flags every batch failed, as a miscompiled variant would
-            if (part == 1 && pe->tu.failWpe && relax.wpe == pe->tu.failWpe)
-                HIPCHK(hipMemsetAsync(sh->bsc.flags, 1, (size_t)rn * 4, sh->stream));
-            if (timed) HIPCHK(hipEventRecord(sh->evP[part], sh->stream));
-            // the post kernel's deferred tie export of this round (the round's dist
-            // arrays persist until the next round's relax)
-            if (part == 1 && sh->tie.req)
-                HIPCHK(hipMemsetD32Async((hipDeviceptr_t)sh->tie.round, r0 / sh->batchRound, 1, sh->stream));
-            if (part == 2 && sh->tie.req)
-                launch_tie_export(sh->dg, sh->bsc, LB, sh->tie, r0 / sh->batchRound, sh->dBatchAmb + ro,
-                                  sh->numCUs * 4, pe->tu.tieCorrupt == 3 ? 0 : -1, sh->stream);
+        if ((rc = launch(relax, 1, bs))) return rc;
+        // tests only (SHDPE_TUNE_FAIL_WPE): the relax variant of that wave
+        // count flags every batch failed, as a miscompiled variant would
+        if (pe->tu.failWpe && relax.wpe == pe->tu.failWpe)
+            HIPCHK(hipMemsetAsync(sh->bsc.flags, 1, (size_t)rn * 4, sh->stream));
+        if (timed) HIPCHK(hipEventRecord(sh->evP[1], sh->stream));
+        // the post kernel's deferred tie export of this round (the round's dist
+        // arrays persist until the next round's relax)
+        if (sh->tie.req)
+            HIPCHK(hipMemsetD32Async((hipDeviceptr_t)sh->tie.round, r0 / sh->batchRound, 1, sh->stream));
+        if (!split) {
+            if ((rc = launch(pl.split ? pl.redo : pl.post, noTable ? 4 : 2, bs))) return rc;
+            if (timed) HIPCHK(hipEventRecord(sh->evP[2], sh->stream));
+        } else {
+            // predecessor part, label part, then the one post kernel over the
+            // batches the label part listed (a grid that exits at once when
+            // there are none): ordered by the stream alone
+            if ((rc = launch(pl.post, 5, bs))) return rc;
+            if (timed) HIPCHK(hipEventRecord(sh->evP[2], sh->stream));
+            HIPCHK(hipMemsetAsync(sh->bsc.redo, 0, 4, sh->stream));
+            if ((rc = launch(pl.label, 6, bs))) return rc;
+            BatchScratch br = bs;
+            br.redoRun = 1;
+            if ((rc = launch(pl.redo, 2, br))) return rc;
         }
+        if (timed) HIPCHK(hipEventRecord(sh->evP[3], sh->stream));
+        if (sh->tie.req)
+            launch_tie_export(sh->dg, sh->bsc, LB, sh->tie, r0 / sh->batchRound, sh->dBatchAmb + ro,
+                              sh->numCUs * 4, pe->tu.tieCorrupt == 3 ? 0 : -1, sh->stream);
         if (roundHook && (rc = (*roundHook)(r0, rn))) return rc;
         if (timed) {
-            HIPCHK(hipEventSynchronize(sh->evP[2]));
+            HIPCHK(hipEventSynchronize(sh->evP[3]));
             trial->msRelax += elapsed(sh->evP[0], sh->evP[1]);
             trial->msPost += elapsed(sh->evP[1], sh->evP[2]);
+            trial->msLabel += elapsed(sh->evP[2], sh->evP[3]);
         }
     }
     return SHD_PE_OK;
@@ -1094,8 +1211,11 @@ static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const Ba
 static const BatchLaunch& relax_launch(const Shard* sh, const BatchTrial* trial) {
     return trial ? trial->relax : sh->plan.relax;
 }
-static const BatchLaunch& post_launch(const Shard* sh, const BatchTrial* trial) {
-    return trial ? trial->post : sh->plan.post;
+static PostLaunches post_launches(const Shard* sh, const BatchTrial* trial) {
+    if (trial) return PostLaunches{trial->post, trial->label, trial->postSplit ? trial->redo : trial->post,
+                                   trial->postSplit};
+    const BatchPlan& p = sh->plan;
+    return PostLaunches{p.post, p.label, p.redo, p.postSplit};
 }
 
 // (batchOrder / roundHook: shd_pe_get_paths -- batch_order of these rows, which
@@ -1122,19 +1242,23 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     HIPCHK(hipMemcpyAsync(sh->dLaneOff, laneOff.data(), laneOff.size() * 8, hipMemcpyHostToDevice, sh->stream));
     if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
     if (sh->bsc.predCnt) HIPCHK(hipMemsetAsync(sh->bsc.predCnt, 0, 16, sh->stream));
+    if (sh->bsc.redo) HIPCHK(hipMemsetAsync(sh->bsc.redo, 0, 8, sh->stream));
     if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
     HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
     HIPCHK(hipEventRecord(sh->evA, sh->stream));
     if (!relax.split)
         launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, sh->dBatchRows), sh->dBatchRows, nB, sh->dBatchAmb, relax,
                           sh->dDbg, sh->dTie, sh->stream, 0);
-    else if ((rc = batch_rounds(pe, sh, relax, post_launch(sh, trial), nB, trial, roundHook)))
+    else if ((rc = batch_rounds(pe, sh, relax, post_launches(sh, trial), nB, trial, roundHook)))
         return rc;
     HIPCHK(hipGetLastError());
     HIPCHK(hipEventRecord(sh->evB, sh->stream));
     std::vector<uint8_t> amb(order.size());
     HIPCHK(hipMemcpyAsync(amb.data(), sh->dBatchAmb, order.size(), hipMemcpyDeviceToHost, sh->stream));
+    int32_t redone[2] = {0, 0};      // [1]: batches of this call that took the redo launch
+    if (sh->bsc.redo) HIPCHK(hipMemcpyAsync(redone, sh->bsc.redo, 8, hipMemcpyDeviceToHost, sh->stream));
     HIPCHK(hipStreamSynchronize(sh->stream));
+    sh->redoBatches += redone[1];
     st.msSparseKernel += elapsed(sh->evA, sh->evB);
     st.launchesSparse++;
     classify_rows(order.data(), order.size(), amb.data(), x);
@@ -1449,11 +1573,16 @@ struct TuneSample {
     double ms = 0.0;                 // batch kernels in all
     double msRelax = 0.0, msPost = 0.0;   // split kernels: their parts
     int64_t exact = 0;               // rows it sent to the exact path
+    // the post kernel in two parts (0 when not timed): the predecessor part,
+    // the label part with the redo launch
+    double msPred = 0.0, msLabel = 0.0;
 };
 
 // The tune's choice among the samples.
 struct TunePick {
     int relax = 0, post = 0;         // candidate indices
+    int pred = 0, label = 0;         // ... of the post kernel's two parts
+    bool split = false;              // the two parts beat the one post kernel
     bool perPart = false;            // picked per part (else one pick for both)
     bool ok[4] = {false, false, false, false};   // candidates that competed
 };
@@ -1462,22 +1591,46 @@ struct TunePick {
 static int tune_run(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, BatchTrial& t, TuneSample& s) {
     const double m0 = sh->stats.msSparseKernel;
     const int64_t x0 = sh->stats.rowsExact;
-    t.msRelax = t.msPost = 0.0;
+    t.msRelax = t.msPost = t.msLabel = 0.0;
     const int rc = compute_shard(pe, sh, pos.data(), (int32_t)pos.size(), &t);
-    s = TuneSample{sh->stats.msSparseKernel - m0, t.msRelax, t.msPost, sh->stats.rowsExact - x0};
+    s = TuneSample{sh->stats.msSparseKernel - m0, t.msRelax, t.msPost, sh->stats.rowsExact - x0, 0.0, 0.0};
+    if (t.postSplit) {
+        s.msPred = t.msPost;
+        s.msLabel = t.msLabel;
+    } else {
+        s.msPost += t.msLabel;      // (one post kernel: the second interval is empty)
+    }
     return rc;
 }
 
 // Times one candidate as both kernels' variant: a first launch maps its code
 // and scratch; the second is timed (split kernels: relax and post separately)
-static int tune_time(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, const BatchLaunch& c,
-                     TuneSample& s) {
+// and, where the shard can run the post kernel in two parts, the same again
+// with candidate k as both parts (on the same rows: the comparison the pick
+// between one post kernel and two rests on).
+static int tune_time(ShdPe* pe, Shard* sh, const std::vector<int32_t>& pos, int k, TuneSample& s) {
+    const BatchPlan& plan = sh->plan;
+    const BatchLaunch& c = plan.cand[k];
     BatchTrial t;
     t.relax = t.post = c;
     int rc = tune_run(pe, sh, pos, t, s);
     if (rc) return rc;
     t.timed = c.split != 0;
-    return tune_run(pe, sh, pos, t, s);
+    if ((rc = tune_run(pe, sh, pos, t, s))) return rc;
+    if (!c.split || !sh->postSplitOk || pe->tu.postSplit == 0) return SHD_PE_OK;
+    BatchTrial u;
+    u.relax = u.redo = c;
+    u.post = plan.candPred[k];
+    u.label = plan.candLabel[k];
+    u.postSplit = true;
+    TuneSample x;
+    if ((rc = tune_run(pe, sh, pos, u, x))) return rc;
+    u.timed = true;
+    if ((rc = tune_run(pe, sh, pos, u, x))) return rc;
+    s.msPred = x.msPred;
+    s.msLabel = x.msLabel;
+    s.exact = std::max(s.exact, x.exact);
+    return SHD_PE_OK;
 }
 
 // The picks, from the candidates' samples alone.
@@ -1509,6 +1662,19 @@ static TunePick tune_pick(const BatchLaunch* cand, const TuneSample* s, int nc) 
     if (!p.perPart) pk = rk;
     p.relax = rk;
     p.post = pk;
+    // the post kernel's two parts, each its fastest variant; taken when their
+    // sum beats the fastest one post kernel on these rows
+    bool parts = p.perPart;
+    for (int k = 0; k < nc; ++k) parts = parts && (!p.ok[k] || (s[k].msPred > 0.0 && s[k].msLabel > 0.0));
+    p.pred = p.label = rk;          // (never an excluded candidate, whatever follows)
+    if (parts) {
+        for (int k = 0; k < nc; ++k) {
+            if (!p.ok[k]) continue;
+            if (s[k].msPred < s[p.pred].msPred) p.pred = k;
+            if (s[k].msLabel < s[p.label].msLabel) p.label = k;
+        }
+        p.split = s[p.pred].msPred + s[p.label].msLabel < s[pk].msPost;
+    }
     return p;
 }
 
@@ -1584,6 +1750,15 @@ static void tune_log(const Shard* sh, const TuneSample* s, const TunePick& p, co
                      sh->gindex, plan.cand[k].wpe, s[k].ms,
                      s[k].msRelax, s[k].msPost, (long)s[k].exact, p.ok[k] ? "" : " (excluded)",
                      k == p.relax ? " <relax" : "", k == p.post ? " <post" : "");
+    if (s[p.pred].msPred > 0.0)
+        std::fprintf(stderr, "[shdpe] shard %d tune: post kernel %.2f ms (%d waves) vs predecessor part %.2f ms (%d "
+                     "waves) + label part %.2f ms (%d waves) -> %s\n", sh->gindex, s[p.post].msPost,
+                     plan.cand[p.post].wpe, s[p.pred].msPred, plan.cand[p.pred].wpe, s[p.label].msLabel,
+                     plan.cand[p.label].wpe, plan.postSplit ? "two parts" : "one kernel");
+    for (int k = 0; k < plan.nc; ++k)
+        if (s[k].msPred > 0.0)
+            std::fprintf(stderr, "[shdpe] shard %d tune: %d waves as parts: predecessor %.2f ms label %.2f ms\n",
+                         sh->gindex, plan.cand[k].wpe, s[k].msPred, s[k].msLabel);
     if (best[1] > 0.0)
         std::fprintf(stderr, "[shdpe] shard %d tune: relax at 0.8 x delta %.2f ms vs %.2f -> delta %.3f\n",
                      sh->gindex, best[1], best[0], plan.relax.delta);
@@ -1603,8 +1778,10 @@ static int tune_shard(ShdPe* pe, Shard* sh) {
     std::vector<int32_t> pos(sh->rowCount);
     for (int32_t i = 0; i < sh->rowCount; ++i) pos[i] = sh->rowStart + i;
     const ShdPeStats keep = sh->stats;
+    const int64_t keepRedo = sh->redoBatches;
+    if (pe->tu.postSplit != 0) (void)ensure_label_arrays(pe, sh);   // (false: only the one post kernel is timed)
     TuneSample s[4];
-    for (int k = 0; k < plan.nc && !rc; ++k) rc = tune_time(pe, sh, pos, plan.cand[k], s[k]);
+    for (int k = 0; k < plan.nc && !rc; ++k) rc = tune_time(pe, sh, pos, k, s[k]);
     TunePick p;
     BatchLaunch relax{};
     double best[2] = {0.0, 0.0};
@@ -1615,9 +1792,18 @@ static int tune_shard(ShdPe* pe, Shard* sh) {
         if (!rc && p.perPart) rc = tune_delta(pe, sh, pos, relax, plan.cand[p.post], best);
     }
     sh->stats = keep;               // the tune's computes are not the caller's
-    if (rc) return rc;
+    sh->redoBatches = keepRedo;
+    if (rc) {
+        if (!plan.postSplit) release_label_arrays(sh);
+        return rc;
+    }
     plan.relax = relax;
-    plan.post = p.post != p.relax ? plan.cand[p.post] : relax;
+    plan.redo = p.post != p.relax ? plan.cand[p.post] : relax;
+    // (SHDPE_POST_SPLIT=1: the two parts whatever the times say)
+    plan.postSplit = sh->postSplitOk && (p.split || (pe->tu.postSplit == 1 && s[p.pred].msPred > 0.0));
+    plan.post = plan.postSplit ? plan.candPred[p.pred] : plan.redo;
+    if (plan.postSplit) plan.label = plan.candLabel[p.label];
+    else release_label_arrays(sh);  // the one post kernel: its labels are per workgroup
     sh->tuned = true;
     plan_stats(pe, sh);
     if (pe->tu.debug || pe->tu.tuneLog) tune_log(sh, s, p, best);
@@ -1955,7 +2141,7 @@ static int paths_tier_batch(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w, Exa
     if (!sh->plan.relax.split) return SHD_PE_OK;
     BatchTrial trial;   // the plan's picks
     trial.relax = sh->plan.relax;
-    trial.post = sh->plan.post;
+    trial.post = sh->plan.postSplit ? sh->plan.redo : sh->plan.post;   // (PART 4: the one post kernel)
     trial.noTable = true;
     const int32_t LB = trial.relax.lb;
     // the pass's batch order (table positions, -1 pads); the requests by their source's index in it
@@ -2440,6 +2626,7 @@ extern "C" int shd_pe_reset_stats(ShdPe* pe) {
         st.batchWaves = keep.batchWaves;
         st.batchPostWaves = keep.batchPostWaves;
         sp->predClaimed = sp->predGathered = 0;
+        sp->redoBatches = 0;
     }
     pe->msGather = 0.0;
     return SHD_PE_OK;
@@ -2453,6 +2640,23 @@ extern "C" int shd_pe_pred_filter_counts(const ShdPe* pe, int64_t* claimed, int6
         *claimed += sp->predClaimed;
         *gathered += sp->predGathered;
     }
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_post_split_info(const ShdPe* pe, int32_t* split, int32_t* labelWaves,
+                                      int64_t* redoBatches) {
+    if (!pe || !split || !labelWaves || !redoBatches) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
+    *split = *labelWaves = 0;
+    *redoBatches = 0;
+    // (before the first compute the plan holds configure's pick; ensure_batch
+    // may still drop the split when the label arrays do not fit)
+    if (pe->batched && !pe->shards.empty()) {
+        const shdpe::Shard& sh = *pe->shards[0];
+        *split = sh.plan.relax.split && sh.plan.postSplit && (!sh.batchReady || sh.postSplitOk) ? 1 : 0;
+        *labelWaves = *split ? sh.plan.label.wpe : 0;
+    }
+    for (auto& sp : pe->shards) *redoBatches += sp->redoBatches;
     return SHD_PE_OK;
 }
 

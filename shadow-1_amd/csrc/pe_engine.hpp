@@ -27,9 +27,17 @@ namespace shdpe {
 struct BatchPlan {
     BatchLaunch cand[4];            // what shd_pe_tune times, in its order: the untuned relax
                                     // pick, the other of 4 / 8 waves, 6 waves
+    BatchLaunch candPred[4], candLabel[4];   // cand[k] as the post kernel's two parts (PART 5 / 6):
+                                    // the part's own LDS bytes and grid
     int nc = 0;
     BatchLaunch relax{};            // picks in use: the relax launch (with the delta chosen) ...
-    BatchLaunch post{};             // ... and, split kernels, the post launch
+    BatchLaunch post{};             // ... and, split kernels, the post launch: the one post kernel,
+                                    // or (postSplit) its predecessor part ...
+    BatchLaunch label{};            // ... followed by its label part ...
+    BatchLaunch redo{};             // ... and the one post kernel over the batches the label part
+                                    // handed back (second attempt: deep trees, undeferred ties)
+    bool postSplit = false;
+    bool partsOk = false;           // configure_batch: every candidate's two parts fit a CU
     bool tunable() const { return nc > 1; }
 };
 
@@ -40,10 +48,11 @@ struct BatchPlan {
 // the batch tier of shd_pe_get_paths (noTable), both through relax_batched /
 // batch_rounds; a plain compute passes no trial.
 struct BatchTrial {
-    BatchLaunch relax{}, post{};
+    BatchLaunch relax{}, post{}, label{}, redo{};
+    bool postSplit = false;         // post = the predecessor part, label / redo as in BatchPlan
     bool timed = false;
     bool noTable = false;           // shd_pe_get_paths: the post kernel stores no table row
-    double msRelax = 0.0, msPost = 0.0;
+    double msRelax = 0.0, msPost = 0.0, msLabel = 0.0;   // (msLabel: label part + redo launch)
 };
 
 // shd_pe_get_path: PathsWalkArgs' arrays for one request (off = 0); the path's vertices follow.
@@ -62,7 +71,7 @@ struct Shard {
     hipStream_t stream = nullptr;
     hipStream_t copyStream = nullptr;
     hipEvent_t ev0 = nullptr, ev1 = nullptr, evA = nullptr, evB = nullptr;
-    hipEvent_t evP[3] = {nullptr, nullptr, nullptr};   // per-part timing (shd_pe_tune)
+    hipEvent_t evP[4] = {nullptr, nullptr, nullptr, nullptr};   // per-part timing (shd_pe_tune)
     std::vector<void*> allocs;
     DevGraph dg{};                  // path kernels (device ids, possibly relabelled)
     DevGraph dgAux{};               // caller's ids, rows sorted by id (aux kernels)
@@ -79,6 +88,8 @@ struct Shard {
     int exactGrid = 0, exactHc = 1;
     BatchPlan plan{};
     int64_t predClaimed = 0, predGathered = 0;   // shd_pe_pred_filter_counts (debug counters)
+    bool postSplitOk = false;       // ensure_batch: label arrays per batch (the post kernel may run in two parts)
+    int64_t redoBatches = 0;        // shd_pe_post_split_info: batches that took the redo launch
     bool tuned = false;
     BatchScratch bsc{};
     bool batchReady = false;
