@@ -36,12 +36,13 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 11  /* 7: graph property check (shd_pe_graph_props);
+#define SHD_PE_ABI_VERSION 12  /* 7: graph property check (shd_pe_graph_props);
                                   8: fill from row shards (shd_pe_fill_rowstore_shards);
                                   9: shd_pe_pred_filter_counts;
                                   10: shd_pe_create_built (graph build on the device),
                                       shd_pe_graph_digest;
-                                  11: shd_pe_post_split_info */
+                                  11: shd_pe_post_split_info;
+                                  12: shd_pe_batch_info */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -515,6 +516,18 @@ int shd_pe_pred_filter_counts(const ShdPe* pe, int64_t* claimed, int64_t* gather
  * shards, that the label part handed to the one post kernel's second attempt
  * since the last shd_pe_reset_stats. */
 int shd_pe_post_split_info(const ShdPe* pe, int32_t* split, int32_t* labelWaves, int64_t* redoBatches);
+/* The rounds of the split batch kernels on shard `shard` of this process
+ * (0 <= shard < shd_pe_num_shards; ABI 12).  A round is the batches whose
+ * distance arrays persist from the relax to the post kernel; it is sized at
+ * the shard's first batched compute from the free device memory (every table
+ * computed so far is one round).  out[0] = batches per round, out[1] = scratch
+ * slots (both 0 before that first compute); out[2] = rounds run and out[3] =
+ * batches run in them since the last shd_pe_reset_stats, over the computes
+ * that write table rows: the timed computes of shd_pe_tune and the pass of
+ * shd_pe_get_paths, which put ShdPeStats back as it was, put these back too.
+ * A diagnostic of this engine's schedule: it replaces nothing in topology.c,
+ * which has no counterpart. */
+int shd_pe_batch_info(const ShdPe* pe, int32_t shard, int64_t out[4]);
 
 /* ---- batched helpers on the device ------------
  * The per-query lookups below, for many queries in one call: inputs and

@@ -169,6 +169,11 @@ struct Tuning {
     int failWpe = 0;           // tests only: the relax variant of this wave count flags
                                // every batch failed (a miscompiled variant; shd_pe_tune
                                // must not pick it)
+    int batchRoundCap = 0;     // tests only: > 0 = at most this many batches per round of the
+                               // split kernels (never below the scratch slots): a small
+                               // table takes several rounds
+    int tieSlotsCap = -1;      // tests only: >= 0 = at most this many tie slots (0: none, the
+                               // state of a graph past 2^30 arcs); -1 unchanged
 };
 
 struct DevScratch {

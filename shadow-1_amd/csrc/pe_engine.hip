@@ -92,6 +92,8 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_POST_SPLIT", t.postSplit);
     gi("SHDPE_LANE_OFFSET", t.laneOffset);
     gi("SHDPE_TUNE_FAIL_WPE", t.failWpe);
+    gi("SHDPE_BATCH_ROUND", t.batchRoundCap);
+    gi("SHDPE_TIE_SLOTS", t.tieSlotsCap);
     gi("SHDPE_TUNE_LOG", t.tuneLog);
     gi("SHDPE_PATHS_GROUP", t.pathsGroup);
     gi("SHDPE_PATHS_CHUNK", t.pathsChunk);
@@ -738,6 +740,8 @@ static int ensure_tie(ShdPe* pe, Shard* sh) {
     size_t cap = std::min<size_t>({pe->mode == 3 ? (size_t)4096 : (size_t)254, (size_t)sh->rowsCap,
                                    ((size_t)2 << 30) / perTie});
     if (pe->hg.nArcs() >= ((int64_t)1 << 30)) cap = 0;
+    // tests only (SHDPE_TIE_SLOTS): fewer slots, or none as past 2^30 arcs
+    if (pe->tu.tieSlotsCap >= 0) cap = std::min(cap, (size_t)pe->tu.tieSlotsCap);
     if (cap > 0) {
         TieBuf t{}, *dd;
         int32_t *sl, *rq;
@@ -846,9 +850,8 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) freeB = (size_t)16 << 30;
         const size_t perD = NS * LB * 8 + (filter ? mStride / 8 : 0);
         const size_t rest = slots * (perSlot - NS * LB * 8);
-        const size_t room = freeB > rest + ((size_t)12 << 30) ? freeB - rest - ((size_t)12 << 30) : perD;
-        const size_t dBudget = std::min<size_t>(room, (size_t)160 << 30);
-        roundB = std::max<size_t>(slots, std::min<size_t>(nBatchesAll, dBudget / perD));
+        // (tests only, SHDPE_BATCH_ROUND: fewer batches per round than would fit)
+        roundB = batch_round_size(slots, nBatchesAll, perD, rest, freeB, pe->tu.batchRoundCap);
     }
     sh->batchRound = (int32_t)roundB;
     // (the queues' and the flags' 16 spare words: `next` sits behind the queues)
@@ -1158,6 +1161,8 @@ static int batch_rounds(ShdPe* pe, Shard* sh, const BatchLaunch& relax, const Po
     for (int32_t r0 = 0; r0 < nB; r0 += sh->batchRound) {
         const int32_t rn = std::min(sh->batchRound, nB - r0);
         const size_t ro = (size_t)r0 * LB;
+        sh->roundsRun++;
+        sh->batchesRun += rn;
         int32_t* const dbgR = sh->dDbg ? sh->dDbg + 16 * r0 : nullptr;
         const BatchScratch bs = scratch_at(sh, sh->dBatchRows + ro);
         auto launch = [&](const BatchLaunch& cfg, int part, const BatchScratch& b) {
@@ -1244,6 +1249,11 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     if (sh->bsc.predCnt) HIPCHK(hipMemsetAsync(sh->bsc.predCnt, 0, 16, sh->stream));
     if (sh->bsc.redo) HIPCHK(hipMemsetAsync(sh->bsc.redo, 0, 8, sh->stream));
     if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
+    // the slots' deferred-export requests: round -1, which no round's k_tie_export
+    // serves.  A slot the post kernel fills in line (its second attempt: a deep
+    // tree with ties) gets no request, and the words an earlier call -- or the
+    // allocator -- left there would name a batch of this call's round
+    if (sh->tie.req) HIPCHK(hipMemsetAsync(sh->tie.req, 0xFF, (size_t)sh->tie.cap * 16, sh->stream));
     HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
     HIPCHK(hipEventRecord(sh->evA, sh->stream));
     if (!relax.split)
@@ -1778,7 +1788,7 @@ static int tune_shard(ShdPe* pe, Shard* sh) {
     std::vector<int32_t> pos(sh->rowCount);
     for (int32_t i = 0; i < sh->rowCount; ++i) pos[i] = sh->rowStart + i;
     const ShdPeStats keep = sh->stats;
-    const int64_t keepRedo = sh->redoBatches;
+    const int64_t keepRedo = sh->redoBatches, keepRounds = sh->roundsRun, keepBatches = sh->batchesRun;
     if (pe->tu.postSplit != 0) (void)ensure_label_arrays(pe, sh);   // (false: only the one post kernel is timed)
     TuneSample s[4];
     for (int k = 0; k < plan.nc && !rc; ++k) rc = tune_time(pe, sh, pos, k, s[k]);
@@ -1793,6 +1803,8 @@ static int tune_shard(ShdPe* pe, Shard* sh) {
     }
     sh->stats = keep;               // the tune's computes are not the caller's
     sh->redoBatches = keepRedo;
+    sh->roundsRun = keepRounds;
+    sh->batchesRun = keepBatches;
     if (rc) {
         if (!plan.postSplit) release_label_arrays(sh);
         return rc;
@@ -2168,8 +2180,11 @@ static int paths_tier_batch(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w, Exa
         return SHD_PE_OK;
     };
     const ShdPeStats savedStats = sh->stats;
+    const int64_t savedRounds[2] = {sh->roundsRun, sh->batchesRun};
     rc = relax_batched(pe, sh, w.uniq.data(), (int32_t)w.uniq.size(), x, &trial, &order, &walkRound);
     sh->stats = savedStats;                              // (relax_batched synchronised: breqs is read)
+    sh->roundsRun = savedRounds[0];                      // (shd_pe_batch_info counts the table passes)
+    sh->batchesRun = savedRounds[1];
     if (rc) return rc;
     std::vector<uint8_t> failed((size_t)c.cnt), flagged(pe->attached.size(), 0), stay(w.reqs.size());
     HIPCHK(hipMemcpyAsync(failed.data(), s.failed, failed.size(), hipMemcpyDeviceToHost, sh->stream));
@@ -2627,6 +2642,7 @@ extern "C" int shd_pe_reset_stats(ShdPe* pe) {
         st.batchPostWaves = keep.batchPostWaves;
         sp->predClaimed = sp->predGathered = 0;
         sp->redoBatches = 0;
+        sp->roundsRun = sp->batchesRun = 0;
     }
     pe->msGather = 0.0;
     return SHD_PE_OK;
@@ -2657,6 +2673,18 @@ extern "C" int shd_pe_post_split_info(const ShdPe* pe, int32_t* split, int32_t* 
         *labelWaves = *split ? sh.plan.label.wpe : 0;
     }
     for (auto& sp : pe->shards) *redoBatches += sp->redoBatches;
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_batch_info(const ShdPe* pe, int32_t shard, int64_t out[4]) {
+    if (!pe || !out || shard < 0 || (size_t)shard >= pe->shards.size()) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
+    const shdpe::Shard& sh = *pe->shards[(size_t)shard];
+    // (batchRound / batchSlots: 0 until ensure_batch ran, at the shard's first batched compute)
+    out[0] = sh.batchRound;
+    out[1] = sh.batchSlots;
+    out[2] = sh.roundsRun;
+    out[3] = sh.batchesRun;
     return SHD_PE_OK;
 }
 

@@ -95,6 +95,7 @@ struct Shard {
     bool batchReady = false;
     int32_t batchRound = 0;         // split kernels: batches per round (persisted dist arrays)
     int32_t batchSlots = 0;         // scratch slots allocated (ensure_batch: no grid of the plan exceeds it)
+    int64_t roundsRun = 0, batchesRun = 0;   // shd_pe_batch_info: batch_rounds' rounds and their batches (table passes)
     int32_t* dBatchRows = nullptr;
     double* dLaneOff = nullptr;     // per entry of dBatchRows its lane's bucket key offset
     uint8_t* dBatchAmb = nullptr;

@@ -393,6 +393,17 @@ std::vector<int32_t> batch_order_cost(const std::vector<int32_t>& rank, const st
     return order;
 }
 
+size_t batch_round_size(size_t slots, size_t nBatchesAll, size_t perD, size_t rest, size_t freeB, int testCap) {
+    if (perD == 0) perD = 1;         // (no vertex: nothing is persisted)
+    // (freeB - rest - reserve without a sum that could wrap)
+    const bool roomy = freeB > rest && freeB - rest > ROUND_RESERVE_BYTES;
+    const size_t room = roomy ? freeB - rest - ROUND_RESERVE_BYTES : perD;
+    const size_t dBudget = std::min(room, ROUND_DIST_CAP_BYTES);
+    size_t roundB = std::max(slots, std::min(nBatchesAll, dBudget / perD));
+    if (testCap > 0) roundB = std::max(slots, std::min(roundB, (size_t)testCap));
+    return roundB;
+}
+
 int select_mode(const HostGraph& g, int forceMode, double denseMin) {
     int mode = (g.isComplete && forceMode != 1 && forceMode != 3) ? 2 : 1;
     if (forceMode == 2) mode = 2;

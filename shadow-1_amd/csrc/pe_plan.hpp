@@ -116,6 +116,21 @@ std::vector<int32_t> batch_order_cost(const std::vector<int32_t>& rank, const st
                                       std::vector<double>* cost = nullptr,
                                       std::vector<double>* laneOff = nullptr, int offsetKind = 1);
 
+// Batches per round of the split batch kernels: a round's batches keep one
+// persisted distance array each (perD bytes, the predecessor filter's flag
+// bits included) from the relax to the post kernel.  freeB is the device's
+// free memory now, rest the bytes of the per-slot scratch still to allocate;
+// 12 GiB stay free for what is allocated later, and a round holds at most
+// 160 GiB of distance arrays (C4: one round of 13 GB; C5: one round of 131 GB
+// beside its 107 GB table).  Never below `slots` (a workgroup indexes its
+// scratch by blockIdx; slots <= nBatchesAll except for an empty shard, whose
+// one slot stands) and otherwise never above nBatchesAll; without room, one
+// batch per round and slot.  testCap > 0 (SHDPE_BATCH_ROUND, tests only)
+// bounds the result from above, down to `slots`.
+constexpr size_t ROUND_RESERVE_BYTES = (size_t)12 << 30;
+constexpr size_t ROUND_DIST_CAP_BYTES = (size_t)160 << 30;
+size_t batch_round_size(size_t slots, size_t nBatchesAll, size_t perD, size_t rest, size_t freeB, int testCap);
+
 // 1 sparse SSSP rows, 2 direct rows (complete graph), 3 dense min-plus.
 int select_mode(const HostGraph& g, int forceMode, double denseMin);
 

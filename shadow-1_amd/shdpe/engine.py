@@ -32,7 +32,7 @@ EXPORTS = [
     "shd_pe_compute_rows", "shd_pe_compute_positions", "shd_pe_get_row", "shd_pe_get_rows",
     "shd_pe_copy_rows_device", "shd_pe_synchronize", "shd_pe_get_stats", "shd_pe_reset_stats",
     "shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_pred_filter_counts",
-    "shd_pe_post_split_info",
+    "shd_pe_post_split_info", "shd_pe_batch_info",
     "shd_pe_stream_bandwidth", "shd_pe_num_shards", "shd_pe_shard_bounds", "shd_pe_plan_shards", "shd_pe_owned_range",
     "shd_pe_gather", "shd_pe_comm_unique_id", "shd_pe_comm_init",
     "shd_pe_direct_path", "shd_pe_self_path", "shd_pe_adjacent", "shd_pe_self_paths",
@@ -255,6 +255,7 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_create_built": (C.c_int, [vp, vp, i32, vp, i32, vp, vp]),
         "shd_pe_graph_digest": (C.c_int, [vp, i32, vp, i32, vp]),
         "shd_pe_post_split_info": (C.c_int, [vp, vp, vp, vp]),
+        "shd_pe_batch_info": (C.c_int, [vp, i32, vp]),
     }
     # ABI-3 ... ABI-8 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
@@ -266,7 +267,8 @@ def load_library(path: str = LIB_PATH):
                 "shd_pe_paths_info", "shd_pe_graph_props",
                 "shd_pe_graph_props_host", "shd_pe_fill_rowstore_shards",
                 "shd_topology_fill_shards", "shd_pe_create_built",
-                "shd_pe_graph_digest", "shd_pe_post_split_info"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_pe_graph_digest", "shd_pe_post_split_info",
+                "shd_pe_batch_info"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -628,6 +630,14 @@ class Engine:
         self._chk(self._lib.shd_pe_post_split_info(self.h, C.byref(split), C.byref(waves), C.byref(redo)),
                   "shd_pe_post_split_info")
         return {"split": int(split.value), "labelWaves": int(waves.value), "redoBatches": int(redo.value)}
+
+    def batch_info(self, shard=0) -> dict:
+        """shd_pe_batch_info of one shard: batches per round of the split batch
+        kernels and scratch slots (0 before the shard's first batched compute),
+        rounds and batches run by table computes since the last reset_stats."""
+        out = np.zeros(4, np.int64)
+        self._chk(self._lib.shd_pe_batch_info(self.h, int(shard), _p(out)), "shd_pe_batch_info")
+        return {"perRound": int(out[0]), "slots": int(out[1]), "rounds": int(out[2]), "batches": int(out[3])}
 
     def reset_stats(self):
         self._chk(self._lib.shd_pe_reset_stats(self.h), "shd_pe_reset_stats")

@@ -1,6 +1,7 @@
 // The create-time planning of pe_plan.cpp (degree_order, relabel_graph,
-// batch_ranks, batch_order, select_mode, shd_pe_plan_shards) over graphs that
-// tests/test_host.py writes as raw arrays: a graph directory holds meta.txt
+// batch_ranks, batch_order, select_mode, batch_round_size, shd_pe_plan_shards)
+// over graphs that tests/test_host.py writes as raw arrays (batch_round_size
+// takes plain numbers: its cases are in the code): a graph directory holds meta.txt
 // ("n directed hasVloss"), from.i32, to.i32, lat.f64, loss.f64, vloss.f64 and
 // att.i32 (the attached list); the HostGraph comes from build_host_graph.
 // Built with pe_plan.cpp and pe_graph.cpp, -fsanitize=address,undefined; no HIP.
@@ -11,6 +12,7 @@
 //                           their bit patterns (tests/golden/host_plan_ba1200.txt)
 #include <algorithm>
 #include <cmath>
+#include <cstdint>
 #include <cstdio>
 #include <cstring>
 #include <functional>
@@ -341,6 +343,67 @@ void test_plan_shards() {
     CHECK(shd_pe_plan_shards(0, 2, 16, b) == SHD_PE_OK && b[0] == 0 && b[2] == 0);
 }
 
+// batch_round_size: the batches per round of the split batch kernels, from the
+// free device memory (ensure_batch passes hipMemGetInfo's figure)
+void test_batch_round_size() {
+    const size_t GiB = (size_t)1 << 30, GB = 1000000000;
+    const size_t reserve = ROUND_RESERVE_BYTES, distCap = ROUND_DIST_CAP_BYTES;
+    CHECK(reserve == 12 * GiB && distCap == 160 * GiB);
+    // no room (free memory at or below rest + 12 GiB, or below rest alone): max(slots, 1)
+    const size_t perD = 50 * 1000 * 1000, rest = 3 * GiB;
+    for (size_t freeB : {(size_t)0, rest - 1, rest, rest + 1, rest + reserve - 1, rest + reserve})
+        for (size_t slots : {(size_t)0, (size_t)1, (size_t)7, (size_t)512}) {
+            CHECK(batch_round_size(slots, 4096, perD, rest, freeB, 0) == std::max<size_t>(slots, 1));
+            CHECK(batch_round_size(slots, 4096, perD, rest, freeB, 3) == std::max<size_t>(slots, 1));
+        }
+    // one byte past it is still one batch; room for k arrays is k batches
+    CHECK(batch_round_size(1, 4096, perD, rest, rest + reserve + 1, 0) == 1);
+    CHECK(batch_round_size(1, 4096, perD, rest, rest + reserve + 2 * perD - 1, 0) == 1);
+    CHECK(batch_round_size(1, 4096, perD, rest, rest + reserve + 2 * perD, 0) == 2);
+    CHECK(batch_round_size(1, 4096, perD, rest, rest + reserve + 100 * perD + 17, 0) == 100);
+    // never below slots; never above nBatchesAll (slots <= nBatchesAll); every batch when all fit
+    std::mt19937_64 rng(77);
+    for (int i = 0; i < 20000; ++i) {
+        const size_t nAll = 1 + rng() % 70000, slots = 1 + rng() % std::min<size_t>(nAll, 2048);
+        const size_t pd = 64 * 8 + rng() % (4 * GiB), rs = rng() % (64 * GiB), fr = rng() % (300 * GiB);
+        const int cap = (int)(rng() % 4 == 0 ? 0 : rng() % 3000);
+        const size_t r0 = batch_round_size(slots, nAll, pd, rs, fr, 0), rc = batch_round_size(slots, nAll, pd, rs, fr, cap);
+        CHECK(slots <= nAll);
+        CHECK(r0 >= slots && r0 <= nAll && rc >= slots && rc <= nAll);
+        // the round's distance arrays fit the room and the cap, unless the slots force more
+        if (r0 > slots) CHECK(r0 * pd <= distCap && r0 * pd + rs + reserve <= fr);
+        if (r0 < nAll) CHECK((r0 + 1) * pd > distCap || (r0 + 1) * pd + rs + reserve > fr);
+        // the test cap bounds from above only, and not below the slots
+        CHECK(rc <= r0);
+        if (cap > 0) CHECK(rc == std::max(slots, std::min(r0, (size_t)cap)));
+        else CHECK(rc == r0);
+    }
+    CHECK(batch_round_size(4, 40, perD, rest, 200 * GiB, 0) == 40);
+    CHECK(batch_round_size(4, 40, perD, rest, 200 * GiB, 1000) == 40);   // (a cap above: unchanged)
+    CHECK(batch_round_size(4, 40, perD, rest, 200 * GiB, 5) == 5);
+    CHECK(batch_round_size(4, 40, perD, rest, 200 * GiB, 4) == 4);
+    CHECK(batch_round_size(4, 40, perD, rest, 200 * GiB, 1) == 4);       // (not below the slots)
+    CHECK(batch_round_size(4, 40, perD, rest, 200 * GiB, -1) == 40);
+    // the 160 GiB cap: 1 GiB arrays, 1 TiB free
+    CHECK(batch_round_size(1, 4096, GiB, 0, 1024 * GiB, 0) == 160);
+    CHECK(batch_round_size(1, 4096, GiB + 1, 0, 1024 * GiB, 0) == 159);
+    CHECK(batch_round_size(256, 4096, GiB, 0, 1024 * GiB, 0) == 256);   // (the slots stand above it)
+    // C4: 16,384 rows at 16 lanes = 1,024 batches, 13 GB of distance arrays; C5: 131 GB in
+    // 4,096 batches beside a 107 GB table on a 288 GB card -- one round each
+    CHECK(batch_round_size(1024, 1024, 13 * GB / 1024, 26 * GB, 250 * GiB, 0) == 1024);
+    CHECK(batch_round_size(512, 4096, 131 * GB / 4096 + 1, 33 * GB, 288 * GB - 107 * GB, 0) == 4096);
+    // ... and C5 under a 96 GiB budget would be two: the cap is what keeps it at one
+    CHECK(96 * GiB / (131 * GB / 4096 + 1) < 4096);
+    // near 2^40 bytes: no product or sum wraps
+    const size_t T = (size_t)1 << 40;
+    CHECK(batch_round_size(1, 1000000, T, T, 4 * T, 0) == 1);            // (one array is past the cap)
+    CHECK(batch_round_size(1, 1000000, 16 * GiB, T, 4 * T, 0) == 10);
+    CHECK(batch_round_size(3, 1000000, T - 1, T - 1, T, 0) == 3);
+    CHECK(batch_round_size(2, (size_t)1 << 31, 512, 3 * T, 4 * T, 0) == 160 * GiB / 512);
+    CHECK(batch_round_size(1, 8, 512, SIZE_MAX - 5, SIZE_MAX, 0) == 1);  // (rest + 12 GiB would wrap)
+    CHECK(batch_round_size(1, 8, 0, 0, 64 * GiB, 0) == 8);               // (no vertex)
+}
+
 void put_ints(FILE* f, const char* name, const std::vector<int32_t>& v) {
     std::fprintf(f, "%s %zu\n", name, v.size());
     for (size_t i = 0; i < v.size(); ++i) std::fprintf(f, "%d%c", v[i], (i + 1) % 16 == 0 || i + 1 == v.size() ? '\n' : ' ');
@@ -389,6 +452,7 @@ int main(int argc, char** argv) {
     test_batch_order_ties();
     test_select_mode();
     test_plan_shards();
+    test_batch_round_size();
     if (failures) return 1;
     std::printf("OK\n");
     return 0;

@@ -4,47 +4,15 @@ the oracle, at 8 and 16 lanes and in the 4-, 6- and 8-wave variants; batches
 the label part cannot finish (trees deeper than the walk budget) take the
 redo launch; several batches per workgroup; shd_pe_get_paths; shd_pe_tune.
 
-Graphs: the recipe of tests/test_gpu_pred_filter.py (ba1200 has a degree-114
-vertex: the heavy list of the predecessor part; `directed` its own in-lists;
-`ties` many tie rows: the deferred tie export and the exact kernel)."""
+Graphs and row comparison: tests/post_split_cases.py."""
 import numpy as np
 import pytest
 
-from plan_cost_cases import plan_cost_graphs
-from shdpe import generators as G
+from post_split_cases import CASES, FIELDS, check_rows
+from post_split_cases import chain as _chain
 from shdpe.graph import Topology
 
 pytestmark = pytest.mark.gpu
-
-FIELDS = ("lat", "rel", "hops", "flags", "pred")
-FLAG_SEM = 0x07
-
-
-def _cases():
-    # (third: True = no row leaves the batched path; False = tie rows must
-    # occur; None = quantised, ties as they fall)
-    c = {name: (top, np.asarray(att, np.int32), True) for name, top, att in plan_cost_graphs()}
-    mid = G.random_sparse(300, 36, seed=21)
-    c["middeg"] = (mid, G.sample_attached(300, 77, seed=3).astype(np.int32), True)
-    c["ba1200q"] = (G.power_law(1200, m=3, seed=4, quantum=0.005),
-                    G.sample_attached(1200, 300, seed=2).astype(np.int32), None)
-    c["ties"] = (G.random_sparse(500, 5, seed=36, quantum=1.0), np.arange(0, 500, 2, dtype=np.int32), False)
-    multi = G.with_parallel_edges(G.random_sparse(400, 5, seed=41, vloss=True), 0.3, seed=7)
-    c["multigraph"] = (multi, np.arange(0, 400, 3, dtype=np.int32), True)
-    return c
-
-
-CASES = _cases()
-
-
-def _chain(n, seed):
-    """Path graph 0-1-...-(n-1) with self-loops: one tree, depth up to n-1
-    (a copy of tests/test_gpu_parity.py's)."""
-    rng = np.random.default_rng(seed)
-    src = np.concatenate([np.arange(n - 1), np.arange(n)])
-    dst = np.concatenate([np.arange(1, n), np.arange(n)])
-    m = src.shape[0]
-    return Topology(n, False, src, dst, rng.uniform(1.0, 50.0, m), rng.uniform(0.0, 0.02, m), None)
 
 
 @pytest.fixture(scope="module")
@@ -58,17 +26,6 @@ def E():
 def expected(oracle_mod):
     """The oracle's rows of every case, computed once."""
     return {name: oracle_mod.OracleGraph(top).rows(att, att, threads=8) for name, (top, att, _) in CASES.items()}
-
-
-def check_rows(rows, exp, ctx):
-    ok = (exp["flags"] & 0x03) == 0                # (failed entries carry no values)
-    # the flags the oracle knows: unreachable | no edge | zero latency (F_EXACT marks the rows the
-    # exact kernel wrote: engine-side, as in tests/test_gpu_sizes.py)
-    assert np.array_equal(rows["flags"] & FLAG_SEM, exp["flags"] & FLAG_SEM), ctx
-    for k in ("lat", "rel"):
-        assert np.array_equal(rows[k][ok].view(np.int64), exp[k][ok].view(np.int64)), (ctx, k)
-    for k in ("hops", "pred"):
-        assert np.array_equal(rows[k][ok], exp[k][ok]), (ctx, k)
 
 
 def table(E, top, att, split, monkeypatch, env=(), sources=None, tune=False):
@@ -151,7 +108,7 @@ def test_deep_tree_takes_the_redo_launch(E, oracle_mod, monkeypatch, lb):
 def test_several_batches_per_workgroup(E, expected, monkeypatch, grid):
     """ba1200's 300 rows are 38 batches of 8: with a grid of 1 or 2 every
     workgroup takes many batches in each kernel, and re-derives its state per
-    batch.  (One round: no existing switch makes a small table take two.)"""
+    batch.  (One round; several rounds: tests/test_gpu_rounds.py.)"""
     top, att, _ = CASES["ba1200"]
     rows, st, info = table(E, top, att, True, monkeypatch, env=(("SHDPE_BATCH_LB", 8), ("SHDPE_BATCH_GRID", grid)))
     assert info["split"] == 1 and info["redoBatches"] == 0, info
