@@ -36,13 +36,15 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 12  /* 7: graph property check (shd_pe_graph_props);
+#define SHD_PE_ABI_VERSION 13  /* 7: graph property check (shd_pe_graph_props);
                                   8: fill from row shards (shd_pe_fill_rowstore_shards);
                                   9: shd_pe_pred_filter_counts;
                                   10: shd_pe_create_built (graph build on the device),
                                       shd_pe_graph_digest;
                                   11: shd_pe_post_split_info;
-                                  12: shd_pe_batch_info */
+                                  12: shd_pe_batch_info;
+                                  13: shd_pe_paths_set_row_tier, shd_pe_paths_info's
+                                      info[6] */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -313,7 +315,7 @@ int shd_pe_get_path(ShdPe* pe, int32_t srcVertex, int32_t dstVertex, int32_t* ve
  * verts == NULL is the sizing call: nothing else is written, no Dijkstra is
  * re-run, the call returns 0.  offsets[count] > cap: SHD_PE_EINVAL with
  * offsets (and status) still valid.  Otherwise every non-NULL array is filled,
- * per owning shard in three tiers:
+ * per owning shard in tiers (the batch tier and the row tier never both apply):
  *  - batch tier (the batched multi-source path with split kernels, the large
  *    sparse graphs' default): one relax + post pass over the unique requested
  *    sources, which stores no table row; after each round the requests whose
@@ -325,10 +327,21 @@ int shd_pe_get_path(ShdPe* pe, int32_t srcVertex, int32_t dstVertex, int32_t* ve
  *    the row's final parents in its slot, and their requests are walked over
  *    those.  A slot that fails the emulation's consistency check, and a walk
  *    that does not arrive at its source, are handed on;
+ *  - row tier (off until shd_pe_paths_set_row_tier switches it on; the per-row
+ *    sparse kernel and the dense min-plus path, neither latFold nor forceMode
+ *    3): one pass of the mode's own relax stage over the unique requested
+ *    sources, which stores no table row.  Sparse: in groups of one row per
+ *    resident workgroup, each row's parents stay in its workgroup's scratch
+ *    slot and the requests of the rows without a tie are walked over them; the
+ *    tie rows with a slot go through the tie tier's procedure, group by group.
+ *    Dense: the min-plus sweeps alone, in chunks of the dense batch, and one
+ *    walk per chunk over the converged distance rows, a wave per request, which
+ *    derives each parent as the predecessor pass does (the unique tight in-arc
+ *    of minimum distance) and hands the request on where there is none;
  *  - grouped emulation (every mode; what shd_pe_get_path does, wide): igraph's
  *    Dijkstra on the device (the exact heap emulation) for the remaining
  *    unique sources -- rows the pass sends to the full emulation, sources of
- *    requests handed on, and every source where the first two tiers do not
+ *    requests handed on, and every source where the tiers above do not
  *    apply -- in groups of one row per resident workgroup, one walk launch
  *    per group over all its requests.
  * Only the grouped emulation stores table rows: the values they hold already,
@@ -348,14 +361,22 @@ typedef struct ShdPePathsOut {      /* any pointer but offsets may be NULL */
 int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* dst, int64_t count,
                      const ShdPePathsOut* out);
 /* Of the last shd_pe_get_paths call (ShdPeStats is not touched), the first
- * min(n, 6) of: info[0] unique sources served wholly by the batch tier,
+ * min(n, 7) of: info[0] unique sources served wholly by the batch tier,
  * info[1] unique sources served wholly from early-stop tie parents (the tie
  * tier), info[2] unique sources served by the grouped full emulation (each
- * unique source with a walk counts in exactly one of the three), info[3]
- * requests that left the batch or the tie tier after its check and were
- * finished by the emulation, info[4] emulation groups launched, info[5]
- * device time of the call from events, in integer microseconds. */
+ * unique source with a walk counts in exactly one of info[0], [1], [2] and
+ * [6]), info[3] requests that left the batch, the tie or the row tier after
+ * its check and were finished by the emulation, info[4] emulation groups
+ * launched, info[5] device time of the call from events, in integer
+ * microseconds, info[6] (ABI 13) unique sources served wholly by the row tier. */
 int shd_pe_paths_info(const ShdPe* pe, int64_t* info, int32_t n);
+/* ABI 13.  enable != 0: later shd_pe_get_paths calls may use the row tier
+ * where it applies -- an engine on the per-row sparse kernel (mode 1, not
+ * batched) or on the dense min-plus path (mode 3), neither a latFold multigraph
+ * nor forceMode 3; on every other engine the call succeeds and changes
+ * nothing.  Off by default.  (Under SHD_PE_DEBUG_ENV, SHDPE_PATHS_FAST=0 still
+ * turns every fast tier off.)  Takes the compute lock; NULL: SHD_PE_EINVAL. */
+int shd_pe_paths_set_row_tier(ShdPe* pe, int32_t enable);
 
 /* Page-locked host memory for shd_pe_get_rows destinations (DMA target, no
  * staging copy).  No reference counterpart: Shadow's row buffers are plain

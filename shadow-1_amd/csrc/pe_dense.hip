@@ -416,16 +416,91 @@ void launch_dense_tie_export(const DevGraph& g, const double* D, const int32_t* 
                        st, g, D, P, n, n, dIdx, dPos, tie);
 }
 
+// k_paths_walk_dense (shd_pe_get_paths' row tier on the dense path): the paths
+// of requests whose source's converged distance row sits in D (the sweeps
+// alone ran: no predecessor pass).  One wave64 per request, four per workgroup;
+// the host orders a launch's requests by source, so neighbouring waves gather
+// from one row of D, which stays in L2.  len - 1 steps from the destination: at
+// each vertex v the lanes stride over its in-arcs (inPtr / inCol / inLat when
+// directed, the vertex's own arc row when undirected), test
+// D[u] <= D[v] && fl(D[u] + w) == D[v] and the wave reduces (minimum tight D[u],
+// arcs at that minimum, lowest such arc).  That is the parent as the
+// predecessor pass, k_tie_export and k_paths_walk_dist derive it: a vertex
+// with a unique minimum tight predecessor has it as igraph's parent whatever
+// ties the row has elsewhere.  No tight arc, two arcs at the minimum, a
+// minimum equal to D[v] (a zero increment), a vertex out of range, or not
+// standing on the source at distance 0 after the last step hand the request on
+// (failed[req] = 1: the grouped emulation serves it).  Every test is on
+// reduced values, so a wave never diverges around its shuffles.
+__global__ __launch_bounds__(256) void k_paths_walk_dense(DevGraph g, PathsDenseArgs p) {
+    const int32_t w = (int32_t)(blockIdx.x * 4 + (threadIdx.x >> 6));
+    const int lane = threadIdx.x & 63;
+    if (w >= p.nReqs) return;
+    const PathReq q = dglobal(p.reqs)[w];
+    const int32_t L = dglobal(p.len)[q.req];
+    if (L <= 0) return;
+    int32_t* out = dglobal(p.verts) + dglobal(p.off)[q.req];
+    const double* __restrict__ Dr = dglobal(p.D) + (int64_t)q.slot * p.ldD;
+    const int32_t* oldId = g.oldId ? dglobal(g.oldId) : nullptr;
+    const bool undirected = g.inCol == g.col;
+    const int32_t* __restrict__ ptr = dglobal(undirected ? g.rowPtr : g.inPtr);
+    const int32_t* __restrict__ col = dglobal(undirected ? g.col : g.inCol);
+    const double* __restrict__ lat = dglobal(undirected ? g.lat : g.inLat);
+    int v = q.t;
+    bool ok = v >= 0 && v < g.n;
+    double dv = ok ? Dr[v] : DINF;
+    ok = ok && dv < DINF;
+    for (int32_t k = L - 1; k >= 1 && ok; --k) {
+        if (lane == 0) out[k] = oldId ? oldId[v] : v;
+        const int a0 = ptr[v], a1 = ptr[v + 1];
+        double best = DINF;
+        int cnt = 0, ba = a1, bu = -1;
+        for (int a = a0 + lane; a < a1; a += 64) {
+            const int u = col[a];
+            const double du = Dr[u];
+            if (du <= dv && __dadd_rn(du, lat[a]) == dv) {      // (a plain add: nothing to contract with)
+                if (du < best) { best = du; cnt = 1; ba = a; bu = u; }
+                else if (du == best) ++cnt;                      // (a ascends: ba stays the lowest)
+            }
+        }
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) {
+            const double ob = __shfl_xor(best, o, 64);
+            const int oc = __shfl_xor(cnt, o, 64);
+            const int oa = __shfl_xor(ba, o, 64);
+            const int ou = __shfl_xor(bu, o, 64);
+            if (ob < best) { best = ob; cnt = oc; ba = oa; bu = ou; }
+            else if (ob == best && oc > 0) {
+                cnt += oc;
+                if (oa < ba) { ba = oa; bu = ou; }
+            }
+        }
+        if (cnt != 1 || best == dv || bu < 0 || bu >= g.n) { ok = false; break; }
+        v = bu;
+        dv = best;
+    }
+    if (lane != 0) return;
+    if (ok && v == q.s && dv == 0.0) out[0] = oldId ? oldId[v] : v;
+    else dglobal(p.failed)[q.req] = 1;
+}
+
+void launch_paths_walk_dense(const DevGraph& g, const PathsDenseArgs& a, void* stream) {
+    if (a.nReqs <= 0) return;
+    hipLaunchKernelGGL(k_paths_walk_dense, dim3((unsigned)((a.nReqs + 3) / 4)), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), g, a);
+}
+
 int launch_dense_rows(const DevGraph& g, const DevTable& tab, const double* W, const double* Rl,
                       double* D, int32_t* P, uint8_t* rowActive, uint8_t* rowChanged,
                       uint8_t* rowAmb, int32_t* dAny, uint8_t* chunkEpoch, const int32_t* dRows,
                       int32_t nRows, int64_t n, const Tuning& tu, void* stream, int* sweepsOut,
-                      double* flopsOut) {
+                      double* flopsOut, DenseStage stage) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t ldD = n;
+    const bool all = stage == DENSE_ALL;
     hipLaunchKernelGGL(k_dense_init, dim3((unsigned)((n + 255) / 256), nRows), dim3(256), 0, st, g,
                        W, D, dRows, n, ldD, rowActive);
-    (void)hipMemsetAsync(rowAmb, 0, nRows, st);
+    if (all) (void)hipMemsetAsync(rowAmb, 0, nRows, st);
     const unsigned gx = (unsigned)((n + TCOL - 1) / TCOL);
     const dim3 gridS((unsigned)((nRows + 16 * MI_SWEEP - 1) / (16 * MI_SWEEP)), gx);
     const int miP = tu.densePredMi >= 3 && tu.densePredMi <= 6 && tu.densePredMi != 5 ? tu.densePredMi
@@ -465,6 +540,11 @@ int launch_dense_rows(const DevGraph& g, const DevTable& tab, const double* W, c
         }
         if (!any || sweeps > n) break;
     }
+    if (sweepsOut) *sweepsOut = sweeps + 1;
+    if (!all) {          // the converged rows stay in D: no predecessor pass, no row writer
+        if (flopsOut) *flopsOut = 2.0 * visits * (16.0 * MI_SWEEP) * TCOL * KB;
+        return 0;
+    }
     if (miP == 6)
         hipLaunchKernelGGL((k_minplus<MP_PRED, 6>), gridP, dim3(256), 0, st, g, W, D, n, ldD, nRows,
                            rowActive, rowChanged, dAny, dRows, P, rowAmb, chunkEpoch, 0);
@@ -479,7 +559,6 @@ int launch_dense_rows(const DevGraph& g, const DevTable& tab, const double* W, c
                            nRows, rowActive, rowChanged, dAny, dRows, P, rowAmb, chunkEpoch, 0);
     hipLaunchKernelGGL(k_dense_write, dim3((unsigned)((g.T + 255) / 256), nRows), dim3(256), 0, st,
                        g, tab, D, P, Rl, n, ldD, dRows, rowAmb);
-    if (sweepsOut) *sweepsOut = sweeps + 1;
     // flops: 2 per relaxation; a visit = TR rows x 128 targets x KB u (tile
     // nominal size); the pred pass is one full n x n pass per row
     if (flopsOut)

@@ -158,7 +158,7 @@ struct Tuning {
                                // repair); 3 = k_tie_export treats its first slot as violated
     int pathsGroup = 0;        // shd_pe_get_paths: sources per emulation group (0: exactGrid)
     int pathsChunk = 0;        // ... requests per staging chunk (0: 65,536)
-    int pathsFast = 1;         // ... 0: no batch / tie tier, every source by the grouped emulation
+    int pathsFast = 1;         // ... 0: no batch / tie / row tier, every source by the grouped emulation
     int predFilter = 1;        // on-demand predecessor pass reads only the in-arcs the relax
                                // flagged (0: every in-arc, BatchScratch::arcHit stays null)
     int postSplit = -1;        // split kernels: the post kernel as two (predecessor part,
@@ -296,11 +296,13 @@ struct SparseLaunch {
 
 // kernels (pe_kernels.hip); all launched on `stream`.
 // rowAmbig[i]: 0 fast path, 1 full heap emulation, 2 + k tie data in slot k
-// of *dTie (device copy; null disables the export)
+// of *dTie (device copy; null disables the export).  noRow (shd_pe_get_paths'
+// row tier, nRows <= cfg.grid): no table row is stored; row i's parents stay
+// in scratch slot i
 void launch_sparse_rows(const DevGraph& g, const DevTable& tab, const DevScratch& sc,
                         const int32_t* dRows, int32_t nRows, uint8_t* dRowAmbig,
                         const SparseLaunch& cfg, int32_t* dDbg, const TieBuf* dTie,
-                        void* stream);
+                        void* stream, bool noRow = false);
 // dSlots (may be null): per exact row its tie slot (-1 = full emulation);
 // rows with a slot stop at the slot's threshold and leave their final
 // parents in tie.P for launch_tie_write
@@ -450,6 +452,19 @@ struct PathsDistArgs {
     uint8_t* failed;         // [count] 1: handed on to the emulation
 };
 void launch_paths_walk_dist(const DevGraph& g, const BatchScratch& bs, const PathsDistArgs& a, void* stream);
+// the same walk over converged min-plus distance rows (pe_dense.hip), a wave per
+// request: PathReq::slot = the source's row of D
+struct PathsDenseArgs {
+    const PathReq* reqs;
+    int32_t nReqs;
+    const double* D;         // [rows][ldD]
+    int64_t ldD;
+    const int32_t* len;
+    const int64_t* off;
+    int32_t* verts;
+    uint8_t* failed;         // [count] 1: handed on to the emulation
+};
+void launch_paths_walk_dense(const DevGraph& g, const PathsDenseArgs& a, void* stream);
 void launch_paths_size(const DevGraph& gAux, const DevTable& tab, const PathsSizeArgs& a, void* stream);
 void launch_paths_scan(const int32_t* dLen, int32_t count, int64_t* dOff, void* stream);
 // the flag bytes of table rows dRows[0, nRows) to dBuf (nRows x T) or back
@@ -462,12 +477,16 @@ void launch_paths_hops(const DevGraph& gAux, const int64_t* dOff, int32_t count,
                        const int32_t* dVerts, double* dHopLat, double* dHopRel, int32_t* dNFailed,
                        void* stream);
 // dense path (pe_dense.hip)
+// launch_dense_rows' stages: everything (sweeps, predecessor pass, row writer),
+// or the sweeps to convergence alone, which leave the distance rows in D and
+// touch neither P, rowAmb nor the table (shd_pe_get_paths' row tier)
+enum DenseStage { DENSE_ALL = 0, DENSE_SWEEPS = 1 };
 void launch_dense_build(const DevGraph& g, double* W, double* Rl, int64_t n, int64_t nArcs,
                         void* stream);
 int launch_dense_rows(const DevGraph& g, const DevTable& tab, const double* W, const double* Rl,
                       double* D, int32_t* P, uint8_t* rowActive, uint8_t* rowChanged,
                       uint8_t* rowAmb, int32_t* dAny, uint8_t* chunkEpoch, const int32_t* dRows,
                       int32_t nRows, int64_t n, const Tuning& tu, void* stream, int* sweepsOut,
-                      double* flopsOut);
+                      double* flopsOut, DenseStage stage);
 
 }  // namespace shdpe

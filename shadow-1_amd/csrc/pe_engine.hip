@@ -1114,7 +1114,7 @@ static int relax_dense(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, Ex
         double flops = 0.0;
         if (launch_dense_rows(sh->dg, sh->tab, sh->dW, sh->dRl, sh->dD, sh->dP, sh->dRowA, sh->dRowB,
                               sh->dRowAmbD, sh->dAny, sh->dChunkEpoch, sh->dRows + d0, dc, pe->hg.n,
-                              pe->tu, sh->stream, &sweeps, &flops))
+                              pe->tu, sh->stream, &sweeps, &flops, DENSE_ALL))
             return SHD_PE_EHIP;
         HIPCHK(hipGetLastError());
         HIPCHK(hipEventRecord(sh->evB, sh->stream));
@@ -2241,6 +2241,151 @@ static int paths_tier_tie(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w, const
     return SHD_PE_OK;
 }
 
+// Whether shd_pe_get_paths' row tier applies to this engine: switched on
+// (shd_pe_paths_set_row_tier), on the per-row sparse kernel or the dense
+// min-plus path, the modes whose relax stage the batch tier does not cover.
+static bool row_tier_applies(const ShdPe* pe) {
+    return pe->pathsRowTier && pe->tu.pathsFast && pe->opt.forceMode != 3 && !pe->hg.latFold &&
+           ((pe->mode == 1 && !pe->batched) || pe->mode == 3);
+}
+
+// Row tier, sparse form: the work set's sources in groups of at most one row
+// per resident workgroup, so k_sparse_rows (the form that stores no table row)
+// runs row i of the group in workgroup i and leaves its parents in scratch
+// slot i.  Per group: one k_paths_walk over the requests of the rows it did not
+// flag; then its tie rows with a slot go through the tie tier's procedure --
+// relevance scan, early-stop emulation (enqueued after the walk: it reuses the
+// scratch slots), a walk over tie.P, the slots' consistency check.  The slots
+// of one group are overwritten by the next.  Handed on: the rows flagged
+// without a slot (all their requests), the rows whose slot failed the check,
+// and every walk that did not arrive.
+static int paths_rows_sparse(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    int rc;
+    if ((rc = ensure_tie(pe, sh))) return rc;
+    const int32_t G = std::max(1, pe->tu.pathsGroup > 0 ? std::min(pe->tu.pathsGroup, sh->cfg.grid) : sh->cfg.grid);
+    const size_t nU = w.uniq.size();
+    // per place in uniq: 0 walked on its slot's parents, 1 full emulation, 2 tie slot, 3 a slot that failed
+    std::vector<uint8_t> kind(nU, 0), amb((size_t)G);
+    std::vector<std::vector<PathReq>> uploads;           // (what the copies read lives until the last
+    std::vector<ExactWork> ties;                         // synchronise; growing moves the inner arrays intact)
+    sh->pathSrc = -1;                                    // slot 0 is overwritten
+    HIPCHK(hipMemcpyAsync(s.rows, w.uniq.data(), nU * 4, hipMemcpyHostToDevice, sh->stream));
+    for (size_t u0 = 0; u0 < nU; u0 += (size_t)G) {
+        const int32_t g = (int32_t)std::min<size_t>((size_t)G, nU - u0);
+        const std::pair<size_t, size_t> r = reqs_in(w.reqs, (int32_t)u0, (int32_t)u0 + g);
+        if (sh->dTie) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
+        launch_sparse_rows(sh->dg, sh->tab, sh->sc, s.rows + u0, g, sh->dRowAmbig, sh->cfg, nullptr, sh->dTie,
+                           sh->stream, true);
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipMemcpyAsync(amb.data(), sh->dRowAmbig, (size_t)g, hipMemcpyDeviceToHost, sh->stream));
+        HIPCHK(hipStreamSynchronize(sh->stream));
+        ties.emplace_back();
+        ExactWork& tie = ties.back();                    // the group's tie rows with a slot
+        std::vector<int32_t> tiePlace;
+        for (int32_t i = 0; i < g; ++i) {
+            kind[u0 + (size_t)i] = amb[(size_t)i] >= 2 ? 2 : amb[(size_t)i];
+            if (amb[(size_t)i] < 2) continue;
+            tie.rows.push_back(w.uniq[u0 + (size_t)i]);
+            tie.slots.push_back(amb[(size_t)i] - 2);
+            tiePlace.push_back((int32_t)u0 + i);
+        }
+        uploads.emplace_back();
+        std::vector<PathReq>& up = uploads.back();       // [walks on the scratch slots | walks on tie.P]
+        for (size_t i = r.first; i < r.second; ++i)
+            if (kind[(size_t)w.reqs[i].slot] == 0)
+                up.push_back(PathReq{w.reqs[i].req, w.reqs[i].slot - (int32_t)u0, w.reqs[i].s, w.reqs[i].t});
+        const size_t nWalk = up.size();
+        for (size_t i = r.first; i < r.second; ++i)
+            if (kind[(size_t)w.reqs[i].slot] == 2)
+                up.push_back(PathReq{w.reqs[i].req, amb[(size_t)w.reqs[i].slot - u0] - 2, w.reqs[i].s, w.reqs[i].t});
+        PathReq* const dUp = s.reqsB + r.first;          // (the group's own part of the chunk's requests)
+        if (!up.empty())
+            HIPCHK(hipMemcpyAsync(dUp, up.data(), up.size() * sizeof(PathReq), hipMemcpyHostToDevice, sh->stream));
+        if ((rc = paths_walk(pe, sh, s, dUp, nWalk, sh->sc.pred, sh->sc.stride, 2))) return rc;
+        const int32_t nTie = (int32_t)tie.rows.size();
+        if (nTie == 0) continue;
+        HIPCHK(hipMemcpyAsync(sh->dRows, tie.rows.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipMemcpyAsync(sh->dSlots, tie.slots.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+        scan_tie_slots(pe, sh, tie.slots, nTie);
+        if ((rc = paths_emulate(pe, sh, sh->dRows, nTie, sh->exactGrid, sh->dSlots)) ||
+            (rc = paths_walk(pe, sh, s, dUp + nWalk, up.size() - nWalk, sh->tie.P, sh->tie.n, 2)))
+            return rc;
+        std::vector<int32_t> redo;                       // (synchronises)
+        if ((rc = failed_tie_rows(sh, tie.rows.data(), tie.slots.data(), nTie, sh->tie.cap, redo))) return rc;
+        for (int32_t p : redo)
+            for (int32_t j = 0; j < nTie; ++j)
+                if (tie.rows[(size_t)j] == p) kind[(size_t)tiePlace[(size_t)j]] = 3;
+    }
+    std::vector<uint8_t> failed((size_t)c.cnt), stay(w.reqs.size()), left(nU, 0);
+    HIPCHK(hipMemcpyAsync(failed.data(), s.failed, failed.size(), hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    HIPCHK(hipMemsetAsync(s.failed, 0, failed.size(), sh->stream));
+    for (size_t i = 0; i < w.reqs.size(); ++i) {
+        const size_t pl = (size_t)w.reqs[i].slot;
+        stay[i] = kind[pl] == 1 || kind[pl] == 3 || failed[(size_t)w.reqs[i].req];
+        pe->pathsInfo[3] += stay[i] && kind[pl] != 1;
+        left[pl] |= stay[i];
+    }
+    for (size_t pl = 0; pl < nU; ++pl)                   // each source served in full, under its tier
+        if (!left[pl]) pe->pathsInfo[kind[pl] == 0 ? 6 : 1] += 1;
+    w.keep(stay);
+    return SHD_PE_OK;
+}
+
+// Row tier, dense form: the work set's sources in chunks of the dense batch,
+// as relax_dense chunks them; per chunk the min-plus sweeps to convergence
+// alone (no predecessor pass, no row writer) and one k_paths_walk_dense over
+// the chunk's requests on the converged distance rows, which derives the
+// parents along the requested chains only.  A request whose walk meets a tie
+// is handed on with its source (no dense tie slots for paths).
+static int paths_rows_dense(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    int rc;
+    if ((rc = ensure_dense(pe, sh))) return rc;
+    const size_t nU = w.uniq.size(), DR = (size_t)sh->denseRows;
+    std::vector<PathReq> up = w.reqs;                    // PathReq::slot: the source's row of D in its chunk
+    for (PathReq& q : up) q.slot = (int32_t)((size_t)q.slot % DR);
+    HIPCHK(hipMemcpyAsync(s.rows, w.uniq.data(), nU * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemcpyAsync(s.reqsB, up.data(), up.size() * sizeof(PathReq), hipMemcpyHostToDevice, sh->stream));
+    for (size_t d0 = 0; d0 < nU; d0 += DR) {
+        const int32_t dc = (int32_t)std::min(DR, nU - d0);
+        const std::pair<size_t, size_t> r = reqs_in(w.reqs, (int32_t)d0, (int32_t)d0 + dc);
+        if (launch_dense_rows(sh->dg, sh->tab, sh->dW, sh->dRl, sh->dD, sh->dP, sh->dRowA, sh->dRowB, sh->dRowAmbD,
+                              sh->dAny, sh->dChunkEpoch, s.rows + d0, dc, pe->hg.n, pe->tu, sh->stream, nullptr,
+                              nullptr, DENSE_SWEEPS))
+            return SHD_PE_EHIP;
+        launch_paths_walk_dense(sh->dg, PathsDenseArgs{s.reqsB + r.first, (int32_t)(r.second - r.first), sh->dD,
+                                                       (int64_t)pe->hg.n, s.len, s.off, s.verts, s.failed},
+                                sh->stream);
+        HIPCHK(hipGetLastError());
+    }
+    std::vector<uint8_t> failed((size_t)c.cnt), stay(w.reqs.size());
+    HIPCHK(hipMemcpyAsync(failed.data(), s.failed, failed.size(), hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));            // (`up` is read by then)
+    HIPCHK(hipMemsetAsync(s.failed, 0, failed.size(), sh->stream));
+    for (size_t i = 0; i < w.reqs.size(); ++i) {
+        stay[i] = failed[(size_t)w.reqs[i].req];
+        pe->pathsInfo[3] += stay[i];
+    }
+    pe->pathsInfo[6] += w.keep(stay);
+    return SHD_PE_OK;
+}
+
+// Row tier (shd_pe_paths_set_row_tier; where the batch tier does not apply):
+// one pass of the mode's own relax stage over the work set's sources, storing
+// no table row, and the walks.  ShdPeStats is put back as it was.
+static int paths_tier_rows(ShdPe* pe, PathsCall& c, size_t k, PathsWork& w) {
+    Shard* sh = pe->shards[k].get();
+    if (w.reqs.empty() || !row_tier_applies(pe)) return SHD_PE_OK;
+    const ShdPeStats savedStats = sh->stats;
+    const int rc = pe->mode == 3 ? paths_rows_dense(pe, c, k, w) : paths_rows_sparse(pe, c, k, w);
+    sh->stats = savedStats;
+    return rc;
+}
+
 // Grouped emulation, the last tier: igraph's whole Dijkstra for each source
 // left, a group per launch: row i of the group runs in workgroup i and leaves
 // every popped vertex's chosen IN-arc in scratch slot i (no tie slots: full
@@ -2340,7 +2485,8 @@ static int paths_extract_chunk(ShdPe* pe, PathsCall& c, size_t k) {
     HIPCHK(hipMemsetAsync(s.failed, 0, (size_t)c.cnt, sh->stream));
     HIPCHK(hipMemsetAsync(s.nFailed, 0, 16, sh->stream));
     if ((rc = paths_trivial(pe, c, k, w)) || (rc = paths_tier_batch(pe, c, k, w, tie)) ||
-        (rc = paths_tier_tie(pe, c, k, w, tie)) || (rc = paths_tier_emulation(pe, c, k, w)))
+        (rc = paths_tier_tie(pe, c, k, w, tie)) || (rc = paths_tier_rows(pe, c, k, w)) ||
+        (rc = paths_tier_emulation(pe, c, k, w)))
         return rc;
     return paths_hops_and_copy_out(pe, c, k, total);
 }
@@ -2423,7 +2569,14 @@ extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* ds
 extern "C" int shd_pe_paths_info(const ShdPe* pe, int64_t* info, int32_t n) {
     if (!pe || !info || n < 0) return SHD_PE_EINVAL;
     std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
-    for (int32_t k = 0; k < std::min<int32_t>(n, 6); ++k) info[k] = pe->pathsInfo[k];
+    for (int32_t k = 0; k < std::min<int32_t>(n, 7); ++k) info[k] = pe->pathsInfo[k];
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_paths_set_row_tier(ShdPe* pe, int32_t enable) {
+    if (!pe) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(pe->mu);
+    pe->pathsRowTier = enable != 0;
     return SHD_PE_OK;
 }
 

@@ -150,7 +150,8 @@ struct ShdPe {
     std::mutex mu;                   // compute / gather
     std::mutex copyMu;               // staging buffers
     double msGather = 0.0;
-    int64_t pathsInfo[6] = {0, 0, 0, 0, 0, 0};   // shd_pe_paths_info of the last shd_pe_get_paths
+    int64_t pathsInfo[7] = {0, 0, 0, 0, 0, 0, 0};   // shd_pe_paths_info of the last shd_pe_get_paths
+    bool pathsRowTier = false;       // shd_pe_paths_set_row_tier
 };
 
 #define HIPCHK(x)                                   \

@@ -365,7 +365,11 @@ __device__ __forceinline__ void process_group(const DevGraph& g, const RowCtx<LA
 // ---------------------------------------------------------------------------
 // k_sparse_rows
 // ---------------------------------------------------------------------------
-template <int LAYOUT, int LPV>
+// NOROW (shd_pe_get_paths' row tier): a row without ties stores no table row
+// -- its parents in the workgroup's scratch slot are the result -- and skips
+// the label repair; a tie row exports its slot as ever.  Instantiations of
+// their own, so the table kernels' code is what it was.
+template <int LAYOUT, int LPV, bool NOROW = false>
 __global__ __launch_bounds__(SP_THREADS) void k_sparse_rows(
     DevGraph g0, DevTable tab0, DevScratch sc0, const int32_t* __restrict__ rows, int32_t nRows,
     uint8_t* rowAmbig, double delta, int32_t qcap, int32_t hcap, int32_t heavyDeg, int32_t* dbg,
@@ -867,6 +871,11 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_rows(
                 }
             }
             if (tid == 0) rowAmbig[b] = sl >= 0 ? (uint8_t)(2 + sl) : (uint8_t)1;
+            __syncthreads();
+            continue;
+        }
+        if constexpr (NOROW) {
+            if (tid == 0) rowAmbig[b] = 0;
             __syncthreads();
             continue;
         }
@@ -2003,14 +2012,14 @@ __global__ __launch_bounds__(256) void k_direct_rows(DevGraph g0, DevTable tab0,
 // ---------------------------------------------------------------------------
 int sparse_max_threads() { return SP_THREADS; }
 
-template <int L, int LPV>
+template <int L, int LPV, bool NOROW = false>
 static void launch_sparse_lpv(const DevGraph& g, const DevTable& tab, const DevScratch& sc,
                               const int32_t* dRows, int32_t nRows, uint8_t* dRowAmbig,
                               const SparseLaunch& cfg, int32_t* dDbg, const TieBuf* dTie,
                               hipStream_t st, int grid) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sparse_rows<L, LPV>),
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_sparse_rows<L, LPV, NOROW>),
                               hipFuncAttributeMaxDynamicSharedMemorySize, cfg.ldsBytes);
-    hipLaunchKernelGGL((k_sparse_rows<L, LPV>), dim3(grid), dim3(cfg.threads), cfg.ldsBytes, st,
+    hipLaunchKernelGGL((k_sparse_rows<L, LPV, NOROW>), dim3(grid), dim3(cfg.threads), cfg.ldsBytes, st,
                        g, tab, sc, dRows, nRows, dRowAmbig, cfg.delta, cfg.qcap, cfg.hcap,
                        cfg.heavyDeg, dDbg, cfg.kflags, dTie);
 }
@@ -2035,10 +2044,21 @@ static void launch_sparse_layout(const DevGraph& g, const DevTable& tab, const D
 void launch_sparse_rows(const DevGraph& g, const DevTable& tab, const DevScratch& sc,
                         const int32_t* dRows, int32_t nRows, uint8_t* dRowAmbig,
                         const SparseLaunch& cfg, int32_t* dDbg, const TieBuf* dTie,
-                        void* stream) {
+                        void* stream, bool noRow) {
     if (nRows <= 0) return;
     const int grid = nRows < cfg.grid ? nRows : cfg.grid;
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (noRow) {       // (4 lanes per light vertex whatever kflags selects: the parents do not depend on it)
+        if (cfg.layout == 3)
+            launch_sparse_lpv<3, 4, true>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);
+        else if (cfg.layout == 2)
+            launch_sparse_lpv<2, 4, true>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);
+        else if (cfg.layout == 1)
+            launch_sparse_lpv<1, 4, true>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);
+        else
+            launch_sparse_lpv<0, 4, true>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);
+        return;
+    }
     if (cfg.layout == 3)
         launch_sparse_layout<3>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);
     else if (cfg.layout == 2)

@@ -55,6 +55,7 @@ EXPORTS = [
     "shd_pe_get_paths", "shd_pe_paths_info",
     "shd_pe_graph_props", "shd_pe_graph_props_host",
     "shd_pe_create_built", "shd_pe_graph_digest",
+    "shd_pe_paths_set_row_tier",
 ]
 VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
 VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
@@ -256,6 +257,7 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_graph_digest": (C.c_int, [vp, i32, vp, i32, vp]),
         "shd_pe_post_split_info": (C.c_int, [vp, vp, vp, vp]),
         "shd_pe_batch_info": (C.c_int, [vp, i32, vp]),
+        "shd_pe_paths_set_row_tier": (C.c_int, [vp, i32]),
     }
     # ABI-3 ... ABI-8 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
@@ -268,7 +270,7 @@ def load_library(path: str = LIB_PATH):
                 "shd_pe_graph_props_host", "shd_pe_fill_rowstore_shards",
                 "shd_topology_fill_shards", "shd_pe_create_built",
                 "shd_pe_graph_digest", "shd_pe_post_split_info",
-                "shd_pe_batch_info"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_pe_batch_info", "shd_pe_paths_set_row_tier"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -599,11 +601,19 @@ class Engine:
 
     def paths_info(self) -> dict:
         """shd_pe_paths_info of the last get_paths: unique sources per tier,
-        requests handed on, emulation groups, device ms."""
-        info = np.zeros(6, np.int64)
-        self._chk(self._lib.shd_pe_paths_info(self.h, _p(info), 6), "shd_pe_paths_info")
+        requests handed on, emulation groups, device ms.  ("rows", the row tier's
+        sources: 0 from a library before ABI 13, which has no such tier.)"""
+        info = np.zeros(7, np.int64)
+        n = 7 if hasattr(self._lib, "shd_pe_paths_set_row_tier") else 6    # (the ABI 13 entry point)
+        self._chk(self._lib.shd_pe_paths_info(self.h, _p(info), n), "shd_pe_paths_info")
         return {"batch": int(info[0]), "tie": int(info[1]), "emulated": int(info[2]),
-                "handed_on": int(info[3]), "groups": int(info[4]), "device_ms": info[5] / 1000.0}
+                "handed_on": int(info[3]), "groups": int(info[4]), "device_ms": info[5] / 1000.0,
+                "rows": int(info[6])}
+
+    def set_paths_row_tier(self, on: bool = True):
+        """shd_pe_paths_set_row_tier: let get_paths serve the per-row sparse and the
+        dense min-plus mode from one pass of their own relax stage (off by default)."""
+        self._chk(self._lib.shd_pe_paths_set_row_tier(self.h, 1 if on else 0), "shd_pe_paths_set_row_tier")
 
     def tune(self):
         """shd_pe_tune: time both k_batch_rows variants on this engine's rows,

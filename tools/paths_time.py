@@ -16,12 +16,32 @@ every first miss of a source.  One process, after compute_all:
             Its paths are checked equal to the batched call's before anything
             is written.
 
-  python tools/paths_time.py [--config c4q] [--out profiles/paths_c4shape.json]"""
+  python tools/paths_time.py [--config c4q] [--out profiles/paths_c4shape.json]
+
+The per-row sparse and the dense mode (--config c2, --config c3b), whose fast
+tier is the row tier (shd_pe_paths_set_row_tier), take another protocol: this
+process starts one child per step, each under its own `timeout`, and starts
+nothing more once a step has failed.
+
+  rows      (with --row-tier) compute_all for scale, the sizing call, then the
+            call with the row tier on: a warm-up, `--repeats` timed calls, the
+            per-tier counters.
+  emu       the same engine without the row tier, every source by the grouped
+            emulation: all requests, or (--emu-sources N; 512 by default at c3b,
+            where a full run takes minutes) those of the first N sources, scaled
+            to all by the number of emulation groups.  Its bytes must equal the
+            row tier's for the same requests.
+
+  python tools/paths_time.py --config c2 --row-tier     -> profiles/paths_c2shape.json
+  python tools/paths_time.py --config c3b --row-tier    -> profiles/paths_c3bshape.json
+  SHDPE_LIB=<older build> python tools/paths_time.py --config c2 --out <file>   (emu alone)"""
 import argparse
 import ctypes as C
+import hashlib
 import json
 import os
 import statistics
+import subprocess
 import sys
 import time
 
@@ -33,9 +53,159 @@ def _range(xs):
     return {"median": statistics.median(xs), "min": min(xs), "max": max(xs)}
 
 
+ROW_TIER_CONFIGS = ("c2", "c2q", "c3b", "c3bq")
+
+
+def _digest(out, n):
+    """sha256 of the output of the first n requests (paths lie in request order)."""
+    offsets, verts, status, hl, hr = out
+    e = int(offsets[n])
+    h = hashlib.sha256()
+    for a in (offsets[:n + 1], verts[:e], status[:n], hl[:e], hr[:e]):
+        h.update(a.tobytes())
+    return h.hexdigest()
+
+
+def _requests(eng):
+    import numpy as np
+    T = eng.T
+    src = eng.attached.copy()
+    dst = eng.attached[(7919 * np.arange(T, dtype=np.int64) + 1) % T].astype(np.int32)
+    return src, dst
+
+
+def _timed_calls(eng, src, dst, what, repeats):
+    wall, dev, out, info = [], [], None, None
+    for _ in range(repeats):
+        t0 = time.perf_counter()
+        out = eng.get_paths(src, dst, hops=True)
+        wall.append((time.perf_counter() - t0) * 1e3)
+        info = eng.paths_info()
+        dev.append(info["device_ms"])
+        print(f"{what}: {wall[-1]:.1f} ms wall, {dev[-1]:.1f} ms device", file=sys.stderr, flush=True)
+    return out, wall, dev, info
+
+
+def step_rows(args):
+    """Child: compute_all, sizing, the call with the row tier on."""
+    import numpy as np
+    from shdpe import engine as E
+    from shdpe import generators as G
+    top, att = G.make_config(args.config)
+    eng = E.Engine(top, att)                 # raises without a gfx950 device: no fallback
+    eng.reset_stats()
+    eng.compute_all()
+    st = eng.stats()
+    T = eng.T
+    src, dst = _requests(eng)
+    lib = E.load_library()
+    size_ms = []
+    for _ in range(1 + max(5, args.repeats)):            # (the first: code object load)
+        offsets = np.zeros(T + 1, np.int64)
+        status = np.zeros(T, np.int32)
+        o = E.PathsOutC(offsets.ctypes.data_as(C.c_void_p), None, None, None, status.ctypes.data_as(C.c_void_p), 0)
+        t0 = time.perf_counter()
+        rc = lib.shd_pe_get_paths(eng.h, src.ctypes.data_as(C.c_void_p), dst.ctypes.data_as(C.c_void_p), T,
+                                  C.byref(o))
+        if rc:
+            raise SystemExit(f"shd_pe_get_paths (sizing): {rc}")
+        size_ms.append((time.perf_counter() - t0) * 1e3)
+    eng.set_paths_row_tier(True)
+    eng.get_paths(src, dst, hops=True)                   # warm-up
+    out, wall, dev, info = _timed_calls(eng, src, dst, "row tier", args.repeats)
+    lens = np.diff(out[0])
+    n_emu = args.emu_sources if 0 < args.emu_sources < T else T
+    res = {
+        "mode": st["mode"], "vertices": int(top.n), "requests": int(T),
+        "compute_all_ms": st["msTotal"], "rows_exact": st["rowsExact"], "rows_tie_early": st["rowsTieEarly"],
+        "sizing_call_wall_ms": _range(size_ms[1:]),
+        "row_tier_calls_timed": len(wall), "row_tier_wall_ms": _range(wall), "row_tier_device_ms": _range(dev),
+        "sources_by_tier": {"rows": info["rows"], "tie": info["tie"], "emulated": info["emulated"],
+                            "batch": info["batch"]},
+        "requests_handed_on": info["handed_on"], "emulation_groups": info["groups"],
+        "row_tier_over_compute_all": statistics.median(dev) / st["msTotal"] if st["msTotal"] else None,
+        "path_entries": int(out[0][-1]), "path_vertices_mean": float(lens.mean()), "path_vertices_max": int(lens.max()),
+        "digest_requests": n_emu, "digest": _digest(out, n_emu),
+    }
+    eng.close()
+    with open(args.out, "w") as f:
+        json.dump(res, f)
+
+
+def step_emu(args):
+    """Child: the grouped emulation alone, over all requests or a sample of sources."""
+    from shdpe import engine as E
+    from shdpe import generators as G
+    top, att = G.make_config(args.config)
+    eng = E.Engine(top, att)
+    eng.reset_stats()
+    eng.compute_all()
+    st = eng.stats()
+    T = eng.T
+    src, dst = _requests(eng)
+    n = args.emu_sources if 0 < args.emu_sources < T else T
+    eng.get_paths(src[:2], dst[:2], hops=True)           # warm-up: code object load
+    out, wall, dev, info = _timed_calls(eng, src[:n], dst[:n], f"emulation only, {n} sources",
+                                        args.emu_repeats or (args.repeats if n == T else 1))
+    if info["emulated"] != n or info["batch"] or info["tie"] or info.get("rows", 0):
+        raise SystemExit(f"not the grouped emulation alone: {info}")
+    per_group = -(-info["emulated"] // max(1, info["groups"]))
+    scale = -(-T // per_group) / max(1, info["groups"])
+    res = {
+        "emulation_only_sources": int(n), "emulation_only_calls_timed": len(wall),
+        "emulation_only_groups": info["groups"], "emulation_rows_per_group": int(per_group),
+        "emulation_only_wall_ms": _range(wall), "emulation_only_device_ms": _range(dev),
+        "emulation_only_scale_to_all": scale,
+        "emulation_only_wall_ms_scaled": statistics.median(wall) * scale,
+        "emulation_only_device_ms_scaled": statistics.median(dev) * scale,
+        "emulation_compute_all_ms": st["msTotal"],
+        "digest_requests": int(n), "digest": _digest(out, n),
+        "library": "SHDPE_LIB" if os.environ.get("SHDPE_LIB") else "in-tree",
+    }
+    eng.close()
+    with open(args.out, "w") as f:
+        json.dump(res, f)
+
+
+def run_steps(args):
+    """This process opens no GPU: one child per step under its own time limit,
+    in sequence, and nothing more after a step that failed."""
+    steps = (["rows"] if args.row_tier else []) + ["emu"]
+    res = {"config": args.config, "unit": "ms"}
+    digests = {}
+    for step in steps:
+        part = f"{args.out}.{step}.part"
+        cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__),
+               "--config", args.config, "--step", step, "--out", part, "--repeats", str(args.repeats),
+               "--emu-repeats", str(args.emu_repeats), "--emu-sources", str(args.emu_sources)]
+        rc = subprocess.run(cmd).returncode
+        if rc:
+            raise SystemExit(f"step {step}: exit status {rc}; no further step was started")
+        with open(part) as f:
+            got = json.load(f)
+        os.remove(part)
+        digests[step] = (got.pop("digest_requests"), got.pop("digest"))
+        res.update(got)
+    if len(digests) == 2:
+        if digests["rows"] != digests["emu"]:
+            raise SystemExit(f"the row tier and the grouped emulation alone differ: {digests}")
+        res["bytes_equal_over_requests"] = digests["emu"][0]
+        res["emulation_only_over_row_tier_wall"] = (res["emulation_only_wall_ms_scaled"] /
+                                                    res["row_tier_wall_ms"]["median"])
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    with open(args.out, "w") as f:
+        json.dump(res, f, indent=1)
+    print(json.dumps(res))
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--config", default="c4")
+    ap.add_argument("--row-tier", action="store_true", help="c2 / c3b: time the call with the row tier on")
+    ap.add_argument("--emu-sources", type=int, default=-1,
+                    help="c2 / c3b: sources of the emulation-only call (0: all; default: all, 512 at c3b)")
+    ap.add_argument("--step", choices=("rows", "emu"), default=None, help="(a child of the c2 / c3b protocol)")
+    ap.add_argument("--step-timeout", type=int, default=900, help="seconds per step of the c2 / c3b protocol")
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--emu-repeats", type=int, default=0, help="calls of the emulation-only engine (0: --repeats)")
     ap.add_argument("--sample", type=int, default=64)
@@ -43,6 +213,12 @@ def main():
     args = ap.parse_args()
     if args.out is None:
         args.out = os.path.join(ROOT, "profiles", f"paths_{args.config}shape.json")
+    if args.emu_sources < 0:
+        args.emu_sources = 512 if args.config.startswith("c3") else 0
+    if args.step:
+        return step_rows(args) if args.step == "rows" else step_emu(args)
+    if args.row_tier or args.config in ROW_TIER_CONFIGS:
+        return run_steps(args)
     import numpy as np
     from shdpe import engine as E
     from shdpe import generators as G
