@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 13  /* 7: graph property check (shd_pe_graph_props);
+#define SHD_PE_ABI_VERSION 14  /* 7: graph property check (shd_pe_graph_props);
                                   8: fill from row shards (shd_pe_fill_rowstore_shards);
                                   9: shd_pe_pred_filter_counts;
                                   10: shd_pe_create_built (graph build on the device),
@@ -44,7 +44,9 @@ extern "C" {
                                   11: shd_pe_post_split_info;
                                   12: shd_pe_batch_info;
                                   13: shd_pe_paths_set_row_tier, shd_pe_paths_info's
-                                      info[6] */
+                                      info[6];
+                                  14: shd_pe_path_load, shd_pe_path_load_info, shd_pe_num_arcs,
+                                      shd_pe_arc_list, shd_pe_find_arc, shd_topology_link_load */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -360,8 +362,9 @@ typedef struct ShdPePathsOut {      /* any pointer but offsets may be NULL */
 } ShdPePathsOut;
 int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* dst, int64_t count,
                      const ShdPePathsOut* out);
-/* Of the last shd_pe_get_paths call (ShdPeStats is not touched), the first
- * min(n, 7) of: info[0] unique sources served wholly by the batch tier,
+/* Of the last shd_pe_get_paths or shd_pe_path_load call (the load call fills
+ * them as a shd_pe_get_paths call of the same requests does; ShdPeStats is not
+ * touched), the first min(n, 7) of: info[0] unique sources served wholly by the batch tier,
  * info[1] unique sources served wholly from early-stop tie parents (the tie
  * tier), info[2] unique sources served by the grouped full emulation (each
  * unique source with a walk counts in exactly one of info[0], [1], [2] and
@@ -377,6 +380,67 @@ int shd_pe_paths_info(const ShdPe* pe, int64_t* info, int32_t n);
  * nothing.  Off by default.  (Under SHD_PE_DEBUG_ENV, SHDPE_PATHS_FAST=0 still
  * turns every fast tier off.)  Takes the compute lock; NULL: SHD_PE_EINVAL. */
 int shd_pe_paths_set_row_tier(ShdPe* pe, int32_t enable);
+
+/* ---- link and vertex load from path packet counts (ABI 14) -------------
+ * The reference leaves two logs for post analysis: each source's paths hop by
+ * hop (topology.c:1831-1841) and, at teardown, every cached path with its
+ * packet counter (_topology_logAllCachedPaths, :1929-1967, path.c:59-71).
+ * shd_pe_path_load is their join, reduced on the device: how much weight
+ * crossed each arc and each vertex of the graph.
+ *
+ * Arcs are the merged non-loop OUT arcs in the caller's vertex ids, sorted by
+ * `from`, then by `to`: parallel edges are one arc (igraph_get_eid's edge, the
+ * newest, stands for the group), an undirected edge is two arcs, a self-loop
+ * is none.  shd_pe_num_arcs is their number (ShdPeStats::nArcs),
+ * shd_pe_arc_list writes both endpoint arrays (that many entries each),
+ * shd_pe_find_arc gives the index of the arc from -> to, -1 where there is
+ * none (ids out of range included), -2 for from == to.  None of the three does
+ * device work; NULL: 0 / SHD_PE_EINVAL / -1. */
+int64_t shd_pe_num_arcs(const ShdPe* pe);
+int shd_pe_arc_list(const ShdPe* pe, int32_t* from, int32_t* to);
+int64_t shd_pe_find_arc(const ShdPe* pe, int32_t from, int32_t to);
+/* Path i is exactly what shd_pe_get_paths(src[i], dst[i]) returns, with the
+ * same status code; w_i = weight[i], or 1 when weight == NULL.
+ *   vertexLoad[v] = sum of w_i over the requests with status 0 whose path
+ *                   contains v;
+ *   arcLoad[a]    = sum of w_i over the hops verts[k-1] -> verts[k] of those
+ *                   paths whose arc is a (the arc shd_pe_get_paths reads the
+ *                   hop's attributes from; the direction is the path's);
+ *   totals[0] requests with status 0, totals[1] sum of w_i * (vertices of path
+ *   i), totals[2] sum of w_i * (hops of path i), totals[3] requests with a
+ *   non-zero status.
+ * So src == dst is the path [src] and adds to vertexLoad[src] only, a complete
+ * graph's path is [src, dst], and a request with a non-zero status adds
+ * nothing and does not fail the call.  Every non-NULL array is overwritten,
+ * not added to; all sums are modulo 2^64.
+ *
+ * pe or out NULL, count < 0, or count > 0 with src or dst NULL: SHD_PE_EINVAL
+ * before anything is written.  Rows not yet computed are computed first.  The
+ * requests run through shd_pe_get_paths' chunks and tiers, ordered by the table
+ * position of their source (the sums do not depend on the order; a source's
+ * pass then runs once, not once per chunk it falls into), and a reduction
+ * kernel adds each chunk's staged paths into one accumulator per local shard
+ * (64-bit device-scope atomic adds behind a per-workgroup LDS table that sums
+ * what shares a place first); no path leaves the device.  (Under
+ * SHD_PE_DEBUG_ENV, SHDPE_LOAD_SORT=0 keeps the caller's order and
+ * SHDPE_LOAD_SLOTS sizes that table.)  A failed accumulator allocation is
+ * SHD_PE_ENOMEM.  Side effects are shd_pe_get_paths': no table byte,
+ * computed-row flag or ShdPeStats field changes, the transient SHD_PE_F_EXACT
+ * bit of the grouped emulation is the one thing a concurrent reader can see,
+ * and shd_pe_paths_info describes the call as it does a shd_pe_get_paths call.
+ * Takes the compute lock. */
+typedef struct ShdPeLoadOut {      /* any pointer may be NULL */
+    uint64_t* arcLoad;    /* shd_pe_num_arcs entries, arc order */
+    uint64_t* vertexLoad; /* nVertices entries */
+    int32_t*  status;     /* count entries: 0 or the SHD_PE_E* code shd_pe_get_paths gives request i */
+    uint64_t* totals;     /* 4 entries, see above */
+} ShdPeLoadOut;
+int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* dst,
+                     const uint64_t* weight, int64_t count, const ShdPeLoadOut* out);
+/* Of the last shd_pe_path_load call, the first min(n, 2) of: info[0] path
+ * entries reduced (vertices of all paths), info[1] global atomic adds the
+ * reduction issued (counted only under SHD_PE_DEBUG_COUNTERS, else 0). */
+int shd_pe_path_load_info(const ShdPe* pe, int64_t* info, int32_t n);
 
 /* Page-locked host memory for shd_pe_get_rows destinations (DMA target, no
  * staging copy).  No reference counterpart: Shadow's row buffers are plain
@@ -693,6 +757,22 @@ int shd_topology_fill(ShdTopology* top, double* msOut);
 /* The same through shd_pe_fill_rowstore_shards: a sharded in-process engine
  * needs no gather first.  info (optional) as there. */
 int shd_topology_fill_shards(ShdTopology* top, int64_t needBudgetBytes, ShdPeFillShardsInfo* info);
+/* ABI 14.  The teardown call: the load of every cached entry with
+ * packetCount > 0 (what _topology_logAllCachedPaths logs, joined with the
+ * paths), in the stored direction (s, d):
+ *  - s == d: the count is added to vertexLoad[s];
+ *  - a direct entry: to both end vertices and to the arc s -> d, on the host;
+ *  - every other entry is a request (s, d, packetCount) of one
+ *    shd_pe_path_load call; one that comes back with a status is skipped and
+ *    counted in totals[3] (as is a direct entry whose pair has no arc, which
+ *    the cache does not store today).
+ * totals[0..2] count the entries, weighted vertices and weighted hops of all
+ * three kinds; out->status is not written (the requests are the call's own).
+ * The cache stores an undirected pair once, so the packets of both directions
+ * are attributed along the stored direction's path: a link's total is the sum
+ * of its two arcs.  Not safe against concurrent inserts (shd_rowstore_foreach
+ * is not).  top or out NULL: SHD_PE_EINVAL. */
+int shd_topology_link_load(ShdTopology* top, const ShdPeLoadOut* out);
 
 /* ------------------------------------------------------------------------
  * GraphML ingestion (host only, no GPU work).  Replaces

@@ -575,6 +575,8 @@ namespace shdpe {
 //                  written straight to its final place; arrival at src checked
 //   k_paths_hops   per output entry: the hop's edge (igraph_get_eid: the
 //                  newest parallel edge) -> latency and 1 - packetloss
+//   k_paths_load   (shd_pe_path_load) per output entry: its request's weight
+//                  added to the entry's vertex and to the arc into it
 //
 // The walk is a chain of dependent 4-B loads (parent arc, then its tail), so
 // one thread serves one request and the parallelism is across requests; the
@@ -701,6 +703,19 @@ __global__ __launch_bounds__(256) void k_paths_walk(DevGraph g0, PathsWalkArgs p
     }
 }
 
+// The request whose path holds output entry e (0 <= e < off[count]): the last i
+// with off[i] <= e.  Empty paths share their successor's offset and are never
+// chosen.
+__device__ __forceinline__ int32_t entry_request(const int64_t* __restrict__ off, int32_t count, int64_t e) {
+    int32_t lo = 0, hi = count;
+    while (hi - lo > 1) {
+        const int32_t mid = lo + ((hi - lo) >> 1);
+        if (off[mid] <= e) lo = mid;
+        else hi = mid;
+    }
+    return lo;
+}
+
 __global__ __launch_bounds__(256) void k_paths_hops(DevGraph g0, const int64_t* __restrict__ off,
                                                     int32_t count, const int32_t* __restrict__ verts,
                                                     double* __restrict__ hopLat,
@@ -709,14 +724,7 @@ __global__ __launch_bounds__(256) void k_paths_hops(DevGraph g0, const int64_t* 
     const DevGraph g = global_view(g0);
     const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
     if (e >= off[count]) return;
-    // the request whose path holds entry e: the last i with off[i] <= e
-    // (empty paths share their successor's offset and are never chosen)
-    int32_t lo = 0, hi = count;
-    while (hi - lo > 1) {
-        const int32_t mid = lo + ((hi - lo) >> 1);
-        if (off[mid] <= e) lo = mid;
-        else hi = mid;
-    }
+    const int32_t lo = entry_request(off, count, e);
     double L = 0.0, R = 0.0;
     if (e > off[lo]) {
         const int u = verts[e - 1], v = verts[e];
@@ -730,6 +738,103 @@ __global__ __launch_bounds__(256) void k_paths_hops(DevGraph g0, const int64_t* 
     }
     if (hopLat) hopLat[e] = L;
     if (hopRel) hopRel[e] = R;
+}
+
+// shd_pe_path_load's reduction, in k_paths_hops' place: per output entry e the
+// weight of its request is added to the entry's vertex (acc[nArcs + v]) and,
+// past a path's first entry, to the arc verts[e-1] -> verts[e] (acc[arc], the
+// arc k_paths_hops reads its attributes from).  The sums are integers mod 2^64,
+// so their order does not matter.  load_entry finds both places; `add` adds.
+template <class Add>
+__device__ __forceinline__ void load_entry(const DevGraph& g, const int64_t* __restrict__ off, int32_t count,
+                                           const int32_t* __restrict__ verts,
+                                           const unsigned long long* __restrict__ weight, int64_t nArcs, int64_t e,
+                                           int32_t* __restrict__ nFailed, Add add) {
+    const int32_t lo = entry_request(off, count, e);
+    const unsigned long long w = weight[lo];
+    const int v = verts[e];
+    if (v < 0 || v >= g.n) {                     // (never a path's vertex: the walks write ids of the graph)
+        atomicAdd(nFailed, 1);
+        return;
+    }
+    if (w) add((unsigned long long)(nArcs + v), w);
+    if (e > off[lo]) {
+        const int u = verts[e - 1];
+        int a = -1;
+        if (u >= 0 && u < g.n && u != v && find_arc(g, u, v, &a)) {
+            if (w) add((unsigned long long)a, w);
+        } else {
+            atomicAdd(nFailed, 1);
+        }
+    }
+}
+
+// A workgroup takes LOAD_PER_THREAD * 256 consecutive entries (requests sorted
+// by source: a few sources' paths, which share the arcs next to them and the
+// hubs) and sums them in an LDS table of (place in acc, 64-bit sum) first --
+// LDS compare-and-swap on the key, LDS 64-bit add, LOAD_PROBES linear probes,
+// then a global no-return 64-bit device-scope add -- and issues one global add
+// per occupied slot at the end.  `slots` is a power of two <= LOAD_SLOTS_MAX.
+// nIssued (debug counters, else null): the global adds issued.
+constexpr int LOAD_SLOTS_MAX = 2048;             // 24 KiB of LDS
+constexpr int LOAD_PER_THREAD = 8;
+constexpr int LOAD_PROBES = 4;
+constexpr uint32_t LOAD_EMPTY = 0xFFFFFFFFu;     // (nArcs + n <= 2^32 - 2: both are int32 counts)
+
+__global__ __launch_bounds__(256) void k_paths_load(DevGraph g0, const int64_t* __restrict__ off,
+                                                    int32_t count, const int32_t* __restrict__ verts,
+                                                    const unsigned long long* __restrict__ weight,
+                                                    int64_t nArcs, unsigned long long* __restrict__ acc,
+                                                    int32_t* __restrict__ nFailed, int slots,
+                                                    unsigned long long* __restrict__ nIssued) {
+    __shared__ uint32_t keys[LOAD_SLOTS_MAX];
+    __shared__ unsigned long long sums[LOAD_SLOTS_MAX];
+    __shared__ unsigned int issuedWg;
+    const DevGraph g = global_view(g0);
+    const int tid = threadIdx.x;
+    for (int i = tid; i < slots; i += 256) {
+        keys[i] = LOAD_EMPTY;
+        sums[i] = 0;
+    }
+    if (tid == 0) issuedWg = 0;
+    __syncthreads();
+    const uint32_t mask = (uint32_t)slots - 1;
+    const int64_t total = off[count];
+    const int64_t base = (int64_t)blockIdx.x * (256 * LOAD_PER_THREAD);
+    unsigned issued = 0;
+    const auto add = [&](unsigned long long at, unsigned long long w) {
+        const uint32_t key = (uint32_t)at;
+        uint32_t h = ((key * 0x9E3779B1u) >> 11) & mask;
+        for (int p = 0; p < LOAD_PROBES; ++p) {
+            const uint32_t was = atomicCAS(&keys[h], LOAD_EMPTY, key);
+            if (was == LOAD_EMPTY || was == key) {
+                atomicAdd(&sums[h], w);
+                return;
+            }
+            h = (h + 1) & mask;
+        }
+        __hip_atomic_fetch_add(acc + at, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ++issued;
+    };
+    for (int it = 0; it < LOAD_PER_THREAD; ++it) {
+        const int64_t e = base + it * 256 + tid;
+        if (e >= total) break;                   // (the barrier below is outside the loop)
+        load_entry(g, off, count, verts, weight, nArcs, e, nFailed, add);
+    }
+    __syncthreads();
+    for (int i = tid; i < slots; i += 256) {
+        const uint32_t key = keys[i];
+        const unsigned long long sum = sums[i];
+        if (key != LOAD_EMPTY && sum) {
+            __hip_atomic_fetch_add(acc + key, sum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            ++issued;
+        }
+    }
+    if (nIssued) {                               // (uniform)
+        if (issued) atomicAdd(&issuedWg, issued);
+        __syncthreads();
+        if (tid == 0 && issuedWg) atomicAdd(nIssued, (unsigned long long)issuedWg);
+    }
 }
 
 void launch_paths_size(const DevGraph& gAux, const DevTable& tab, const PathsSizeArgs& a, void* stream) {
@@ -763,6 +868,17 @@ void launch_paths_hops(const DevGraph& gAux, const int64_t* dOff, int32_t count,
     hipLaunchKernelGGL(k_paths_hops, dim3((unsigned)((entries + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), gAux, dOff, count, dVerts, dHopLat, dHopRel,
                        dNFailed);
+}
+
+void launch_paths_load(const DevGraph& gAux, const PathsLoadArgs& a, void* stream) {
+    if (a.entries <= 0) return;
+    const hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    int slots = 8;                               // the largest power of two <= min(a.slots, LOAD_SLOTS_MAX)
+    while (slots * 2 <= a.slots && slots * 2 <= LOAD_SLOTS_MAX) slots *= 2;
+    const int64_t per = 256 * LOAD_PER_THREAD;
+    hipLaunchKernelGGL(k_paths_load, dim3((unsigned)((a.entries + per - 1) / per)), dim3(256), 0, st, gAux, a.off,
+                       a.count, a.verts, (const unsigned long long*)a.weight, a.nArcs, (unsigned long long*)a.acc,
+                       a.nFailed, slots, (unsigned long long*)a.nIssued);
 }
 
 }  // namespace shdpe

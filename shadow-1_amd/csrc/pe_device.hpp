@@ -159,6 +159,8 @@ struct Tuning {
     int pathsGroup = 0;        // shd_pe_get_paths: sources per emulation group (0: exactGrid)
     int pathsChunk = 0;        // ... requests per staging chunk (0: 65,536)
     int pathsFast = 1;         // ... 0: no batch / tie / row tier, every source by the grouped emulation
+    int loadSort = 1;          // shd_pe_path_load: 0 keeps the caller's request order (no sort by source)
+    int loadSlots = 2048;      // ... the reduction's LDS table size (rounded down to a power of two in [8, 2048])
     int predFilter = 1;        // on-demand predecessor pass reads only the in-arcs the relax
                                // flagged (0: every in-arc, BatchScratch::arcHit stays null)
     int postSplit = -1;        // split kernels: the post kernel as two (predecessor part,
@@ -476,6 +478,22 @@ void launch_paths_walk(const DevGraph& g, const PathsWalkArgs& a, void* stream);
 void launch_paths_hops(const DevGraph& gAux, const int64_t* dOff, int32_t count, int64_t entries,
                        const int32_t* dVerts, double* dHopLat, double* dHopRel, int32_t* dNFailed,
                        void* stream);
+// shd_pe_path_load's reduction over the same staging: per output entry the weight
+// of its request added to acc[nArcs + vertex] and, past a path's first entry, to
+// acc[arc into it]
+struct PathsLoadArgs {
+    const int64_t* off;      // [count + 1]
+    int32_t count;
+    int64_t entries;         // off[count]
+    const int32_t* verts;    // [entries] caller's ids
+    const uint64_t* weight;  // [count]
+    int64_t nArcs;
+    uint64_t* acc;           // [nArcs + n] sums mod 2^64
+    int32_t* nFailed;        // an entry that is no vertex, a hop without an arc
+    int32_t slots;           // size of the workgroup's LDS table (rounded down to a power of two in [8, 2048])
+    uint64_t* nIssued;       // debug counters (else null): global atomic adds issued
+};
+void launch_paths_load(const DevGraph& gAux, const PathsLoadArgs& a, void* stream);
 // dense path (pe_dense.hip)
 // launch_dense_rows' stages: everything (sweeps, predecessor pass, row writer),
 // or the sweeps to convergence alone, which leave the distance rows in D and

@@ -98,6 +98,8 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_PATHS_GROUP", t.pathsGroup);
     gi("SHDPE_PATHS_CHUNK", t.pathsChunk);
     gi("SHDPE_PATHS_FAST", t.pathsFast);
+    gi("SHDPE_LOAD_SORT", t.loadSort);
+    gi("SHDPE_LOAD_SLOTS", t.loadSlots);
 }
 
 extern "C" void shd_pe_default_options(ShdPeOptions* opt) {
@@ -1964,6 +1966,8 @@ struct PathsStage {
     PathReq *reqs = nullptr, *reqsB = nullptr;      // requests of the emulation tier / of the batch tier
     uint8_t *failed = nullptr, *flags = nullptr;
     double *hopLat = nullptr, *hopRel = nullptr;
+    uint64_t *weight = nullptr, *acc = nullptr;     // shd_pe_path_load: the chunk's weights; nArcs + n sums
+    uint64_t* issued = nullptr;                     // ... debug counters: global atomic adds issued
     int64_t entries = 0;             // capacity of verts / hopLat / hopRel
     std::vector<int32_t> hLen, hStat;
     std::vector<PathReq> hTrivial, hWalk;   // `reqs` on the host: [trivial | emulation], until the copy-out
@@ -1989,6 +1993,8 @@ struct PathsCall {
     int32_t group;                   // sources per emulation group (<= every shard's exactGrid)
     int64_t entries;                 // output entries per chunk
     bool hops;
+    const uint64_t* weight = nullptr;    // shd_pe_path_load (out == nullptr): one per request; the chunks'
+                                         // paths are reduced into PathsStage::acc, none is copied out
     std::vector<PathsStage> st;      // per local shard
     int64_t c0 = 0;                  // the chunk at hand: requests [c0, c0 + cnt)
     int32_t cnt = 0;
@@ -2076,6 +2082,15 @@ static int paths_stage_extract(ShdPe* pe, PathsCall& c, size_t k) {
         (rc = s.get(&s.flags, (size_t)std::min(c.group, sh->rowCount) * pe->attached.size())))
         return rc;
     if (c.hops && ((rc = s.get(&s.hopLat, E)) || (rc = s.get(&s.hopRel, E)))) return rc;
+    if (c.weight) {
+        const size_t nAcc = (size_t)pe->hg.nArcs() + (size_t)pe->hg.n;
+        if ((rc = s.get(&s.weight, C)) || (rc = s.get(&s.acc, nAcc))) return rc;
+        HIPCHK(hipMemsetAsync(s.acc, 0, nAcc * 8, sh->stream));
+        if (pe->tu.debug) {
+            if ((rc = s.get(&s.issued, 1))) return rc;
+            HIPCHK(hipMemsetAsync(s.issued, 0, 8, sh->stream));
+        }
+    }
     s.entries = (int64_t)E;
     return SHD_PE_OK;
 }
@@ -2465,10 +2480,29 @@ static int paths_hops_and_copy_out(ShdPe* pe, PathsCall& c, size_t k, int64_t to
     return SHD_PE_OK;
 }
 
+// shd_pe_path_load, where paths_hops_and_copy_out stands: the chunk's staged
+// paths reduced into the shard's accumulator; only the failure words come back.
+static int paths_load_chunk(ShdPe* pe, PathsCall& c, size_t k, int64_t total) {
+    Shard* sh = pe->shards[k].get();
+    PathsStage& s = c.st[k];
+    HIPCHK(hipMemcpyAsync(s.weight, c.weight + c.c0, (size_t)c.cnt * 8, hipMemcpyHostToDevice, sh->stream));
+    launch_paths_load(sh->dgAux, PathsLoadArgs{s.off, c.cnt, total, s.verts, s.weight, pe->hg.nArcs(), s.acc,
+                                               s.nFailed + 1, pe->tu.loadSlots, s.issued}, sh->stream);
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipEventRecord(sh->ev1, sh->stream));
+    int32_t nFailed[2] = {0, 0};
+    HIPCHK(hipMemcpyAsync(nFailed, s.nFailed, 8, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    c.ms += elapsed(sh->ev0, sh->ev1);
+    if (nFailed[0] || nFailed[1]) return SHD_PE_EHIP;    // as in paths_hops_and_copy_out
+    return SHD_PE_OK;
+}
+
 // Paths of the chunk's requests that shard k answers (paths_size_chunk ran):
-// the tiers in sequence, then the hop attributes and the copy-out.  Each tier
-// serves what it can of the work set, counts the sources it served in full
-// into pathsInfo, and leaves in the set exactly what it hands on.
+// the tiers in sequence, then the hop attributes and the copy-out (or, for
+// shd_pe_path_load, the reduction).  Each tier serves what it can of the work
+// set, counts the sources it served in full into pathsInfo, and leaves in the
+// set exactly what it hands on.
 static int paths_extract_chunk(ShdPe* pe, PathsCall& c, size_t k) {
     Shard* sh = pe->shards[k].get();
     PathsStage& s = c.st[k];
@@ -2488,7 +2522,76 @@ static int paths_extract_chunk(ShdPe* pe, PathsCall& c, size_t k) {
         (rc = paths_tier_tie(pe, c, k, w, tie)) || (rc = paths_tier_rows(pe, c, k, w)) ||
         (rc = paths_tier_emulation(pe, c, k, w)))
         return rc;
-    return paths_hops_and_copy_out(pe, c, k, total);
+    return c.weight ? paths_load_chunk(pe, c, k, total) : paths_hops_and_copy_out(pe, c, k, total);
+}
+
+// The rows the lengths of these requests are read from, computed first where missing.
+static int paths_ensure_rows(ShdPe* pe, const int32_t* src, const int32_t* dst, int64_t count) {
+    if (pe->mode == 2) return SHD_PE_OK;
+    const HostGraph& g = pe->hg;
+    std::vector<int32_t> todo;
+    std::vector<uint8_t> seen(pe->attached.size(), 0);
+    for (int64_t i = 0; i < count; ++i) {
+        const int32_t s = src[i], t = dst[i];
+        if (s < 0 || s >= g.n || t < 0 || t >= g.n || s == t) continue;
+        const int32_t ps = pe->posOf[s];
+        if (ps < pe->ownStart || ps >= pe->ownEnd || pe->posOf[t] < 0 || seen[(size_t)ps]) continue;
+        seen[(size_t)ps] = 1;
+        if (!row_done(pe, ps)) todo.push_back(ps);
+    }
+    return compute_positions_locked(pe, todo.data(), (int32_t)todo.size());
+}
+
+// The bounds of a call's chunks and groups, and its per-shard staging.
+static void paths_call_init(const ShdPe* pe, PathsCall& c, int64_t count) {
+    c.chunk = (int32_t)std::min<int64_t>(count, pe->tu.pathsChunk > 0 ? pe->tu.pathsChunk : PATHS_CHUNK);
+    c.group = INT32_MAX;
+    for (auto& sh : pe->shards) c.group = std::min(c.group, sh->exactGrid);
+    // (a chunk's unique sources of a shard fit its dBatchRows / dBatchAmb: they
+    // are rows of the shard, so at most min(chunk, rowCount) <= rowsCap)
+    c.chunk = std::min(c.chunk, 1 << 20);
+    if (pe->tu.pathsGroup > 0) c.group = std::min(c.group, pe->tu.pathsGroup);
+    c.entries = std::max<int64_t>(PATHS_ENTRIES, (int64_t)pe->hg.n + 1);
+    c.st.resize(pe->shards.size());
+}
+
+// Pass 1, sizing: every request's length and status -> offsets (count + 1) and,
+// where given, status.
+static int paths_size_all(ShdPe* pe, PathsCall& c, int64_t count, int64_t* offsets, int32_t* status) {
+    int64_t total = 0;
+    offsets[0] = 0;
+    for (int64_t c0 = 0; c0 < count; c0 += c.chunk) {
+        const int32_t cnt = (int32_t)std::min<int64_t>(c.chunk, count - c0);
+        for (size_t k = 0; k < pe->shards.size(); ++k) {
+            const int rc = paths_size_chunk(pe, c, k, c0, cnt);
+            if (rc) return rc;
+        }
+        for (int32_t i = 0; i < cnt; ++i) {
+            int32_t L = 0, st = SHD_PE_ENOTOWNED;
+            for (const PathsStage& s : c.st)
+                if (s.hStat[(size_t)i] != PATHS_NOT_MINE) { L = s.hLen[(size_t)i]; st = s.hStat[(size_t)i]; }
+            if (status) status[c0 + i] = st;
+            total += L;
+            offsets[c0 + i + 1] = total;
+        }
+    }
+    return SHD_PE_OK;
+}
+
+// Pass 2, extraction: chunks bounded in requests and in output entries.
+static int paths_extract_all(ShdPe* pe, PathsCall& c, int64_t count, const int64_t* offsets) {
+    for (int64_t c0 = 0; c0 < count;) {
+        int64_t c1 = c0 + 1;
+        while (c1 < count && c1 - c0 < c.chunk && offsets[c1 + 1] - offsets[c0] <= c.entries) ++c1;
+        c.c0 = c0;
+        c.cnt = (int32_t)(c1 - c0);
+        for (size_t k = 0; k < pe->shards.size(); ++k) {
+            int rc;
+            if ((rc = paths_size_chunk(pe, c, k, c0, c.cnt)) || (rc = paths_extract_chunk(pe, c, k))) return rc;
+        }
+        c0 = c1;
+    }
+    return SHD_PE_OK;
 }
 
 extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* dst, int64_t count,
@@ -2500,70 +2603,145 @@ extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* ds
     for (int64_t& x : pe->pathsInfo) x = 0;
     out->offsets[0] = 0;
     if (count == 0) return SHD_PE_OK;
-    const HostGraph& g = pe->hg;
-    const int32_t T = (int32_t)pe->attached.size();
     int rc;
-    // rows the lengths are read from, computed first where missing
-    if (pe->mode != 2) {
-        std::vector<int32_t> todo;
-        std::vector<uint8_t> seen((size_t)T, 0);
-        for (int64_t i = 0; i < count; ++i) {
-            const int32_t s = src[i], t = dst[i];
-            if (s < 0 || s >= g.n || t < 0 || t >= g.n || s == t) continue;
-            const int32_t ps = pe->posOf[s];
-            if (ps < pe->ownStart || ps >= pe->ownEnd || pe->posOf[t] < 0 || seen[(size_t)ps]) continue;
-            seen[(size_t)ps] = 1;
-            if (!row_done(pe, ps)) todo.push_back(ps);
-        }
-        if ((rc = compute_positions_locked(pe, todo.data(), (int32_t)todo.size()))) return rc;
-    }
+    if ((rc = paths_ensure_rows(pe, src, dst, count))) return rc;
     PathsCall c;
     c.src = src;
     c.dst = dst;
     c.out = out;
-    c.chunk = (int32_t)std::min<int64_t>(count, pe->tu.pathsChunk > 0 ? pe->tu.pathsChunk : PATHS_CHUNK);
-    c.group = INT32_MAX;
-    for (auto& sh : pe->shards) c.group = std::min(c.group, sh->exactGrid);
-    // (a chunk's unique sources of a shard fit its dBatchRows / dBatchAmb: they
-    // are rows of the shard, so at most min(chunk, rowCount) <= rowsCap)
-    c.chunk = std::min(c.chunk, 1 << 20);
-    if (pe->tu.pathsGroup > 0) c.group = std::min(c.group, pe->tu.pathsGroup);
-    c.entries = std::max<int64_t>(PATHS_ENTRIES, (int64_t)g.n + 1);
     c.hops = out->hopLat || out->hopRel;
-    c.st.resize(pe->shards.size());
+    paths_call_init(pe, c, count);
     auto finish = [&](int r) {
         pe->pathsInfo[5] = (int64_t)std::llround(c.ms * 1000.0);
         return r;
     };
-    // pass 1, sizing: every request's length and status -> offsets
-    int64_t total = 0;
-    for (int64_t c0 = 0; c0 < count; c0 += c.chunk) {
-        const int32_t cnt = (int32_t)std::min<int64_t>(c.chunk, count - c0);
-        for (size_t k = 0; k < pe->shards.size(); ++k)
-            if ((rc = paths_size_chunk(pe, c, k, c0, cnt))) return finish(rc);
-        for (int32_t i = 0; i < cnt; ++i) {
-            int32_t L = 0, st = SHD_PE_ENOTOWNED;
-            for (const PathsStage& s : c.st)
-                if (s.hStat[(size_t)i] != PATHS_NOT_MINE) { L = s.hLen[(size_t)i]; st = s.hStat[(size_t)i]; }
-            if (out->status) out->status[c0 + i] = st;
-            total += L;
-            out->offsets[c0 + i + 1] = total;
+    if ((rc = paths_size_all(pe, c, count, out->offsets, out->status))) return finish(rc);
+    if (!out->verts) return finish(SHD_PE_OK);
+    if (out->offsets[count] > out->cap) return finish(SHD_PE_EINVAL);
+    return finish(paths_extract_all(pe, c, count, out->offsets));
+}
+
+// shd_pe_get_paths' pipeline up to the end of the tiers, with the requests
+// ordered by the table position of their source (SHDPE_LOAD_SORT=0: as given)
+// and a reduction in the copy-out's place.
+extern "C" int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* dst, const uint64_t* weight,
+                                int64_t count, const ShdPeLoadOut* out) {
+    if (!pe || !out || count < 0 || (count > 0 && (!src || !dst))) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(pe->mu);
+    for (int64_t& x : pe->pathsInfo) x = 0;
+    pe->loadInfo[0] = pe->loadInfo[1] = 0;
+    const HostGraph& g = pe->hg;
+    const size_t nArcs = (size_t)g.nArcs(), nAcc = nArcs + (size_t)g.n;
+    uint64_t tot[4] = {0, 0, 0, 0};
+    std::vector<uint64_t> sum, part, w;                  // the sums; one shard's; the weights in run order
+    std::vector<int64_t> order, offsets;
+    std::vector<int32_t> ssrc, sdst, stat;
+    try {                                                // (every host array of the call: 44 B per request)
+        sum.assign(nAcc, 0);
+        part.resize(count > 0 ? nAcc : 0);
+        w.resize((size_t)count);
+        order.resize((size_t)count);
+        offsets.assign((size_t)count + 1, 0);
+        ssrc.resize((size_t)count);
+        sdst.resize((size_t)count);
+        stat.resize((size_t)count);
+    } catch (const std::bad_alloc&) {
+        return SHD_PE_ENOMEM;
+    }
+    auto write_out = [&]() {
+        if (out->arcLoad) std::memcpy(out->arcLoad, sum.data(), nArcs * 8);
+        if (out->vertexLoad) std::memcpy(out->vertexLoad, sum.data() + nArcs, (size_t)g.n * 8);
+        if (out->totals) std::memcpy(out->totals, tot, 32);
+    };
+    if (count == 0) {
+        write_out();
+        return SHD_PE_OK;
+    }
+    // a source's pass runs once where its requests share a chunk: by table position, the
+    // requests without one (bad ids, unattached) last
+    const auto key = [&](int64_t i) {
+        const int32_t sv = src[i];
+        const int32_t p = sv >= 0 && sv < g.n ? pe->posOf[sv] : -1;
+        return p < 0 ? INT32_MAX : p;
+    };
+    for (int64_t i = 0; i < count; ++i) order[(size_t)i] = i;
+    if (pe->tu.loadSort)
+        std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return key(a) < key(b); });
+    for (int64_t i = 0; i < count; ++i) {
+        const int64_t j = order[(size_t)i];
+        ssrc[(size_t)i] = src[j];
+        sdst[(size_t)i] = dst[j];
+        w[(size_t)i] = weight ? weight[j] : 1;
+    }
+    int rc;
+    if ((rc = paths_ensure_rows(pe, ssrc.data(), sdst.data(), count))) return rc;
+    PathsCall c;
+    c.src = ssrc.data();
+    c.dst = sdst.data();
+    c.out = nullptr;
+    c.hops = false;
+    c.weight = w.data();
+    paths_call_init(pe, c, count);
+    auto finish = [&](int r) {
+        pe->pathsInfo[5] = (int64_t)std::llround(c.ms * 1000.0);
+        return r;
+    };
+    if ((rc = paths_size_all(pe, c, count, offsets.data(), stat.data())) ||
+        (rc = paths_extract_all(pe, c, count, offsets.data())))
+        return finish(rc);
+    // the shards' accumulators, summed (integers: in any order)
+    for (size_t k = 0; k < pe->shards.size(); ++k) {
+        if (!c.st[k].acc) continue;                      // (no request of this shard had a path)
+        Shard* sh = pe->shards[k].get();
+        HIPCHK(hipSetDevice(sh->device));
+        HIPCHK(hipMemcpyAsync(part.data(), c.st[k].acc, nAcc * 8, hipMemcpyDeviceToHost, sh->stream));
+        HIPCHK(hipStreamSynchronize(sh->stream));
+        for (size_t i = 0; i < nAcc; ++i) sum[i] += part[i];
+        if (c.st[k].issued) {
+            uint64_t issued = 0;
+            HIPCHK(hipMemcpy(&issued, c.st[k].issued, 8, hipMemcpyDeviceToHost));
+            pe->loadInfo[1] += (int64_t)issued;
         }
     }
-    if (!out->verts) return finish(SHD_PE_OK);
-    if (total > out->cap) return finish(SHD_PE_EINVAL);
-    // pass 2, extraction: chunks bounded in requests and in output entries
-    for (int64_t c0 = 0; c0 < count;) {
-        int64_t c1 = c0 + 1;
-        while (c1 < count && c1 - c0 < c.chunk && out->offsets[c1 + 1] - out->offsets[c0] <= c.entries) ++c1;
-        c.c0 = c0;
-        c.cnt = (int32_t)(c1 - c0);
-        for (size_t k = 0; k < pe->shards.size(); ++k)
-            if ((rc = paths_size_chunk(pe, c, k, c0, c.cnt)) || (rc = paths_extract_chunk(pe, c, k)))
-                return finish(rc);
-        c0 = c1;
+    pe->loadInfo[0] = offsets[(size_t)count];
+    for (int64_t i = 0; i < count; ++i) {
+        const uint64_t L = (uint64_t)(offsets[(size_t)i + 1] - offsets[(size_t)i]);
+        if (out->status) out->status[order[(size_t)i]] = stat[(size_t)i];
+        if (stat[(size_t)i] != SHD_PE_OK) {
+            tot[3] += 1;
+            continue;
+        }
+        tot[0] += 1;
+        tot[1] += w[(size_t)i] * L;
+        tot[2] += w[(size_t)i] * (L - 1);
     }
+    write_out();
     return finish(SHD_PE_OK);
+}
+
+extern "C" int shd_pe_path_load_info(const ShdPe* pe, int64_t* info, int32_t n) {
+    if (!pe || !info || n < 0) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
+    for (int32_t k = 0; k < std::min<int32_t>(n, 2); ++k) info[k] = pe->loadInfo[k];
+    return SHD_PE_OK;
+}
+
+extern "C" int64_t shd_pe_num_arcs(const ShdPe* pe) { return pe ? pe->hg.nArcs() : 0; }
+
+extern "C" int shd_pe_arc_list(const ShdPe* pe, int32_t* from, int32_t* to) {
+    if (!pe || !from || !to) return SHD_PE_EINVAL;
+    const HostGraph& g = pe->hg;
+    for (int32_t u = 0; u < g.n; ++u)
+        for (int32_t a = g.rowPtr[(size_t)u]; a < g.rowPtr[(size_t)u + 1]; ++a) {
+            from[a] = u;
+            to[a] = g.col[(size_t)a];
+        }
+    return SHD_PE_OK;
+}
+
+extern "C" int64_t shd_pe_find_arc(const ShdPe* pe, int32_t from, int32_t to) {
+    if (!pe || from < 0 || from >= pe->hg.n || to < 0 || to >= pe->hg.n) return -1;
+    return pe->hg.findArc(from, to);
 }
 
 extern "C" int shd_pe_paths_info(const ShdPe* pe, int64_t* info, int32_t n) {

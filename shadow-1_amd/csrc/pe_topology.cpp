@@ -218,6 +218,62 @@ extern "C" int shd_topology_fill_shards(ShdTopology* t, int64_t needBudgetBytes,
     return SHD_PE_OK;
 }
 
+// The teardown join of _topology_logAllCachedPaths (:1929-1967) with the paths
+// of :1831-1841: self and direct entries are added here, every other entry is
+// one request of a single shd_pe_path_load call.
+static int link_load_locked(ShdTopology* t, const ShdPeLoadOut* out) {
+    struct Entry { int32_t s, d, direct; uint64_t n; };
+    std::vector<Entry> entries;
+    shd_rowstore_foreach(t->store, [](int32_t s, int32_t d, double, double, int32_t isDirect, uint64_t n, void* user) {
+        if (n > 0) static_cast<std::vector<Entry>*>(user)->push_back(Entry{s, d, isDirect, n});
+    }, &entries);
+    const shdpe::HostGraph* g = t->g;
+    const size_t nArcs = (size_t)g->nArcs();
+    std::vector<uint64_t> arc(nArcs), vert((size_t)g->n), tot(4, 0), w;
+    std::vector<int32_t> src, dst;
+    for (const Entry& e : entries)
+        if (e.s != e.d && !e.direct) {
+            src.push_back(e.s);
+            dst.push_back(e.d);
+            w.push_back(e.n);
+        }
+    const ShdPeLoadOut mine{arc.data(), vert.data(), nullptr, tot.data()};
+    const int rc = shd_pe_path_load(t->pe, src.data(), dst.data(), w.data(), (int64_t)src.size(), &mine);
+    if (rc) return rc;
+    for (const Entry& e : entries) {
+        if (e.s != e.d && !e.direct) continue;
+        // (a direct entry is stored for an edge only; one without an arc adds
+        // nothing and is counted as refused, so totals[2] stays the arcs' sum)
+        const int64_t a = e.s == e.d ? -2 : g->findArc(e.s, e.d);
+        if (e.s != e.d && a < 0) {
+            tot[3] += 1;
+            continue;
+        }
+        vert[(size_t)e.s] += e.n;
+        tot[0] += 1;
+        tot[1] += e.n;
+        if (e.s == e.d) continue;
+        vert[(size_t)e.d] += e.n;
+        tot[1] += e.n;
+        tot[2] += e.n;
+        arc[(size_t)a] += e.n;
+    }
+    if (out->arcLoad) std::memcpy(out->arcLoad, arc.data(), nArcs * 8);
+    if (out->vertexLoad) std::memcpy(out->vertexLoad, vert.data(), (size_t)g->n * 8);
+    if (out->totals) std::memcpy(out->totals, tot.data(), 32);
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_topology_link_load(ShdTopology* t, const ShdPeLoadOut* out) {
+    if (!t || !out) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(t->mu);
+    try {
+        return link_load_locked(t, out);
+    } catch (const std::bad_alloc&) {                    // (the entry list, the request arrays, the sums)
+        return SHD_PE_ENOMEM;
+    }
+}
+
 extern "C" int64_t shd_topology_rows_computed(const ShdTopology* t) {
     return t ? t->rowsComputed.load(std::memory_order_relaxed) : 0;
 }

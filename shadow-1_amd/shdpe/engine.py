@@ -56,6 +56,8 @@ EXPORTS = [
     "shd_pe_graph_props", "shd_pe_graph_props_host",
     "shd_pe_create_built", "shd_pe_graph_digest",
     "shd_pe_paths_set_row_tier",
+    "shd_pe_num_arcs", "shd_pe_arc_list", "shd_pe_find_arc", "shd_pe_path_load",
+    "shd_pe_path_load_info", "shd_topology_link_load",
 ]
 VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
 VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
@@ -125,6 +127,12 @@ class PathsOutC(C.Structure):
     """ShdPePathsOut"""
     _fields_ = [("offsets", C.c_void_p), ("verts", C.c_void_p), ("hopLat", C.c_void_p),
                 ("hopRel", C.c_void_p), ("status", C.c_void_p), ("cap", C.c_int64)]
+
+
+class LoadOutC(C.Structure):
+    """ShdPeLoadOut"""
+    _fields_ = [("arcLoad", C.c_void_p), ("vertexLoad", C.c_void_p), ("status", C.c_void_p),
+                ("totals", C.c_void_p)]
 
 
 class GraphPropsC(C.Structure):
@@ -258,6 +266,12 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_post_split_info": (C.c_int, [vp, vp, vp, vp]),
         "shd_pe_batch_info": (C.c_int, [vp, i32, vp]),
         "shd_pe_paths_set_row_tier": (C.c_int, [vp, i32]),
+        "shd_pe_num_arcs": (i64, [vp]),
+        "shd_pe_arc_list": (C.c_int, [vp, vp, vp]),
+        "shd_pe_find_arc": (i64, [vp, i32, i32]),
+        "shd_pe_path_load": (C.c_int, [vp, vp, vp, vp, i64, vp]),
+        "shd_topology_link_load": (C.c_int, [vp, vp]),
+        "shd_pe_path_load_info": (C.c_int, [vp, vp, i32]),
     }
     # ABI-3 ... ABI-8 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
@@ -270,7 +284,9 @@ def load_library(path: str = LIB_PATH):
                 "shd_pe_graph_props_host", "shd_pe_fill_rowstore_shards",
                 "shd_topology_fill_shards", "shd_pe_create_built",
                 "shd_pe_graph_digest", "shd_pe_post_split_info",
-                "shd_pe_batch_info", "shd_pe_paths_set_row_tier"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_pe_batch_info", "shd_pe_paths_set_row_tier", "shd_pe_num_arcs",
+                "shd_pe_arc_list", "shd_pe_find_arc", "shd_pe_path_load",
+                "shd_pe_path_load_info", "shd_topology_link_load"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -365,6 +381,47 @@ def strerror(code: int) -> str:
 
 def _p(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def _load_out(n_arcs: int, n: int, count: int) -> dict:
+    return {"arc": np.zeros(n_arcs, np.uint64), "vertex": np.zeros(n, np.uint64),
+            "status": np.zeros(count, np.int32), "totals": np.zeros(4, np.uint64)}
+
+
+def edge_load(top, arc_from, arc_to, arc_load) -> np.ndarray:
+    """The arc loads of path_load / link_load per EDGE of the topology
+    (uint64[top.m], pure numpy).  The newest edge of each parallel group (by
+    ordered endpoints when directed, unordered when undirected) takes the
+    group's load -- it is the edge igraph_get_eid returns, the one the paths
+    are made of; an undirected edge takes the sum of both its arcs.  Older
+    parallel edges and self-loops get 0."""
+    n = np.uint64(top.n)
+    arc_from = np.asarray(arc_from).astype(np.uint64)
+    arc_to = np.asarray(arc_to).astype(np.uint64)
+    arc_load = np.asarray(arc_load, dtype=np.uint64)
+    a, b = np.asarray(top.src).astype(np.uint64), np.asarray(top.dst).astype(np.uint64)
+    out = np.zeros(a.shape[0], np.uint64)
+    if a.shape[0] == 0:
+        return out
+    if not top.directed:
+        a, b = np.minimum(a, b), np.maximum(a, b)
+    key = a * n + b
+    # the newest edge of a group: the last one in edge order
+    rev_first = np.unique(key[::-1], return_index=True)[1]
+    newest = key.shape[0] - 1 - rev_first
+    newest = newest[a[newest] != b[newest]]
+    arc_key = arc_from * n + arc_to              # sorted: the arc order
+
+    def load_of(k):
+        if arc_key.shape[0] == 0:
+            return np.zeros(k.shape, np.uint64)
+        at = np.minimum(np.searchsorted(arc_key, k), arc_key.shape[0] - 1)
+        return np.where(arc_key[at] == k, arc_load[at], np.uint64(0))
+
+    out[newest] = load_of(key[newest])
+    if not top.directed:
+        out[newest] += load_of(b[newest] * n + a[newest])
+    return out
 
 
 class Engine:
@@ -614,6 +671,44 @@ class Engine:
         """shd_pe_paths_set_row_tier: let get_paths serve the per-row sparse and the
         dense min-plus mode from one pass of their own relax stage (off by default)."""
         self._chk(self._lib.shd_pe_paths_set_row_tier(self.h, 1 if on else 0), "shd_pe_paths_set_row_tier")
+
+    def arcs(self):
+        """shd_pe_arc_list: (from, to) of the merged non-loop OUT arcs in the
+        caller's vertex ids, sorted by from, then to -- the order of path_load's
+        arc array."""
+        n = int(self._lib.shd_pe_num_arcs(self.h))
+        a, b = np.empty(n, np.int32), np.empty(n, np.int32)
+        self._chk(self._lib.shd_pe_arc_list(self.h, _p(a), _p(b)), "shd_pe_arc_list")
+        return a, b
+
+    def find_arc(self, s: int, t: int) -> int:
+        """shd_pe_find_arc: the arc index of s -> t, -1 for none, -2 for s == t."""
+        return int(self._lib.shd_pe_find_arc(self.h, int(s), int(t)))
+
+    def path_load(self, src, dst, weight=None) -> dict:
+        """shd_pe_path_load: the weight (None: 1 each) of every request summed
+        over the arcs and vertices of its path, on the device -> dict(arc, vertex
+        (uint64, mod 2**64), status (int32 per request), totals (uint64[4]:
+        requests served, weighted vertices, weighted hops, requests refused))."""
+        s = np.ascontiguousarray(src, dtype=np.int32)
+        d = np.ascontiguousarray(dst, dtype=np.int32)
+        if s.ndim != 1 or s.shape != d.shape:
+            raise ValueError("src/dst must be 1-D arrays of one length")
+        w = None if weight is None else np.ascontiguousarray(weight, dtype=np.uint64)
+        if w is not None and w.shape != s.shape:
+            raise ValueError("weight must have one entry per request")
+        out = _load_out(int(self._lib.shd_pe_num_arcs(self.h)), self.top.n, s.shape[0])
+        o = LoadOutC(_p(out["arc"]), _p(out["vertex"]), _p(out["status"]), _p(out["totals"]))
+        self._chk(self._lib.shd_pe_path_load(self.h, _p(s), _p(d), _p(w), s.shape[0], C.byref(o)),
+                  "shd_pe_path_load")
+        return out
+
+    def path_load_info(self) -> dict:
+        """shd_pe_path_load_info of the last path_load: path entries reduced and
+        (debug counters only, else 0) global atomic adds issued."""
+        info = np.zeros(2, np.int64)
+        self._chk(self._lib.shd_pe_path_load_info(self.h, _p(info), 2), "shd_pe_path_load_info")
+        return {"entries": int(info[0]), "atomics": int(info[1])}
 
     def tune(self):
         """shd_pe_tune: time both k_batch_rows variants on this engine's rows,
@@ -894,6 +989,19 @@ class TopologyShim:
         if rc:
             raise EngineError(rc, "shd_topology_fill_shards")
         return info.as_dict()
+
+    def link_load(self) -> dict:
+        """shd_topology_link_load: the packet counters of every cached path summed
+        over its arcs and vertices (stored direction) -> dict(arc, vertex,
+        totals) as Engine.path_load gives them."""
+        eng = self.engine
+        out = _load_out(int(self._lib.shd_pe_num_arcs(eng.h)), eng.top.n, 0)
+        del out["status"]
+        o = LoadOutC(_p(out["arc"]), _p(out["vertex"]), None, _p(out["totals"]))
+        rc = self._lib.shd_topology_link_load(self.h, C.byref(o))
+        if rc:
+            raise EngineError(rc, "shd_topology_link_load")
+        return out
 
     def increment(self, s, d):
         return self._lib.shd_topology_increment_path_packet_counter(self.h, int(s), int(d))
