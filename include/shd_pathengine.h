@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 14  /* 7: graph property check (shd_pe_graph_props);
+#define SHD_PE_ABI_VERSION 15  /* 7: graph property check (shd_pe_graph_props);
                                   8: fill from row shards (shd_pe_fill_rowstore_shards);
                                   9: shd_pe_pred_filter_counts;
                                   10: shd_pe_create_built (graph build on the device),
@@ -46,7 +46,8 @@ extern "C" {
                                   13: shd_pe_paths_set_row_tier, shd_pe_paths_info's
                                       info[6];
                                   14: shd_pe_path_load, shd_pe_path_load_info, shd_pe_num_arcs,
-                                      shd_pe_arc_list, shd_pe_find_arc, shd_topology_link_load */
+                                      shd_pe_arc_list, shd_pe_find_arc, shd_topology_link_load;
+                                  15: shd_pe_sparse_info */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -613,6 +614,19 @@ int shd_pe_post_split_info(const ShdPe* pe, int32_t* split, int32_t* labelWaves,
  * A diagnostic of this engine's schedule: it replaces nothing in topology.c,
  * which has no counterpart. */
 int shd_pe_batch_info(const ShdPe* pe, int32_t shard, int64_t out[4]);
+/* The launch of the per-row sparse kernel as shard `shard` of this process was
+ * configured (0 <= shard < shd_pe_num_shards; ABI 15; host only, valid from
+ * shd_pe_create on): out[0] = LDS layout (0 row state in HBM, 1 distances in
+ * LDS, 2 distances, hops and row pointers in LDS, 3 distances and pending bits
+ * only), out[1] = threads per workgroup, out[2] = light queue capacity, out[3]
+ * = heavy queue capacity (entries; a frontier beyond either stays pending for
+ * the next bucket scan), out[4] = heavy degree threshold, out[5] = lanes per
+ * light vertex, out[6] = kernel variant bits, out[7] = persistent workgroups.
+ * An engine whose ShdPeStats.batched is 1 runs the batched kernel instead and
+ * reports here what the per-row kernel would have run with.  A diagnostic for
+ * tests of the SHDPE_* switches (a mistyped one leaves the default, which this
+ * call shows): it replaces nothing in topology.c, which has no counterpart. */
+int shd_pe_sparse_info(const ShdPe* pe, int32_t shard, int64_t out[8]);
 
 /* ---- batched helpers on the device ------------
  * The per-query lookups below, for many queries in one call: inputs and

@@ -37,6 +37,7 @@
 //   4. tie export for rows whose target paths meet an ambiguous entry.
 #include <hip/hip_runtime.h>
 
+#include "pe_bucket.hpp"
 #include "pe_device.hpp"
 #include "pe_devutil.hpp"
 
@@ -199,13 +200,6 @@ __device__ __forceinline__ void wave_append(int32_t* Q, int* tail, bool want, in
     base = __shfl(base, leader, 64);
     if (want) __hip_atomic_store(&Q[base + __popcll(m & ((1ull << lane) - 1))], val, __ATOMIC_RELAXED,
                                  __HIP_MEMORY_SCOPE_WORKGROUP);
-}
-
-// bucket of a key: the smallest multiple of delta above it
-__device__ __forceinline__ double next_bound(double mn, double delta) {
-    double nb = (floor(mn / delta) + 1.0) * delta;
-    if (!(mn < nb)) nb = mn + delta;
-    return nb;
 }
 
 // workgroup-uniform values read from LDS, pinned to scalar registers (the
@@ -519,7 +513,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                 const double fm = uni(b2d(ctl->farMin));
                 __syncthreads();
                 if (!farAny) break;
-                bound = uni(fm < b2d(INF_BITS) ? next_bound(fm, delta) : b2d(INF_BITS));
+                bound = uni(fm < b2d(INF_BITS) ? bucket_bound(fm, delta) : b2d(INF_BITS));
                 if (tid == 0) {
                     ctl->farAny = 0;
                     ctl->farMin = INF_BITS;

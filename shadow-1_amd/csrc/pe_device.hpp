@@ -293,7 +293,9 @@ struct SparseLaunch {
     int32_t layout;      // 2: dist+hops+rowPtr in LDS, 1: dist in LDS, 0: HBM slot,
                          // 3: dist+pending in LDS only (2 rows/CU), queues in HBM
     double delta;        // bucket width
-    int32_t kflags;      // kernel variant bits (tuning): 1 AoS arcs in relax, 2 AoS in pred pass
+    int32_t kflags;      // kernel variant bits (tuning): 1 col / lat arrays instead of the 12-B arcs in
+                         // the relax, 2 unused, 4 nontemporal stores in the row writer, 8 grouped predecessor
+                         // pass, 16 / 32 / 48 layout 3 with 2 / 1 / 8 lanes per light vertex
 };
 
 // kernels (pe_kernels.hip); all launched on `stream`.
@@ -340,6 +342,8 @@ void launch_tie_write(const DevGraph& g, const DevTable& tab, const int32_t* dRo
 void launch_direct_rows(const DevGraph& g, const DevTable& tab, const int32_t* dRows,
                         int32_t nRows, void* stream);
 int sparse_max_threads();
+// lanes per light vertex of the k_sparse_rows instantiation that `cfg` launches
+int sparse_lanes_per_vertex(const SparseLaunch& cfg);
 // batched multi-source sparse path (pe_batch.hip): batchRows = nBatches*lb
 // table positions (-1 pads a short batch); rowAmbig[i] != 0 when entry i's
 // row has equal-distance predecessor ties (-> k_exact_rows): 1 = full heap

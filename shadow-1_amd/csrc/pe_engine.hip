@@ -3019,6 +3019,20 @@ extern "C" int shd_pe_batch_info(const ShdPe* pe, int32_t shard, int64_t out[4])
     return SHD_PE_OK;
 }
 
+extern "C" int shd_pe_sparse_info(const ShdPe* pe, int32_t shard, int64_t out[8]) {
+    if (!pe || !out || shard < 0 || (size_t)shard >= pe->shards.size()) return SHD_PE_EINVAL;
+    const shdpe::SparseLaunch& c = pe->shards[(size_t)shard]->cfg;    // (written by configure only)
+    out[0] = c.layout;
+    out[1] = c.threads;
+    out[2] = c.qcap;
+    out[3] = c.hcap;
+    out[4] = c.heavyDeg;
+    out[5] = shdpe::sparse_lanes_per_vertex(c);
+    out[6] = c.kflags;
+    out[7] = c.grid;
+    return SHD_PE_OK;
+}
+
 extern "C" int shd_pe_direct_path(const ShdPe* pe, int32_t s, int32_t t, double* lat,
                                   double* rel) {
     if (!pe) return SHD_PE_EINVAL;

@@ -27,6 +27,7 @@
 #include <cstdlib>
 #include <type_traits>
 
+#include "pe_bucket.hpp"
 #include "pe_device.hpp"
 #include "pe_devutil.hpp"
 
@@ -545,8 +546,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_rows(
                 if (qn == 0 && hn == 0) {
                     if (mn == INF_BITS) break;
                     const double m = b2d(mn);
-                    bound = (floor(m / delta) + 1.0) * delta;
-                    if (!(m < bound)) bound = m + delta;
+                    bound = bucket_bound(m, delta);
                     continue;
                 }
             }
@@ -657,8 +657,7 @@ __global__ __launch_bounds__(SP_THREADS) void k_sparse_rows(
             if (qn == 0 && hn == 0) {
                 if (mn == INF_BITS) break;
                 const double m = b2d(mn);
-                bound = (floor(m / delta) + 1.0) * delta;
-                if (!(m < bound)) bound = m + delta;
+                bound = bucket_bound(m, delta);
                 par ^= 1;
                 __syncthreads();
                 continue;
@@ -2012,6 +2011,12 @@ __global__ __launch_bounds__(256) void k_direct_rows(DevGraph g0, DevTable tab0,
 // ---------------------------------------------------------------------------
 int sparse_max_threads() { return SP_THREADS; }
 
+// kflags bits 4-5 pick layout 3's instantiation; the other layouts have one
+int sparse_lanes_per_vertex(const SparseLaunch& cfg) {
+    static const int lpv[4] = {4, 2, 1, 8};
+    return cfg.layout == 3 ? lpv[(cfg.kflags >> 4) & 3] : 4;
+}
+
 template <int L, int LPV, bool NOROW = false>
 static void launch_sparse_lpv(const DevGraph& g, const DevTable& tab, const DevScratch& sc,
                               const int32_t* dRows, int32_t nRows, uint8_t* dRowAmbig,
@@ -2030,12 +2035,12 @@ static void launch_sparse_layout(const DevGraph& g, const DevTable& tab, const D
                                  const SparseLaunch& cfg, int32_t* dDbg, const TieBuf* dTie,
                                  hipStream_t st, int grid) {
     if constexpr (L == 3) {
-        const int sel = (cfg.kflags >> 4) & 3;
-        if (sel == 1)
+        const int lpv = sparse_lanes_per_vertex(cfg);
+        if (lpv == 2)
             return launch_sparse_lpv<L, 2>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);
-        if (sel == 2)
+        if (lpv == 1)
             return launch_sparse_lpv<L, 1>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);
-        if (sel == 3)
+        if (lpv == 8)
             return launch_sparse_lpv<L, 8>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);
     }
     launch_sparse_lpv<L, 4>(g, tab, sc, dRows, nRows, dRowAmbig, cfg, dDbg, dTie, st, grid);

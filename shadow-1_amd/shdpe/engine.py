@@ -32,7 +32,7 @@ EXPORTS = [
     "shd_pe_compute_rows", "shd_pe_compute_positions", "shd_pe_get_row", "shd_pe_get_rows",
     "shd_pe_copy_rows_device", "shd_pe_synchronize", "shd_pe_get_stats", "shd_pe_reset_stats",
     "shd_pe_get_stats_sized", "shd_pe_stats_size", "shd_pe_pred_filter_counts",
-    "shd_pe_post_split_info", "shd_pe_batch_info",
+    "shd_pe_post_split_info", "shd_pe_batch_info", "shd_pe_sparse_info",
     "shd_pe_stream_bandwidth", "shd_pe_num_shards", "shd_pe_shard_bounds", "shd_pe_plan_shards", "shd_pe_owned_range",
     "shd_pe_gather", "shd_pe_comm_unique_id", "shd_pe_comm_init",
     "shd_pe_direct_path", "shd_pe_self_path", "shd_pe_adjacent", "shd_pe_self_paths",
@@ -265,6 +265,7 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_graph_digest": (C.c_int, [vp, i32, vp, i32, vp]),
         "shd_pe_post_split_info": (C.c_int, [vp, vp, vp, vp]),
         "shd_pe_batch_info": (C.c_int, [vp, i32, vp]),
+        "shd_pe_sparse_info": (C.c_int, [vp, i32, vp]),
         "shd_pe_paths_set_row_tier": (C.c_int, [vp, i32]),
         "shd_pe_num_arcs": (i64, [vp]),
         "shd_pe_arc_list": (C.c_int, [vp, vp, vp]),
@@ -284,7 +285,7 @@ def load_library(path: str = LIB_PATH):
                 "shd_pe_graph_props_host", "shd_pe_fill_rowstore_shards",
                 "shd_topology_fill_shards", "shd_pe_create_built",
                 "shd_pe_graph_digest", "shd_pe_post_split_info",
-                "shd_pe_batch_info", "shd_pe_paths_set_row_tier", "shd_pe_num_arcs",
+                "shd_pe_batch_info", "shd_pe_sparse_info", "shd_pe_paths_set_row_tier", "shd_pe_num_arcs",
                 "shd_pe_arc_list", "shd_pe_find_arc", "shd_pe_path_load",
                 "shd_pe_path_load_info", "shd_topology_link_load"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
@@ -743,6 +744,15 @@ class Engine:
         out = np.zeros(4, np.int64)
         self._chk(self._lib.shd_pe_batch_info(self.h, int(shard), _p(out)), "shd_pe_batch_info")
         return {"perRound": int(out[0]), "slots": int(out[1]), "rounds": int(out[2]), "batches": int(out[3])}
+
+    def sparse_info(self, shard=0) -> dict:
+        """shd_pe_sparse_info of one shard: the per-row sparse kernel's launch as
+        configured (LDS layout, threads, queue capacities, heavy threshold, lanes
+        per light vertex, kflags, grid)."""
+        out = np.zeros(8, np.int64)
+        self._chk(self._lib.shd_pe_sparse_info(self.h, int(shard), _p(out)), "shd_pe_sparse_info")
+        keys = ("layout", "threads", "qcap", "hcap", "heavyDeg", "lanesPerVertex", "kflags", "grid")
+        return {k: int(v) for k, v in zip(keys, out)}
 
     def reset_stats(self):
         self._chk(self._lib.shd_pe_reset_stats(self.h), "shd_pe_reset_stats")

@@ -180,10 +180,14 @@ def test_power_law_hubs(E, oracle_mod):
     _check_engine(E, oracle_mod, top, att, sources=att[::20])
 
 
-def test_large_graph_hbm_layout(E, oracle_mod):
+def test_power_law_60k_takes_batched_kernel(E, oracle_mod):
+    """n = 60,000 has no LDS layout for a row, and configure turns every
+    layout-0 engine into a batched one: this is k_batch_rows (k_sparse_rows'
+    layout 0 runs in tests/test_gpu_relax_matrix.py, with SHDPE_BATCH=0)."""
     top = G.power_law(60_000, m=2, seed=6)
     att = G.sample_attached(top.n, 2000, seed=3)
-    _check_engine(E, oracle_mod, top, att, sources=att[::100])
+    st = _check_engine(E, oracle_mod, top, att, sources=att[::100])
+    assert st["batched"] == 1
 
 
 def test_missing_self_loop_and_unreachable(E, oracle_mod):
