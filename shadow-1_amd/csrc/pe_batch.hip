@@ -270,41 +270,86 @@ __device__ __noinline__ double fold_rel_batch(const double* __restrict__ vrel,
     return acc;
 }
 
-// PART 0: the whole batch in one kernel (relax, predecessors over every
-// vertex, labels + writer, tie export).  PART 1 / 2: the same split in two
-// kernels over a round of batches whose dist arrays persist in HBM between
-// them (slot = batch index): PART 1 relaxes, PART 2 derives predecessors ON
-// DEMAND (only vertices on some target's path in some lane; the full pass only
-// for tie rows and trees too deep for the walks), labels, rows and the tie
-// export -- each with its own register budget.  PART 4: PART 2 without the row
-// writer's stores (the pass of shd_pe_get_paths, which wants the round's
-// distances, ambiguity bytes and tie export only): its own instantiation, so
-// the post kernel keeps its code.  PART 5 / 6: PART 2's first attempt cut in
-// two kernels at the one place where only the batch's `failed` bit crosses
-// (flags[batch]): PART 5 runs the on-demand predecessor pass and the Bellman
-// verdict, PART 6 the label walks, the row writer and the deferred tie-export
-// request, each with its own register budget and its own LDS (pred_heavy_cap /
-// the walk stacks).  Their label records are per BATCH (bs.LB holds a round's),
-// not per workgroup.  A batch that needs PART 2's second attempt (a tree
-// deeper than WALK_BUDGET, a tie batch without a deferred-export buffer)
-// writes no row in PART 6 and is appended to bs.redo; PART 2 launched with
-// bs.redoRun then runs over that list and starts at the full pass.  The order
-// between the kernels is the stream's.
+// k_batch_rows<LB, WPE, GB, PART>.  PART 0 is the whole batch in one kernel; the
+// others split it over a round of batches whose dist arrays persist in HBM (slot
+// = batch index), each with its own register budget and LDS, ordered by the
+// stream; only the batch's flag word crosses.  PART 5 / 6 keep label records
+// per BATCH (bs.LB).  ON DEMAND = only vertices on some target's path.
+//   PART  init             relax  predecessors            labels, rows            ties          then
+//   0     fill, seed       yes    full; repair -> relax   walks, sweeps, rows     in line
+//   1     fill, seed       yes    -                       -                       -             flush_hits, flags
+//   2     failed <- flags  -      on demand, then full    walks | sweeps, rows    request|line
+//   4     as 2 (shd_pe_get_paths' pass: distances, ambiguity bytes, tie export; no row stores)
+//   5     failed <- flags  -      on demand               -                       -             failed -> flags
+//   6     failed <- flags  -      -                       walks, rows | redo      request
+// PART 2's second attempt (full pass) serves a tree deeper than WALK_BUDGET or a
+// tie batch without a deferred-export buffer; PART 6 writes no row for such a
+// batch and appends it to bs.redo; PART 2 with bs.redoRun runs over that list.
+template <int PART> struct PartTraits {
+    static constexpr bool relax_part = PART == 1, pred_part = PART == 5, label_part = PART == 6;
+    static constexpr bool relaxes = PART == 0 || PART == 1;
+    static constexpr bool round_arrays = PART != 0;        // dist arrays per batch of the round
+    static constexpr bool has_labels_in_bs = pred_part || label_part;   // label records per batch too (bs.LB)
+    static constexpr bool uses_bitmaps = !label_part;
+    static constexpr bool reads_relax_flags = PART >= 2;   // bs.flags[b]: failed, in-arc flags written
+    static constexpr bool runs_pred_pass = !relax_part && !label_part;
+    static constexpr bool writes_rows = PART != 4;
+    static constexpr bool defers_ties = PART >= 2;         // k_tie_export after the kernel, if it has a buffer
+    static constexpr bool exports_ties = !relax_part && !pred_part;
+};
+
+// candidates = vertices with a near bit (consumed)
+// (hubs -- degree >= the engine's heavy threshold -- go to a list
+// of their own, processed by whole waves: one 16-lane group on a
+// hub's ~1000 arcs would set the phase's length)
+template <int NT, bool GB>
+__device__ __forceinline__ void list_near(const Bits<GB> anyC, const uint32_t* heavyBits, BCtrl* ctl, int32_t* Q, size_t NS,
+                                          int nw, int tid) {
+    for (int w = tid; w < nw; w += NT) {
+        uint32_t bits = anyC.ld(w);
+        if (bits) {
+            anyC.st(w, 0u);
+            uint32_t hv = bits & heavyBits[w];
+            bits &= ~hv;
+            if (bits) {
+                int pos = atomicAdd(&ctl->qtail, __popc(bits));
+                while (bits) {
+                    const int bb = __ffs(bits) - 1;
+                    bits &= bits - 1;
+                    Q[pos++] = (w << 5) + bb;
+                }
+            }
+            if (hv) {
+                int pos = atomicAdd(&ctl->htail, __popc(hv));
+                while (hv) {
+                    const int bb = __ffs(hv) - 1;
+                    hv &= hv - 1;
+                    Q[NS - 1 - pos++] = (w << 5) + bb;
+                }
+            }
+        }
+    }
+}
+
+// the batch's in-arc flags, LDS -> HBM (bit 1 of the flag word: written)
+template <int NT>
+__device__ __forceinline__ void flush_hits(const uint32_t* hb, uint32_t* AHw, int64_t mStride, int tid) {
+    fence_wg();
+    __syncthreads();
+    const uint4* const H4 = reinterpret_cast<const uint4*>(hb);
+    uint4* const G4 = reinterpret_cast<uint4*>(AHw);
+    const int cnt16 = (int)(mStride >> 7);
+    for (int i = tid; i < cnt16; i += NT) G4[i] = H4[i];
+}
+
 template <int LB, int WPE, bool GB, int PART>
 __global__ __launch_bounds__(BT_THREADS) __attribute__((amdgpu_waves_per_eu(WPE)))
-void k_batch_rows(DevGraph g0, DevTable tab0,
-                                                           BatchScratch bs,
-                                                           const int32_t* __restrict__ batchRows,
-                                                           int32_t nBatches, uint8_t* rowAmbig,
-                                                           double delta, int32_t* dbg,
-                                                           const TieBuf* __restrict__ tieDesc) {
-    constexpr bool NOTAB = PART == 4;
-    constexpr bool PRED = PART == 5, LABEL = PART == 6;
+void k_batch_rows(DevGraph g0, DevTable tab0, BatchScratch bs, const int32_t* __restrict__ batchRows, int32_t nBatches,
+                  uint8_t* rowAmbig, double delta, int32_t* dbg, const TieBuf* __restrict__ tieDesc) {
+    using P = PartTraits<PART>;
     // the plain relax with LDS bitmaps flags in-arcs for the predecessor filter
     constexpr bool HITS = PART == 1 && !GB;
-    constexpr int PT = NOTAB || PRED || LABEL ? 2 : PART;
-    constexpr int BV = BCfg<WPE>::BV;
-    constexpr int SMAX = BCfg<WPE>::SMAX;
+    constexpr int BV = BCfg<WPE>::BV, SMAX = BCfg<WPE>::SMAX;
     // the light-vertex relax loop and the predecessor pass are software-
     // pipelined three takes deep with lane-distributed arc records (round 5:
     // C4 N=1 106 -> 98.4 ms, N=8 shards 19.4 -> 18.9 ms same box, r05f;
@@ -360,8 +405,8 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         const int row = batchRows[(size_t)b * LB + l];
         const int src = row >= 0 ? g.attached[row] : -1;
         if (gid == 0) laneRow[l] = row;
-        if constexpr (PT != 0) D = as_global(bs.D + (size_t)b * SE);
-        if constexpr (PRED || LABEL) LBL = as_global(bs.LB + (size_t)b * SE);
+        if constexpr (P::round_arrays) D = as_global(bs.D + (size_t)b * SE);
+        if constexpr (P::has_labels_in_bs) LBL = as_global(bs.LB + (size_t)b * SE);
         // predecessor filter (split kernels): the batch's in-arc flags, one
         // bit per in-arc slot -- the relax sets bit outToIn[a] when some active
         // lane's pre-check of arc a finds dist[u] + w <= dist[x] (every arc
@@ -373,7 +418,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         // in-arc.  (Flag stores to HBM from the relax loop cost it three times
         // what the pass gains: DESIGN.md §7.)
         uint32_t* AHw = nullptr;
-        if constexpr (PT != 0)
+        if constexpr (P::round_arrays)
             if (bs.arcHit) AHw = as_global(bs.arcHit) + (size_t)b * (size_t)(bs.mStride >> 5);
         uint32_t* const hb = reinterpret_cast<uint32_t*>(smem + BCTRL_BYTES + 8 * nwp);
         const bool hits = HITS && AHw != nullptr && bs.hitLds != 0;
@@ -382,7 +427,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
             ulonglong2* D2 = reinterpret_cast<ulonglong2*>(D);
             const size_t cnt2 = NE / 2;
             const ulonglong2 inf2 = make_ulonglong2(INF_ENC, INF_ENC);
-            if constexpr (PT != 2) {
+            if constexpr (P::relaxes) {
                 for (size_t i = tid; i < cnt2; i += NT) D2[i] = inf2;
                 if (hits) {     // no in-arc flagged yet (mStride is a multiple of 128 bits)
                     uint4* const H4 = reinterpret_cast<uint4*>(hb);
@@ -390,7 +435,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
                     for (int i = tid; i < cnt16; i += NT) H4[i] = make_uint4(0u, 0u, 0u, 0u);
                 }
             }
-            if constexpr (!LABEL)
+            if constexpr (P::uses_bitmaps)
                 for (int w = tid; w < nwp; w += NT) { any0.st(w, 0u); any1.st(w, 0u); }
             if (tid == 0) {
                 ctl->qtail = 0;
@@ -414,7 +459,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         // plan, lane_offsets); key = dist + (maxOff - off) lines the lanes up
         const double off = row >= 0 ? as_global(bs.laneOff)[(size_t)b * LB + l] : 0.0;
         if (gid == 0) atomicMax(reinterpret_cast<unsigned long long*>(&ctl->maxOff), d2b(off));
-        if (PT != 2 && gid == 0 && src >= 0) {
+        if (P::relaxes && gid == 0 && src >= 0) {
             D[(size_t)src * LB + l] = enc_dirty(d2b(0.0));
             any0.set(src);
         }
@@ -443,7 +488,7 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         const int phaseCap = 8 * n + 1024;
         double bound = delta;
         unsigned long long myFar = INF_BITS;      // smallest far key this thread added
-        if constexpr (PT == 2) failed = (as_global(bs.flags)[b] & 1) != 0;
+        if constexpr (P::reads_relax_flags) failed = (as_global(bs.flags)[b] & 1) != 0;
 #ifdef SHDPE_DIAG_WHY
         uint32_t why = failed ? 128u : 0u;
         __shared__ int sDiagViol;
@@ -454,1198 +499,1150 @@ void k_batch_rows(DevGraph g0, DevTable tab0,
         bool lastFull = true;     // the final attempt ran the full predecessor pass
         // (the redo launch starts at the full pass: what attempt 1 does)
         for (int attempt = PART == 2 && bs.redoRun ? 1 : 0;; ++attempt) {
-        const bool fullPred = !(PRED || LABEL) && (PT != 2 || attempt > 0);
-        if (attempt > 0) DIAG_WHY(64u);
-        if (attempt > 0) {
-            if (tid == 0) {
-                ctl->qtail = 0;
-                ctl->changed = 0;
-                ctl->ambMask = 0u;
-            }
-            fence_wg();
-            __syncthreads();
-        }
-        for (;;) {   // phases + verification until the Bellman check holds
-        if constexpr (PT != 2) {
-        for (;;) {
-            if (failed) break;
-            const Bits<GB> anyC = par ? any1 : any0;   // near
-            const Bits<GB> anyF = par ? any0 : any1;   // far
-            // candidates = vertices with a near bit (consumed)
-            // (hubs -- degree >= the engine's heavy threshold -- go to a list
-            // of their own, processed by whole waves: one 16-lane group on a
-            // hub's ~1000 arcs would set the phase's length)
-            for (int w = tid; w < nw; w += NT) {
-                uint32_t bits = anyC.ld(w);
-                if (bits) {
-                    anyC.st(w, 0u);
-                    uint32_t hv = bits & g.heavyBits[w];
-                    bits &= ~hv;
-                    if (bits) {
-                        int pos = atomicAdd(&ctl->qtail, __popc(bits));
-                        while (bits) {
-                            const int bb = __ffs(bits) - 1;
-                            bits &= bits - 1;
-                            Q[pos++] = (w << 5) + bb;
-                        }
-                    }
-                    if (hv) {
-                        int pos = atomicAdd(&ctl->htail, __popc(hv));
-                        while (hv) {
-                            const int bb = __ffs(hv) - 1;
-                            hv &= hv - 1;
-                            Q[NS - 1 - pos++] = (w << 5) + bb;
-                        }
-                    }
-                }
-            }
-            if (myFar != INF_BITS) {
-                atomicMin(&ctl->farMin, myFar);
-                myFar = INF_BITS;
-            }
-            fence_wg();
-            __syncthreads();
-            const int qn = uni(ctl->qtail);
-            const int hn = uni(ctl->htail);
-            if (qn == 0 && hn == 0) {
-                // bucket settled: advance to the far set, or done
-                const int farAny = uni(ctl->farAny);
-                const double fm = uni(b2d(ctl->farMin));
-                __syncthreads();
-                if (!farAny) break;
-                bound = uni(fm < b2d(INF_BITS) ? bucket_bound(fm, delta) : b2d(INF_BITS));
+            const bool fullPred = P::relaxes || (!P::has_labels_in_bs && attempt > 0);
+            if (attempt > 0) DIAG_WHY(64u);
+            if (attempt > 0) {
                 if (tid == 0) {
-                    ctl->farAny = 0;
-                    ctl->farMin = INF_BITS;
+                    ctl->qtail = 0;
+                    ctl->changed = 0;
+                    ctl->ambMask = 0u;
                 }
-                par ^= 1;
-                ++phases;
+                fence_wg();
                 __syncthreads();
-                continue;
             }
-            if (phases > phaseCap) {        // safety net: never spin the GPU
-                failed = true;
-                break;
-            }
-            int farAdd = 0;
-            const long long tg0 = dbg ? (long long)clock64() : 0;
-            // hubs first (their improvements reach the light vertices in this
-            // phase): one wave per hub, its 64 / LB groups interleave the arcs
-            {
-                constexpr int GPW = 64 / LB;
-                const int wv = tid >> 6, NW = NT >> 6, gw = (tid & 63) / LB;
-                for (int h = wv; h < hn; h += NW) {
-                    const int u = ld_wg(&Q[NS - 1 - h]);
-                    unsigned long long* const pu = &D[(size_t)u * LB + l];
-                    const unsigned long long e0 = ld_d(pu);
-                    const int a0 = g.rowPtr[u], a1 = g.rowPtr[u + 1];
-                    const double k0 = b2d(dec(e0)) + sh;
-                    const bool dirty = is_dirty(e0);
-                    const bool below = dirty && k0 < bound;
-                    const bool act = EAGER ? dirty && __ballot(below) >> gbase & LBMASK : below;
-                    const bool defer = dirty && !act;
-                    const uint32_t amask = (uint32_t)(__ballot(act) >> gbase) & LBMASK;
-                    const uint32_t dmask = (uint32_t)(__ballot(defer) >> gbase) & LBMASK;
-                    if (gw == 0 && l == 0 && dmask) anyF.set(u);
-                    if (gw == 0 && defer) {
-                        myFar = d2b(k0) < myFar ? d2b(k0) : myFar;
-                        farAdd = 1;
-                    }
-                    if (gw == 0 && act) mark_clean(pu, e0);
-                    const unsigned long long dub1 = act ? dec(e0) : INF_BITS;
-                    if (!__ballot(amask != 0)) continue;       // wave-uniform
-                    if (dbg && gw == 0 && l == 0) {
-                        atomicAdd(&ctl->dProcs, 1u);
-                        atomicAdd(&ctl->dArcs, (unsigned int)(a1 - a0));
-                        atomicAdd(&ctl->dLanes, (unsigned int)__popc(amask));
-                    }
-                    for (int t = a0 + gw * BK; t < a1; t += GPW * BK) {
-                        int xs[BK], rs[BK];
-                        double ws[BK];
-                        unsigned long long dx[BK];
-#pragma unroll
-                        for (int k = 0; k < BK; ++k) {
-                            const int a = t + k;
-                            const bool ok = a < a1;
-                            const Arc A = g.arcs[ok ? a : 0];
-                            xs[k] = ok ? A.col : -1;
-                            ws[k] = A.lat;
-                            rs[k] = A.pad;
+            for (;;) {   // phases + verification until the Bellman check holds
+                if constexpr (P::relaxes) {
+                    for (;;) {
+                        if (failed) break;
+                        const Bits<GB> anyC = par ? any1 : any0;   // near
+                        const Bits<GB> anyF = par ? any0 : any1;   // far
+                        list_near<NT>(anyC, g.heavyBits, ctl, Q, NS, nw, tid);
+                        if (myFar != INF_BITS) {
+                            atomicMin(&ctl->farMin, myFar);
+                            myFar = INF_BITS;
                         }
-#pragma unroll
-                        for (int k = 0; k < BK; ++k)
-                            dx[k] = relax_ld(D, xs[k] >= 0 ? xs[k] : 0, LB, l);
-#pragma unroll
-                        for (int k = 0; k < BK; ++k) {
-                            const int x = xs[k];
-                            bool impN = false, impF = false, hit = false;
-                            if (x >= 0) {
-                                const double nd = b2d(dub1) + ws[k];
-                                const unsigned long long nb = d2b(nd);
-                                hit = act && nb <= dec(dx[k]);
-                                if (nb < dec(dx[k])) {
-                                    relax_min(&D[(size_t)x * LB + l], enc_dirty(nb));
-                                    const double kx = nd + sh;
-                                    impN = kx < bound;
-                                    impF = !impN;
-                                    if (impF) myFar = d2b(kx) < myFar ? d2b(kx) : myFar;
-                                }
+                        fence_wg();
+                        __syncthreads();
+                        const int qn = uni(ctl->qtail);
+                        const int hn = uni(ctl->htail);
+                        if (qn == 0 && hn == 0) {
+                            // bucket settled: advance to the far set, or done
+                            const int farAny = uni(ctl->farAny);
+                            const double fm = uni(b2d(ctl->farMin));
+                            __syncthreads();
+                            if (!farAny) break;
+                            bound = uni(fm < b2d(INF_BITS) ? bucket_bound(fm, delta) : b2d(INF_BITS));
+                            if (tid == 0) {
+                                ctl->farAny = 0;
+                                ctl->farMin = INF_BITS;
                             }
-                            const uint64_t bn = __ballot(impN), bf = __ballot(impF);
-                            uint64_t bh = 0;
-                            if constexpr (HITS) bh = __ballot(hit);
-                            if (l == 0) {
-                                if ((bn >> gbase) & LBMASK) anyC.set(x);
-                                if ((bf >> gbase) & LBMASK) {
-                                    anyF.set(x);
+                            par ^= 1;
+                            ++phases;
+                            __syncthreads();
+                            continue;
+                        }
+                        if (phases > phaseCap) {        // safety net: never spin the GPU
+                            failed = true;
+                            break;
+                        }
+                        int farAdd = 0;
+                        const long long tg0 = dbg ? (long long)clock64() : 0;
+                        // hubs first (their improvements reach the light vertices in this
+                        // phase): one wave per hub, its 64 / LB groups interleave the arcs
+                        {
+                            constexpr int GPW = 64 / LB;
+                            const int wv = tid >> 6, NW = NT >> 6, gw = (tid & 63) / LB;
+                            for (int h = wv; h < hn; h += NW) {
+                                const int u = ld_wg(&Q[NS - 1 - h]);
+                                unsigned long long* const pu = &D[(size_t)u * LB + l];
+                                const unsigned long long e0 = ld_d(pu);
+                                const int a0 = g.rowPtr[u], a1 = g.rowPtr[u + 1];
+                                const double k0 = b2d(dec(e0)) + sh;
+                                const bool dirty = is_dirty(e0);
+                                const bool below = dirty && k0 < bound;
+                                const bool act = EAGER ? dirty && __ballot(below) >> gbase & LBMASK : below;
+                                const bool defer = dirty && !act;
+                                const uint32_t amask = (uint32_t)(__ballot(act) >> gbase) & LBMASK;
+                                const uint32_t dmask = (uint32_t)(__ballot(defer) >> gbase) & LBMASK;
+                                if (gw == 0 && l == 0 && dmask) anyF.set(u);
+                                if (gw == 0 && defer) {
+                                    myFar = d2b(k0) < myFar ? d2b(k0) : myFar;
                                     farAdd = 1;
                                 }
-                                // tight or improving in some lane: flag the in-arc
-                                if constexpr (HITS)
-                                    if (hits && ((bh >> gbase) & LBMASK)) atomicOr(&hb[rs[k] >> 5], 1u << (rs[k] & 31));
-                            }
-                        }
-                    }
-                }
-            }
-            // Groups take BV queue entries at a time from an LDS counter, so
-            // the phase ends when the last entry is done rather than when the
-            // unluckiest static share is.  A value loaded ahead may be stale;
-            // like any racing read it is only ever larger (entries decrease):
-            // relaxing from it is wasted work, and its clean mark (atomic min)
-            // leaves a newer dirty value dirty for the next listing round.
-            const int qc = qn > 0 ? qn - 1 : 0;
-            auto take = [&]() {
-                int i = 0;
-                if (l == 0) i = atomicAdd(&ctl->qhead, BV);
-                return __shfl(i, gbase, 64);
-            };
-            // A three-stage software pipeline over the group's takes (BV
-            // vertices each).  The group's lanes hold ONE arc record per
-            // vertex (lane l: arc a0 + l of the vertex's first LB arcs --
-            // one coalesced LB x 16-B read per group instead of BK
-            // broadcast records per round and a dependent record round
-            // trip before every dist gather); the relaxing lanes take the
-            // heads by cross-lane reads.  Per take the group issues the
-            // records of the next take, the dist lines + row ranges of the
-            // one after, and the queue entries of the third, then relaxes
-            // the current vertices: their chain is the BKR-wide dist
-            // gathers only.  An entry past the queue end is u = -1 (takes
-            // rise monotonically, so a take whose first entry is -1 ends).
-            auto q_at = [&](int i) { return i < qn ? ld_wg(&Q[min(i, qc)]) : -1; };
-            auto ld_head = [&](int uu, unsigned long long& d, int& r0, int& r1) {
-                const int uc = uu >= 0 ? uu : 0;
-                const unsigned long long d0 = ld_d(&D[(size_t)uc * LB + l]);
-                const int x0 = g.rowPtr[uc], x1 = g.rowPtr[uc + 1];
-                d = uu >= 0 ? d0 : INF_ENC;
-                r0 = uu >= 0 ? x0 : 0;
-                r1 = uu >= 0 ? x1 : 0;
-            };
-            auto ld_arc = [&](int a, int aEnd, int& c, double& w, int& r) {
-                const bool ok = a < aEnd;
-                const Arc A = g.arcs[ok ? a : 0];
-                c = ok ? A.col : -1;
-                w = A.lat;
-                r = A.pad;      // the arc's slot in its head's in-list (same 16-B record)
-            };
-            int uC[BV], u1[BV], u2[BV], a0C[BV], a1C[BV], a01[BV], a11[BV], mcC[BV], mrC[BV];
-            unsigned long long dbC[BV], db1[BV];
-            double mlC[BV];
-            {
-                const int i0 = take(), i1 = take(), i2 = take();
+                                if (gw == 0 && act) mark_clean(pu, e0);
+                                const unsigned long long dub1 = act ? dec(e0) : INF_BITS;
+                                if (!__ballot(amask != 0)) continue;       // wave-uniform
+                                if (dbg && gw == 0 && l == 0) {
+                                    atomicAdd(&ctl->dProcs, 1u);
+                                    atomicAdd(&ctl->dArcs, (unsigned int)(a1 - a0));
+                                    atomicAdd(&ctl->dLanes, (unsigned int)__popc(amask));
+                                }
+                                for (int t = a0 + gw * BK; t < a1; t += GPW * BK) {
+                                    int xs[BK], rs[BK];
+                                    double ws[BK];
+                                    unsigned long long dx[BK];
 #pragma unroll
-                for (int v = 0; v < BV; ++v) {
-                    uC[v] = q_at(i0 + v);
-                    u1[v] = q_at(i1 + v);
-                    u2[v] = q_at(i2 + v);
-                }
-            }
+                                    for (int k = 0; k < BK; ++k) {
+                                        const int a = t + k;
+                                        const bool ok = a < a1;
+                                        const Arc A = g.arcs[ok ? a : 0];
+                                        xs[k] = ok ? A.col : -1;
+                                        ws[k] = A.lat;
+                                        rs[k] = A.pad;
+                                    }
 #pragma unroll
-            for (int v = 0; v < BV; ++v) {
-                ld_head(uC[v], dbC[v], a0C[v], a1C[v]);
-                ld_head(u1[v], db1[v], a01[v], a11[v]);
-            }
+                                    for (int k = 0; k < BK; ++k)
+                                        dx[k] = relax_ld(D, xs[k] >= 0 ? xs[k] : 0, LB, l);
 #pragma unroll
-            for (int v = 0; v < BV; ++v) ld_arc(a0C[v] + l, a1C[v], mcC[v], mlC[v], mrC[v]);
-            while (uC[0] >= 0) {
-                int mc1[BV], mr1[BV], a02[BV], a12[BV], u3[BV];
-                double ml1[BV];
-                unsigned long long db2[BV];
-#pragma unroll
-                for (int v = 0; v < BV; ++v) ld_arc(a01[v] + l, a11[v], mc1[v], ml1[v], mr1[v]);
-#pragma unroll
-                for (int v = 0; v < BV; ++v) ld_head(u2[v], db2[v], a02[v], a12[v]);
-                {
-                    const int i3 = take();
-#pragma unroll
-                    for (int v = 0; v < BV; ++v) u3[v] = q_at(i3 + v);
-                }
-                unsigned long long dub[BV];
-                int deg[BV], maxd = 0;
-#pragma unroll
-                for (int v = 0; v < BV; ++v) {
-                    const double k0 = b2d(dec(dbC[v])) + sh;
-                    const bool dirty = is_dirty(dbC[v]);
-                    const bool below = dirty && k0 < bound;
-                    const bool act = EAGER ? dirty && __ballot(below) >> gbase & LBMASK : below;
-                    const bool defer = dirty && !act;
-                    const uint32_t amask = (uint32_t)(__ballot(act) >> gbase) & LBMASK;
-                    const uint32_t dmask = (uint32_t)(__ballot(defer) >> gbase) & LBMASK;
-                    if (l == 0 && dmask) anyF.set(uC[v]);
-                    if (defer) {
-                        myFar = d2b(k0) < myFar ? d2b(k0) : myFar;
-                        farAdd = 1;
-                    }
-                    if (act) mark_clean(&D[(size_t)uC[v] * LB + l], dbC[v]);
-                    dub[v] = act ? dec(dbC[v]) : INF_BITS;
-                    deg[v] = amask ? a1C[v] - a0C[v] : 0;          // group-uniform
-                    if (amask && dbg && l == 0) {
-                        atomicAdd(&ctl->dProcs, 1u);
-                        atomicAdd(&ctl->dArcs, (unsigned int)deg[v]);
-                        atomicAdd(&ctl->dLanes, (unsigned int)__popc(amask));
-                    }
-                    maxd = max(maxd, deg[v]);
-                }
-                // relax the out-arcs for the dirty lanes below the bound
-                for (int c0 = 0; c0 < maxd; c0 += LB) {
-                    int mc[BV], mr[BV];
-                    double ml[BV];
-#pragma unroll
-                    for (int v = 0; v < BV; ++v) {
-                        mc[v] = mcC[v];
-                        ml[v] = mlC[v];
-                        mr[v] = mrC[v];
-                        if (c0 > 0) ld_arc(a0C[v] + c0 + l, a0C[v] + deg[v], mc[v], ml[v], mr[v]);   // degree > LB
-                    }
-                    const int cn = min(LB, maxd - c0);
-                    uint32_t hacc[BV];      // the chunk's arcs with a hit in some lane
-#pragma unroll
-                    for (int v = 0; v < BV; ++v) hacc[v] = 0u;
-                    for (int t = 0; t < cn; t += BKR) {
-                        int xs[BV][BKR];
-                        double ws[BV][BKR];
-                        unsigned long long dx[BV][BKR];
-#pragma unroll
-                        for (int v = 0; v < BV; ++v)
-#pragma unroll
-                            for (int k = 0; k < BKR; ++k) {
-                                const int srcL = gbase + min(t + k, LB - 1);   // inside the group
-                                const int c = __shfl(mc[v], srcL, 64);
-                                ws[v][k] = __shfl(ml[v], srcL, 64);
-                                xs[v][k] = t + k < cn && c0 + t + k < deg[v] ? c : -1;   // (the chunk's own records)
-                            }
-#pragma unroll
-                        for (int v = 0; v < BV; ++v)
-#pragma unroll
-                            for (int k = 0; k < BKR; ++k)
-                                dx[v][k] = relax_ld(D, xs[v][k] >= 0 ? xs[v][k] : 0, LB, l);
-#pragma unroll
-                        for (int v = 0; v < BV; ++v)
-#pragma unroll
-                            for (int k = 0; k < BKR; ++k) {
-                                const int x = xs[v][k];
-                                bool impN = false, impF = false, hit = false;
-                                if (x >= 0) {
-                                    const double nd = b2d(dub[v]) + ws[v][k];
-                                    const unsigned long long nb = d2b(nd);
-                                    hit = dub[v] != INF_BITS && nb <= dec(dx[v][k]);
-                                    if (nb < dec(dx[v][k])) {
-                                        relax_min(&D[(size_t)x * LB + l], enc_dirty(nb));
-                                        const double kx = nd + sh;
-                                        impN = kx < bound;
-                                        impF = !impN;
-                                        if (impF) myFar = d2b(kx) < myFar ? d2b(kx) : myFar;
+                                    for (int k = 0; k < BK; ++k) {
+                                        const int x = xs[k];
+                                        bool impN = false, impF = false, hit = false;
+                                        if (x >= 0) {
+                                            const double nd = b2d(dub1) + ws[k];
+                                            const unsigned long long nb = d2b(nd);
+                                            hit = act && nb <= dec(dx[k]);
+                                            if (nb < dec(dx[k])) {
+                                                relax_min(&D[(size_t)x * LB + l], enc_dirty(nb));
+                                                const double kx = nd + sh;
+                                                impN = kx < bound;
+                                                impF = !impN;
+                                                if (impF) myFar = d2b(kx) < myFar ? d2b(kx) : myFar;
+                                            }
+                                        }
+                                        const uint64_t bn = __ballot(impN), bf = __ballot(impF);
+                                        uint64_t bh = 0;
+                                        if constexpr (HITS) bh = __ballot(hit);
+                                        if (l == 0) {
+                                            if ((bn >> gbase) & LBMASK) anyC.set(x);
+                                            if ((bf >> gbase) & LBMASK) {
+                                                anyF.set(x);
+                                                farAdd = 1;
+                                            }
+                                            // tight or improving in some lane: flag the in-arc
+                                            if constexpr (HITS)
+                                                if (hits && ((bh >> gbase) & LBMASK)) atomicOr(&hb[rs[k] >> 5], 1u << (rs[k] & 31));
+                                        }
                                     }
                                 }
-                                const uint64_t bn = __ballot(impN), bf = __ballot(impF);
-                                if (l == 0) {
-                                    if ((bn >> gbase) & LBMASK) anyC.set(x);
-                                    if ((bf >> gbase) & LBMASK) {
-                                        anyF.set(x);
-                                        farAdd = 1;
-                                    }
-                                }
-                                if constexpr (HITS) {      // (branch-free: `hits` gates the store below)
-                                    const uint64_t bh = __ballot(hit);
-                                    hacc[v] |= (bh >> gbase) & LBMASK ? 1u << ((t + k) & 31) : 0u;
-                                }
                             }
-                    }
-                    // tight or improving in some lane: the lane that holds the
-                    // arc's record flags its in-arc slot (once per chunk)
-                    if constexpr (HITS) {
-#pragma unroll
-                        for (int v = 0; v < BV; ++v)
-                            if (hits && ((hacc[v] >> l) & 1u)) atomicOr(&hb[mr[v] >> 5], 1u << (mr[v] & 31));
-                    }
-                }
-#pragma unroll
-                for (int v = 0; v < BV; ++v) {
-                    uC[v] = u1[v]; dbC[v] = db1[v]; a0C[v] = a01[v]; a1C[v] = a11[v];
-                    mcC[v] = mc1[v]; mlC[v] = ml1[v]; mrC[v] = mr1[v];
-                    u1[v] = u2[v]; db1[v] = db2[v]; a01[v] = a02[v]; a11[v] = a12[v];
-                    u2[v] = u3[v];
-                }
-            }
-            if (dbg && l == 0) {
-                const unsigned long long bz = (unsigned long long)((long long)clock64() - tg0);
-                atomicMax(&ctl->busyMax, bz);
-                atomicAdd(&ctl->busySum, bz);
-            }
-            if (farAdd) ctl->farAny = 1;
-            fence_wg();
-            __syncthreads();
-            if (tid == 0) {
-                ctl->qtail = 0;
-                ctl->qhead = 0;
-                ctl->htail = 0;
-                if (dbg) {
-                    atomicAdd(&dbg[16 * b + 12], (int)(ctl->busyMax >> 10));
-                    atomicAdd(&dbg[16 * b + 13], (int)((ctl->busySum / NG) >> 10));
-                    atomicAdd(&dbg[16 * b + 14], qn);
-                    ctl->busyMax = 0;
-                    ctl->busySum = 0;
-                }
-            }
-            ++phases;
-            __syncthreads();
-        }
-        }   // PT != 2
-        if (dbg && tid == 0) ctl->t1 = (long long)clock64();
-        if constexpr (PT == 1) break;
-        if constexpr (LABEL) break;      // (the predecessor part ran, PART 5)
-
-        // ================= 2. Bellman check + predecessor pass ===============
-        // (a) every entry must satisfy dist[v] <= dist[u] + w for all in-arcs
-        //     (a violation = an update lost to a concurrent plain store: fix
-        //     it, mark v pending, and go back to phase 1);
-        // (b) igraph sets parent[v] from the first POPPED tight predecessor:
-        //     the tight in-arc with minimum dist[u]; equal minima from distinct
-        //     vertices (or a zero-increment arc) -> the heap decides -> tie
-        //     row (k_exact_rows) if such an entry lies on a target's path.
-        int viol = 0;
-        {
-            const Bits<GB> anyC = par ? any1 : any0;
-            // on demand: vertices are claimed in the (empty) far bitmap and
-            // listed in Q, targets first, then round by round the tree
-            // parents of the last round's entries in every lane
-            const Bits<GB> clm = par ? any0 : any1;
-            // entries of in-degree >= PRED_HEAVY are set aside per round and
-            // scanned by a whole wave each (its groups split the in-arcs and
-            // combine by cross-group shuffles): one group on a hub's ~1000
-            // in-arcs would set the round's length.  List in the LDS beyond
-            // the bitmaps (free until the label walks), capped by that room.
-            int* const heavyList = reinterpret_cast<int*>(smem + BCTRL_BYTES + (GB ? 0 : 8 * nwp));
-            const int stackB = NT * SMAX * 8, bitsB = GB ? 0 : 8 * nwp;
-            const int hcap = PRED ? pred_heavy_cap(nwp, GB) : min(4096, max(0, stackB - bitsB) / 4);
-            int lo = 0, hi = n;
-            // the on-demand pass gathers only the in-arcs the relax flagged (a
-            // superset of the tight ones); the full pass reads every in-arc
-            bool filt = false;
-            if constexpr (PT == 2) filt = !fullPred && AHw != nullptr && (as_global(bs.flags)[b] & 2) != 0;
-            if (!fullPred) {
-                for (int j = tid; j < g.T; j += NT) {
-                    const int v = g.attached[j];
-                    wave_append(Q, &ctl->qtail, !clm.test_set(v), v);
-                }
-                fence_wg();
-                __syncthreads();
-                hi = uni(ctl->qtail);
-                __syncthreads();
-            }
-            while (lo < hi) {
-            // the relax loop's three-stage pipeline (BV list entries per
-            // group and stride): the group's lanes hold one in-arc record
-            // per entry (lane l: in-arc a0 + l, one coalesced read), the
-            // scan takes the tails by cross-lane reads, so an entry's
-            // chain is its BKQ-wide dist gathers.  Records of the next
-            // stride, dist lines + in-arc ranges of the one after, list
-            // entries of the third are in flight meanwhile.
-            const int S = NG * BV;
-            auto item = [&](int i) { return i < hi ? (fullPred ? i : ld_wg(&Q[i])) : -1; };
-            auto ld_head = [&](int vv, unsigned long long& d, int& r0, int& r1) {
-                const int vc = vv >= 0 ? vv : 0;
-                const unsigned long long d0 = dec(ld_wg(&D[(size_t)vc * LB + l]));
-                const int x0 = undirected ? g.rowPtr[vc] : g.inPtr[vc];
-                const int x1 = undirected ? g.rowPtr[vc + 1] : g.inPtr[vc + 1];
-                d = vv >= 0 ? d0 : INF_BITS;
-                r0 = vv >= 0 ? x0 : 0;
-                r1 = vv >= 0 ? x1 : 0;
-            };
-            // (filtered pass: an in-arc the relax did not flag reads as absent
-            // -- its flag bit is loaded beside its record, one or two words
-            // per group)
-            auto ld_rec = [&](int a, int aEnd, int& c, double& w) {
-                bool ok = a < aEnd;
-                const int ac = ok ? a : 0;
-                if (filt) ok = ok && ((AHw[ac >> 5] >> (ac & 31)) & 1u) != 0;
-                if (undirected) {
-                    const Arc A = g.arcs[ac];
-                    c = A.col;
-                    w = A.lat;
-                } else {
-                    c = g.inCol[ac];
-                    w = g.inLat[ac];
-                }
-                c = ok ? c : -1;
-            };
-            int v0 = lo + gid * BV;
-            int vC[BV], v1[BV], v2[BV], a0C[BV], a1C[BV], a01[BV], a11[BV], mcC[BV];
-            unsigned long long dC[BV], d1[BV];
-            double mlC[BV];
-#pragma unroll
-            for (int v = 0; v < BV; ++v) {
-                vC[v] = item(v0 + v);
-                v1[v] = item(v0 + S + v);
-                v2[v] = item(v0 + 2 * S + v);
-            }
-#pragma unroll
-            for (int v = 0; v < BV; ++v) {
-                ld_head(vC[v], dC[v], a0C[v], a1C[v]);
-                ld_head(v1[v], d1[v], a01[v], a11[v]);
-            }
-#pragma unroll
-            for (int v = 0; v < BV; ++v) ld_rec(a0C[v] + l, a1C[v], mcC[v], mlC[v]);
-            for (; v0 < hi; v0 += S) {
-                int mc1[BV], a02[BV], a12[BV], v3[BV];
-                double ml1[BV];
-                unsigned long long d2[BV];
-#pragma unroll
-                for (int v = 0; v < BV; ++v) ld_rec(a01[v] + l, a11[v], mc1[v], ml1[v]);
-#pragma unroll
-                for (int v = 0; v < BV; ++v) ld_head(v2[v], d2[v], a02[v], a12[v]);
-#pragma unroll
-                for (int v = 0; v < BV; ++v) v3[v] = item(v0 + 3 * S + v);
-                bool root[BV], hvy[BV];
-                unsigned long long best[BV], mn[BV];
-                int cnt[BV], ba[BV], bu[BV], deg[BV], maxd = 0;
-#pragma unroll
-                for (int v = 0; v < BV; ++v) {
-                    root[v] = vC[v] == src || src < 0;
-                    best[v] = INF_BITS;
-                    mn[v] = INF_BITS;
-                    cnt[v] = 0;
-                    ba[v] = -1;
-                    bu[v] = -1;
-                    deg[v] = vC[v] >= 0 ? a1C[v] - a0C[v] : 0;   // group-uniform
-                    hvy[v] = false;
-                    if (dbg && !fullPred && l == 0 && deg[v]) atomicAdd(&ctl->dClaim, (unsigned int)deg[v]);
-                    if (deg[v] >= PRED_HEAVY) {                   // -> the round's wave pass
-                        int slot = 0;
-                        if (l == 0) slot = atomicAdd(&ctl->htail, 1);
-                        slot = __shfl(slot, gbase, 64);
-                        if (slot < hcap) {
-                            if (l == 0) heavyList[slot] = vC[v];
-                            hvy[v] = true;
-                            deg[v] = 0;
                         }
-                    }
-                    maxd = max(maxd, deg[v]);
-                }
-                for (int c0 = 0; c0 < maxd; c0 += LB) {
-                    int mc[BV];
-                    double ml[BV];
+                        // Groups take BV queue entries at a time from an LDS counter, so
+                        // the phase ends when the last entry is done rather than when the
+                        // unluckiest static share is.  A value loaded ahead may be stale;
+                        // like any racing read it is only ever larger (entries decrease):
+                        // relaxing from it is wasted work, and its clean mark (atomic min)
+                        // leaves a newer dirty value dirty for the next listing round.
+                        const int qc = qn > 0 ? qn - 1 : 0;
+                        auto take = [&]() {
+                            int i = 0;
+                            if (l == 0) i = atomicAdd(&ctl->qhead, BV);
+                            return __shfl(i, gbase, 64);
+                        };
+                        // A three-stage software pipeline over the group's takes (BV
+                        // vertices each).  The group's lanes hold ONE arc record per
+                        // vertex (lane l: arc a0 + l of the vertex's first LB arcs --
+                        // one coalesced LB x 16-B read per group instead of BK
+                        // broadcast records per round and a dependent record round
+                        // trip before every dist gather); the relaxing lanes take the
+                        // heads by cross-lane reads.  Per take the group issues the
+                        // records of the next take, the dist lines + row ranges of the
+                        // one after, and the queue entries of the third, then relaxes
+                        // the current vertices: their chain is the BKR-wide dist
+                        // gathers only.  An entry past the queue end is u = -1 (takes
+                        // rise monotonically, so a take whose first entry is -1 ends).
+                        auto q_at = [&](int i) { return i < qn ? ld_wg(&Q[min(i, qc)]) : -1; };
+                        auto ld_head = [&](int uu, unsigned long long& d, int& r0, int& r1) {
+                            const int uc = uu >= 0 ? uu : 0;
+                            const unsigned long long d0 = ld_d(&D[(size_t)uc * LB + l]);
+                            const int x0 = g.rowPtr[uc], x1 = g.rowPtr[uc + 1];
+                            d = uu >= 0 ? d0 : INF_ENC;
+                            r0 = uu >= 0 ? x0 : 0;
+                            r1 = uu >= 0 ? x1 : 0;
+                        };
+                        auto ld_arc = [&](int a, int aEnd, int& c, double& w, int& r) {
+                            const bool ok = a < aEnd;
+                            const Arc A = g.arcs[ok ? a : 0];
+                            c = ok ? A.col : -1;
+                            w = A.lat;
+                            r = A.pad;      // the arc's slot in its head's in-list (same 16-B record)
+                        };
+                        int uC[BV], u1[BV], u2[BV], a0C[BV], a1C[BV], a01[BV], a11[BV], mcC[BV], mrC[BV];
+                        unsigned long long dbC[BV], db1[BV];
+                        double mlC[BV];
+                        {
+                            const int i0 = take(), i1 = take(), i2 = take();
 #pragma unroll
-                    for (int v = 0; v < BV; ++v) {
-                        mc[v] = mcC[v];
-                        ml[v] = mlC[v];
-                        if (c0 > 0) ld_rec(a0C[v] + c0 + l, a0C[v] + deg[v], mc[v], ml[v]);
-                    }
-                    // the chunk's records to gather: those present (in the
-                    // filtered pass, flagged), as a mask over the group's lanes;
-                    // the gather rounds walk its set bits in in-list order
-                    uint32_t hm[BV], hany = 0u;
-#pragma unroll
-                    for (int v = 0; v < BV; ++v) {
-                        const int rem = deg[v] - c0;
-                        const uint32_t dm = rem >= LB ? LBMASK : rem > 0 ? (1u << (rem & 31)) - 1u : 0u;
-                        hm[v] = (uint32_t)(__ballot(mc[v] >= 0) >> gbase) & dm;
-                        if (dbg && !fullPred && l == 0 && hm[v]) atomicAdd(&ctl->dGath, (unsigned int)__popc(hm[v]));
-                        hany |= hm[v];
-                    }
-                    while (hany) {
-                        int cu[BV][BKQ], jj[BV][BKQ];
-                        double lw[BV][BKQ];
-                        unsigned long long du[BV][BKQ];
-                        hany = 0u;
+                            for (int v = 0; v < BV; ++v) {
+                                uC[v] = q_at(i0 + v);
+                                u1[v] = q_at(i1 + v);
+                                u2[v] = q_at(i2 + v);
+                            }
+                        }
 #pragma unroll
                         for (int v = 0; v < BV; ++v) {
-#pragma unroll
-                            for (int k = 0; k < BKQ; ++k) {
-                                const bool on = hm[v] != 0u;
-                                const int j = on ? __ffs(hm[v]) - 1 : 0;
-                                hm[v] &= hm[v] - 1u;
-                                const int srcL = gbase + j;
-                                const int c = __shfl(mc[v], srcL, 64);
-                                lw[v][k] = __shfl(ml[v], srcL, 64);
-                                cu[v][k] = on ? c : -1;   // (a repeat would count as a tie)
-                                jj[v][k] = j;
-                            }
-                            hany |= hm[v];
+                            ld_head(uC[v], dbC[v], a0C[v], a1C[v]);
+                            ld_head(u1[v], db1[v], a01[v], a11[v]);
                         }
 #pragma unroll
-                        for (int v = 0; v < BV; ++v)
+                        for (int v = 0; v < BV; ++v) ld_arc(a0C[v] + l, a1C[v], mcC[v], mlC[v], mrC[v]);
+                        while (uC[0] >= 0) {
+                            int mc1[BV], mr1[BV], a02[BV], a12[BV], u3[BV];
+                            double ml1[BV];
+                            unsigned long long db2[BV];
 #pragma unroll
-                            for (int k = 0; k < BKQ; ++k) {
-                                const unsigned long long t2 =
-                                    dec(ld_wg(&D[(size_t)(cu[v][k] >= 0 ? cu[v][k] : 0) * LB + l]));
-                                du[v][k] = cu[v][k] >= 0 ? t2 : INF_BITS;
+                            for (int v = 0; v < BV; ++v) ld_arc(a01[v] + l, a11[v], mc1[v], ml1[v], mr1[v]);
+#pragma unroll
+                            for (int v = 0; v < BV; ++v) ld_head(u2[v], db2[v], a02[v], a12[v]);
+                            {
+                                const int i3 = take();
+#pragma unroll
+                                for (int v = 0; v < BV; ++v) u3[v] = q_at(i3 + v);
                             }
+                            unsigned long long dub[BV];
+                            int deg[BV], maxd = 0;
 #pragma unroll
-                        for (int v = 0; v < BV; ++v)
+                            for (int v = 0; v < BV; ++v) {
+                                const double k0 = b2d(dec(dbC[v])) + sh;
+                                const bool dirty = is_dirty(dbC[v]);
+                                const bool below = dirty && k0 < bound;
+                                const bool act = EAGER ? dirty && __ballot(below) >> gbase & LBMASK : below;
+                                const bool defer = dirty && !act;
+                                const uint32_t amask = (uint32_t)(__ballot(act) >> gbase) & LBMASK;
+                                const uint32_t dmask = (uint32_t)(__ballot(defer) >> gbase) & LBMASK;
+                                if (l == 0 && dmask) anyF.set(uC[v]);
+                                if (defer) {
+                                    myFar = d2b(k0) < myFar ? d2b(k0) : myFar;
+                                    farAdd = 1;
+                                }
+                                if (act) mark_clean(&D[(size_t)uC[v] * LB + l], dbC[v]);
+                                dub[v] = act ? dec(dbC[v]) : INF_BITS;
+                                deg[v] = amask ? a1C[v] - a0C[v] : 0;          // group-uniform
+                                if (amask && dbg && l == 0) {
+                                    atomicAdd(&ctl->dProcs, 1u);
+                                    atomicAdd(&ctl->dArcs, (unsigned int)deg[v]);
+                                    atomicAdd(&ctl->dLanes, (unsigned int)__popc(amask));
+                                }
+                                maxd = max(maxd, deg[v]);
+                            }
+                            // relax the out-arcs for the dirty lanes below the bound
+                            for (int c0 = 0; c0 < maxd; c0 += LB) {
+                                int mc[BV], mr[BV];
+                                double ml[BV];
 #pragma unroll
-                            for (int k = 0; k < BKQ; ++k) {
-                                if (cu[v][k] < 0 || root[v]) continue;
-                                const double cand = b2d(du[v][k]) + lw[v][k];
-                                const unsigned long long cb = d2b(cand);
-                                mn[v] = cb < mn[v] ? cb : mn[v];
-                                if (dC[v] != INF_BITS && du[v][k] <= dC[v] && cand == b2d(dC[v])) {
-                                    if (du[v][k] < best[v]) {
-                                        best[v] = du[v][k];
-                                        cnt[v] = 1;
-                                        ba[v] = a0C[v] + c0 + jj[v][k];
-                                        bu[v] = cu[v][k];
-                                    } else if (du[v][k] == best[v]) {
-                                        ++cnt[v];
-                                    }
+                                for (int v = 0; v < BV; ++v) {
+                                    mc[v] = mcC[v];
+                                    ml[v] = mlC[v];
+                                    mr[v] = mrC[v];
+                                    if (c0 > 0) ld_arc(a0C[v] + c0 + l, a0C[v] + deg[v], mc[v], ml[v], mr[v]);   // degree > LB
+                                }
+                                const int cn = min(LB, maxd - c0);
+                                uint32_t hacc[BV];      // the chunk's arcs with a hit in some lane
+#pragma unroll
+                                for (int v = 0; v < BV; ++v) hacc[v] = 0u;
+                                for (int t = 0; t < cn; t += BKR) {
+                                    int xs[BV][BKR];
+                                    double ws[BV][BKR];
+                                    unsigned long long dx[BV][BKR];
+#pragma unroll
+                                    for (int v = 0; v < BV; ++v)
+#pragma unroll
+                                        for (int k = 0; k < BKR; ++k) {
+                                            const int srcL = gbase + min(t + k, LB - 1);   // inside the group
+                                            const int c = __shfl(mc[v], srcL, 64);
+                                            ws[v][k] = __shfl(ml[v], srcL, 64);
+                                            xs[v][k] = t + k < cn && c0 + t + k < deg[v] ? c : -1;   // (the chunk's own records)
+                                        }
+#pragma unroll
+                                    for (int v = 0; v < BV; ++v)
+#pragma unroll
+                                        for (int k = 0; k < BKR; ++k)
+                                            dx[v][k] = relax_ld(D, xs[v][k] >= 0 ? xs[v][k] : 0, LB, l);
+#pragma unroll
+                                    for (int v = 0; v < BV; ++v)
+#pragma unroll
+                                        for (int k = 0; k < BKR; ++k) {
+                                            const int x = xs[v][k];
+                                            bool impN = false, impF = false, hit = false;
+                                            if (x >= 0) {
+                                                const double nd = b2d(dub[v]) + ws[v][k];
+                                                const unsigned long long nb = d2b(nd);
+                                                hit = dub[v] != INF_BITS && nb <= dec(dx[v][k]);
+                                                if (nb < dec(dx[v][k])) {
+                                                    relax_min(&D[(size_t)x * LB + l], enc_dirty(nb));
+                                                    const double kx = nd + sh;
+                                                    impN = kx < bound;
+                                                    impF = !impN;
+                                                    if (impF) myFar = d2b(kx) < myFar ? d2b(kx) : myFar;
+                                                }
+                                            }
+                                            const uint64_t bn = __ballot(impN), bf = __ballot(impF);
+                                            if (l == 0) {
+                                                if ((bn >> gbase) & LBMASK) anyC.set(x);
+                                                if ((bf >> gbase) & LBMASK) {
+                                                    anyF.set(x);
+                                                    farAdd = 1;
+                                                }
+                                            }
+                                            if constexpr (HITS) {      // (branch-free: `hits` gates the store below)
+                                                const uint64_t bh = __ballot(hit);
+                                                hacc[v] |= (bh >> gbase) & LBMASK ? 1u << ((t + k) & 31) : 0u;
+                                            }
+                                        }
+                                }
+                                // tight or improving in some lane: the lane that holds the
+                                // arc's record flags its in-arc slot (once per chunk)
+                                if constexpr (HITS) {
+#pragma unroll
+                                    for (int v = 0; v < BV; ++v)
+                                        if (hits && ((hacc[v] >> l) & 1u)) atomicOr(&hb[mr[v] >> 5], 1u << (mr[v] & 31));
                                 }
                             }
-                    }
-                }
 #pragma unroll
-                for (int v = 0; v < BV; ++v) {
-                    const int vv = vC[v];
-                    if (vv < 0 || hvy[v]) continue;
-                    const size_t e = (size_t)vv * LB + l;
-                    const bool bad = !root[v] && mn[v] < dC[v];
-                    if (bad) {
-                        D[e] = enc_dirty(mn[v]);
-                        viol = 1;
-                        DIAG_VIOL(b, vv, l, dC[v], mn[v], 0);
+                            for (int v = 0; v < BV; ++v) {
+                                uC[v] = u1[v]; dbC[v] = db1[v]; a0C[v] = a01[v]; a1C[v] = a11[v];
+                                mcC[v] = mc1[v]; mlC[v] = ml1[v]; mrC[v] = mr1[v];
+                                u1[v] = u2[v]; db1[v] = db2[v]; a01[v] = a02[v]; a11[v] = a12[v];
+                                u2[v] = u3[v];
+                            }
+                        }
+                        if (dbg && l == 0) {
+                            const unsigned long long bz = (unsigned long long)((long long)clock64() - tg0);
+                            atomicMax(&ctl->busyMax, bz);
+                            atomicAdd(&ctl->busySum, bz);
+                        }
+                        if (farAdd) ctl->farAny = 1;
+                        fence_wg();
+                        __syncthreads();
+                        if (tid == 0) {
+                            ctl->qtail = 0;
+                            ctl->qhead = 0;
+                            ctl->htail = 0;
+                            if (dbg) {
+                                atomicAdd(&dbg[16 * b + 12], (int)(ctl->busyMax >> 10));
+                                atomicAdd(&dbg[16 * b + 13], (int)((ctl->busySum / NG) >> 10));
+                                atomicAdd(&dbg[16 * b + 14], qn);
+                                ctl->busyMax = 0;
+                                ctl->busySum = 0;
+                            }
+                        }
+                        ++phases;
+                        __syncthreads();
                     }
-                    const uint32_t bm = (uint32_t)(__ballot(bad) >> gbase) & LBMASK;
-                    if (bm && l == 0) anyC.set(vv);
-                    const bool tree = !root[v] && dC[v] != INF_BITS && ba[v] >= 0;
-                    // ambiguous (see the generic loop below)
-                    const bool ea = !root[v] && dC[v] != INF_BITS && (cnt[v] != 1 || best[v] == dC[v]);
-                    const int hx = tree ? ba[v] : -1;
-                    const bool isSrc = vv == src;
-                    lbl_st(&LBL[e], isSrc ? 1.0 : -1.0, isSrc ? 0 : -1,
-                           ea ? (TIE_AMB | (hx > 0 ? hx : 0)) : hx);
-                    if (!tree) bu[v] = -1;
-                }
-                if (!fullPred) {
-#pragma unroll
-                    for (int v = 0; v < BV; ++v) {
-                        const int p = vC[v] >= 0 && !hvy[v] ? bu[v] : -1;
-                        wave_append(Q, &ctl->qtail, p >= 0 && !clm.test_set(p), p);
+                }   // relaxes
+                if (dbg && tid == 0) ctl->t1 = (long long)clock64();
+                if constexpr (P::relax_part) break;
+                if constexpr (P::label_part) break;      // (the predecessor part ran, PART 5)
+
+                // ================= 2. Bellman check + predecessor pass ===============
+                // (a) every entry must satisfy dist[v] <= dist[u] + w for all in-arcs
+                //     (a violation = an update lost to a concurrent plain store: fix
+                //     it, mark v pending, and go back to phase 1);
+                // (b) igraph sets parent[v] from the first POPPED tight predecessor:
+                //     the tight in-arc with minimum dist[u]; equal minima from distinct
+                //     vertices (or a zero-increment arc) -> the heap decides -> tie
+                //     row (k_exact_rows) if such an entry lies on a target's path.
+                int viol = 0;
+                {
+                    const Bits<GB> anyC = par ? any1 : any0;
+                    // on demand: vertices are claimed in the (empty) far bitmap and
+                    // listed in Q, targets first, then round by round the tree
+                    // parents of the last round's entries in every lane
+                    const Bits<GB> clm = par ? any0 : any1;
+                    // entries of in-degree >= PRED_HEAVY are set aside per round and
+                    // scanned by a whole wave each (its groups split the in-arcs and
+                    // combine by cross-group shuffles): one group on a hub's ~1000
+                    // in-arcs would set the round's length.  List in the LDS beyond
+                    // the bitmaps (free until the label walks), capped by that room.
+                    int* const heavyList = reinterpret_cast<int*>(smem + BCTRL_BYTES + (GB ? 0 : 8 * nwp));
+                    const int stackB = NT * SMAX * 8, bitsB = GB ? 0 : 8 * nwp;
+                    const int hcap = P::pred_part ? pred_heavy_cap(nwp, GB) : min(4096, max(0, stackB - bitsB) / 4);
+                    int lo = 0, hi = n;
+                    // the on-demand pass gathers only the in-arcs the relax flagged (a
+                    // superset of the tight ones); the full pass reads every in-arc
+                    bool filt = false;
+                    if constexpr (P::reads_relax_flags) filt = !fullPred && AHw != nullptr && (as_global(bs.flags)[b] & 2) != 0;
+                    if (!fullPred) {
+                        for (int j = tid; j < g.T; j += NT) {
+                            const int v = g.attached[j];
+                            wave_append(Q, &ctl->qtail, !clm.test_set(v), v);
+                        }
+                        fence_wg();
+                        __syncthreads();
+                        hi = uni(ctl->qtail);
+                        __syncthreads();
                     }
-                }
-#pragma unroll
-                for (int v = 0; v < BV; ++v) {
-                    vC[v] = v1[v]; dC[v] = d1[v]; a0C[v] = a01[v]; a1C[v] = a11[v];
-                    mcC[v] = mc1[v]; mlC[v] = ml1[v];
-                    v1[v] = v2[v]; d1[v] = d2[v]; a01[v] = a02[v]; a11[v] = a12[v];
-                    v2[v] = v3[v];
-                }
-            }
-            {
-                // the round's heavy entries, one wave each
-                fence_wg();
-                __syncthreads();
-                const int nh = min(uni(ctl->htail), hcap);
-                constexpr int GPW = 64 / LB;
-                const int wv = tid >> 6, NW = NT >> 6, gw = (tid & 63) / LB;
-                for (int h = wv; h < nh; h += NW) {
-                    const int vv = __builtin_amdgcn_readfirstlane(ld_wg(&heavyList[h]));
-                    const unsigned long long dv = dec(ld_wg(&D[(size_t)vv * LB + l]));
-                    const int a0 = undirected ? g.rowPtr[vv] : g.inPtr[vv];
-                    const int a1 = undirected ? g.rowPtr[vv + 1] : g.inPtr[vv + 1];
-                    const int deg = a1 - a0;
-                    const bool root = vv == src || src < 0;
-                    unsigned long long best = INF_BITS, mn = INF_BITS;
-                    int cnt = 0, ba = -1, bu = -1;
-                    for (int c0 = gw * LB; c0 < deg; c0 += GPW * LB) {
-                        int mc;
-                        double ml;
-                        {
-                            const int a = a0 + c0 + l;
-                            bool ok = a < a1;
+                    while (lo < hi) {
+                        // the relax loop's three-stage pipeline (BV list entries per
+                        // group and stride): the group's lanes hold one in-arc record
+                        // per entry (lane l: in-arc a0 + l, one coalesced read), the
+                        // scan takes the tails by cross-lane reads, so an entry's
+                        // chain is its BKQ-wide dist gathers.  Records of the next
+                        // stride, dist lines + in-arc ranges of the one after, list
+                        // entries of the third are in flight meanwhile.
+                        const int S = NG * BV;
+                        auto item = [&](int i) { return i < hi ? (fullPred ? i : ld_wg(&Q[i])) : -1; };
+                        auto ld_head = [&](int vv, unsigned long long& d, int& r0, int& r1) {
+                            const int vc = vv >= 0 ? vv : 0;
+                            const unsigned long long d0 = dec(ld_wg(&D[(size_t)vc * LB + l]));
+                            const int x0 = undirected ? g.rowPtr[vc] : g.inPtr[vc];
+                            const int x1 = undirected ? g.rowPtr[vc + 1] : g.inPtr[vc + 1];
+                            d = vv >= 0 ? d0 : INF_BITS;
+                            r0 = vv >= 0 ? x0 : 0;
+                            r1 = vv >= 0 ? x1 : 0;
+                        };
+                        // (filtered pass: an in-arc the relax did not flag reads as absent
+                        // -- its flag bit is loaded beside its record, one or two words
+                        // per group)
+                        auto ld_rec = [&](int a, int aEnd, int& c, double& w) {
+                            bool ok = a < aEnd;
                             const int ac = ok ? a : 0;
                             if (filt) ok = ok && ((AHw[ac >> 5] >> (ac & 31)) & 1u) != 0;
                             if (undirected) {
                                 const Arc A = g.arcs[ac];
-                                mc = A.col;
-                                ml = A.lat;
+                                c = A.col;
+                                w = A.lat;
                             } else {
-                                mc = g.inCol[ac];
-                                ml = g.inLat[ac];
+                                c = g.inCol[ac];
+                                w = g.inLat[ac];
                             }
-                            mc = ok ? mc : -1;
+                            c = ok ? c : -1;
+                        };
+                        int v0 = lo + gid * BV;
+                        int vC[BV], v1[BV], v2[BV], a0C[BV], a1C[BV], a01[BV], a11[BV], mcC[BV];
+                        unsigned long long dC[BV], d1[BV];
+                        double mlC[BV];
+#pragma unroll
+                        for (int v = 0; v < BV; ++v) {
+                            vC[v] = item(v0 + v);
+                            v1[v] = item(v0 + S + v);
+                            v2[v] = item(v0 + 2 * S + v);
                         }
-                        // (the same mask walk as the groups' scan, per wave chunk)
-                        uint32_t hm = (uint32_t)(__ballot(mc >= 0) >> gbase) & LBMASK;
-                        if (dbg && !fullPred && l == 0 && hm) atomicAdd(&ctl->dGath, (unsigned int)__popc(hm));
-                        while (hm) {
-                            int cu[BKQ], jj[BKQ];
-                            double lw[BKQ];
-                            unsigned long long du[BKQ];
 #pragma unroll
-                            for (int k = 0; k < BKQ; ++k) {
-                                const bool on = hm != 0u;
-                                const int j = on ? __ffs(hm) - 1 : 0;
-                                hm &= hm - 1u;
-                                const int srcL = gbase + j;
-                                const int c = __shfl(mc, srcL, 64);
-                                lw[k] = __shfl(ml, srcL, 64);
-                                cu[k] = on ? c : -1;
-                                jj[k] = j;
-                            }
+                        for (int v = 0; v < BV; ++v) {
+                            ld_head(vC[v], dC[v], a0C[v], a1C[v]);
+                            ld_head(v1[v], d1[v], a01[v], a11[v]);
+                        }
 #pragma unroll
-                            for (int k = 0; k < BKQ; ++k) {
-                                const unsigned long long t2 =
-                                    dec(ld_wg(&D[(size_t)(cu[k] >= 0 ? cu[k] : 0) * LB + l]));
-                                du[k] = cu[k] >= 0 ? t2 : INF_BITS;
-                            }
+                        for (int v = 0; v < BV; ++v) ld_rec(a0C[v] + l, a1C[v], mcC[v], mlC[v]);
+                        for (; v0 < hi; v0 += S) {
+                            int mc1[BV], a02[BV], a12[BV], v3[BV];
+                            double ml1[BV];
+                            unsigned long long d2[BV];
 #pragma unroll
-                            for (int k = 0; k < BKQ; ++k) {
-                                if (cu[k] < 0 || root) continue;
-                                const double cand = b2d(du[k]) + lw[k];
-                                const unsigned long long cb = d2b(cand);
-                                mn = cb < mn ? cb : mn;
-                                if (dv != INF_BITS && du[k] <= dv && cand == b2d(dv)) {
-                                    if (du[k] < best) {
-                                        best = du[k];
-                                        cnt = 1;
-                                        ba = a0 + c0 + jj[k];
-                                        bu = cu[k];
-                                    } else if (du[k] == best) {
-                                        ++cnt;
+                            for (int v = 0; v < BV; ++v) ld_rec(a01[v] + l, a11[v], mc1[v], ml1[v]);
+#pragma unroll
+                            for (int v = 0; v < BV; ++v) ld_head(v2[v], d2[v], a02[v], a12[v]);
+#pragma unroll
+                            for (int v = 0; v < BV; ++v) v3[v] = item(v0 + 3 * S + v);
+                            bool root[BV], hvy[BV];
+                            unsigned long long best[BV], mn[BV];
+                            int cnt[BV], ba[BV], bu[BV], deg[BV], maxd = 0;
+#pragma unroll
+                            for (int v = 0; v < BV; ++v) {
+                                root[v] = vC[v] == src || src < 0;
+                                best[v] = INF_BITS;
+                                mn[v] = INF_BITS;
+                                cnt[v] = 0;
+                                ba[v] = -1;
+                                bu[v] = -1;
+                                deg[v] = vC[v] >= 0 ? a1C[v] - a0C[v] : 0;   // group-uniform
+                                hvy[v] = false;
+                                if (dbg && !fullPred && l == 0 && deg[v]) atomicAdd(&ctl->dClaim, (unsigned int)deg[v]);
+                                if (deg[v] >= PRED_HEAVY) {                   // -> the round's wave pass
+                                    int slot = 0;
+                                    if (l == 0) slot = atomicAdd(&ctl->htail, 1);
+                                    slot = __shfl(slot, gbase, 64);
+                                    if (slot < hcap) {
+                                        if (l == 0) heavyList[slot] = vC[v];
+                                        hvy[v] = true;
+                                        deg[v] = 0;
                                     }
                                 }
+                                maxd = max(maxd, deg[v]);
+                            }
+                            for (int c0 = 0; c0 < maxd; c0 += LB) {
+                                int mc[BV];
+                                double ml[BV];
+#pragma unroll
+                                for (int v = 0; v < BV; ++v) {
+                                    mc[v] = mcC[v];
+                                    ml[v] = mlC[v];
+                                    if (c0 > 0) ld_rec(a0C[v] + c0 + l, a0C[v] + deg[v], mc[v], ml[v]);
+                                }
+                                // the chunk's records to gather: those present (in the
+                                // filtered pass, flagged), as a mask over the group's lanes;
+                                // the gather rounds walk its set bits in in-list order
+                                uint32_t hm[BV], hany = 0u;
+#pragma unroll
+                                for (int v = 0; v < BV; ++v) {
+                                    const int rem = deg[v] - c0;
+                                    const uint32_t dm = rem >= LB ? LBMASK : rem > 0 ? (1u << (rem & 31)) - 1u : 0u;
+                                    hm[v] = (uint32_t)(__ballot(mc[v] >= 0) >> gbase) & dm;
+                                    if (dbg && !fullPred && l == 0 && hm[v]) atomicAdd(&ctl->dGath, (unsigned int)__popc(hm[v]));
+                                    hany |= hm[v];
+                                }
+                                while (hany) {
+                                    int cu[BV][BKQ], jj[BV][BKQ];
+                                    double lw[BV][BKQ];
+                                    unsigned long long du[BV][BKQ];
+                                    hany = 0u;
+#pragma unroll
+                                    for (int v = 0; v < BV; ++v) {
+#pragma unroll
+                                        for (int k = 0; k < BKQ; ++k) {
+                                            const bool on = hm[v] != 0u;
+                                            const int j = on ? __ffs(hm[v]) - 1 : 0;
+                                            hm[v] &= hm[v] - 1u;
+                                            const int srcL = gbase + j;
+                                            const int c = __shfl(mc[v], srcL, 64);
+                                            lw[v][k] = __shfl(ml[v], srcL, 64);
+                                            cu[v][k] = on ? c : -1;   // (a repeat would count as a tie)
+                                            jj[v][k] = j;
+                                        }
+                                        hany |= hm[v];
+                                    }
+#pragma unroll
+                                    for (int v = 0; v < BV; ++v)
+#pragma unroll
+                                        for (int k = 0; k < BKQ; ++k) {
+                                            const unsigned long long t2 =
+                                                dec(ld_wg(&D[(size_t)(cu[v][k] >= 0 ? cu[v][k] : 0) * LB + l]));
+                                            du[v][k] = cu[v][k] >= 0 ? t2 : INF_BITS;
+                                        }
+#pragma unroll
+                                    for (int v = 0; v < BV; ++v)
+#pragma unroll
+                                        for (int k = 0; k < BKQ; ++k) {
+                                            if (cu[v][k] < 0 || root[v]) continue;
+                                            const double cand = b2d(du[v][k]) + lw[v][k];
+                                            const unsigned long long cb = d2b(cand);
+                                            mn[v] = cb < mn[v] ? cb : mn[v];
+                                            if (dC[v] != INF_BITS && du[v][k] <= dC[v] && cand == b2d(dC[v])) {
+                                                if (du[v][k] < best[v]) {
+                                                    best[v] = du[v][k];
+                                                    cnt[v] = 1;
+                                                    ba[v] = a0C[v] + c0 + jj[v][k];
+                                                    bu[v] = cu[v][k];
+                                                } else if (du[v][k] == best[v]) {
+                                                    ++cnt[v];
+                                                }
+                                            }
+                                        }
+                                }
+                            }
+#pragma unroll
+                            for (int v = 0; v < BV; ++v) {
+                                const int vv = vC[v];
+                                if (vv < 0 || hvy[v]) continue;
+                                const size_t e = (size_t)vv * LB + l;
+                                const bool bad = !root[v] && mn[v] < dC[v];
+                                if (bad) {
+                                    D[e] = enc_dirty(mn[v]);
+                                    viol = 1;
+                                    DIAG_VIOL(b, vv, l, dC[v], mn[v], 0);
+                                }
+                                const uint32_t bm = (uint32_t)(__ballot(bad) >> gbase) & LBMASK;
+                                if (bm && l == 0) anyC.set(vv);
+                                const bool tree = !root[v] && dC[v] != INF_BITS && ba[v] >= 0;
+                                // ambiguous (see the generic loop below)
+                                const bool ea = !root[v] && dC[v] != INF_BITS && (cnt[v] != 1 || best[v] == dC[v]);
+                                const int hx = tree ? ba[v] : -1;
+                                const bool isSrc = vv == src;
+                                lbl_st(&LBL[e], isSrc ? 1.0 : -1.0, isSrc ? 0 : -1,
+                                       ea ? (TIE_AMB | (hx > 0 ? hx : 0)) : hx);
+                                if (!tree) bu[v] = -1;
+                            }
+                            if (!fullPred) {
+#pragma unroll
+                                for (int v = 0; v < BV; ++v) {
+                                    const int p = vC[v] >= 0 && !hvy[v] ? bu[v] : -1;
+                                    wave_append(Q, &ctl->qtail, p >= 0 && !clm.test_set(p), p);
+                                }
+                            }
+#pragma unroll
+                            for (int v = 0; v < BV; ++v) {
+                                vC[v] = v1[v]; dC[v] = d1[v]; a0C[v] = a01[v]; a1C[v] = a11[v];
+                                mcC[v] = mc1[v]; mlC[v] = ml1[v];
+                                v1[v] = v2[v]; d1[v] = d2[v]; a01[v] = a02[v]; a11[v] = a12[v];
+                                v2[v] = v3[v];
                             }
                         }
-                    }
-                    // combine the groups' scans (lane l of every group holds
-                    // source l): counts of equal minima add up, so an entry is
-                    // ambiguous exactly as after one sequential scan
-                    for (int o = LB; o < 64; o <<= 1) {
-                        const unsigned long long ob = __shfl_xor(best, o, 64), om = __shfl_xor(mn, o, 64);
-                        const int oc = __shfl_xor(cnt, o, 64), oa = __shfl_xor(ba, o, 64), ou = __shfl_xor(bu, o, 64);
-                        mn = om < mn ? om : mn;
-                        if (ob < best) {
-                            best = ob; cnt = oc; ba = oa; bu = ou;
-                        } else if (ob == best && ob != INF_BITS) {
-                            cnt += oc;
-                            if (oa >= 0 && (ba < 0 || oa < ba)) { ba = oa; bu = ou; }
+                        {
+                            // the round's heavy entries, one wave each
+                            fence_wg();
+                            __syncthreads();
+                            const int nh = min(uni(ctl->htail), hcap);
+                            constexpr int GPW = 64 / LB;
+                            const int wv = tid >> 6, NW = NT >> 6, gw = (tid & 63) / LB;
+                            for (int h = wv; h < nh; h += NW) {
+                                const int vv = __builtin_amdgcn_readfirstlane(ld_wg(&heavyList[h]));
+                                const unsigned long long dv = dec(ld_wg(&D[(size_t)vv * LB + l]));
+                                const int a0 = undirected ? g.rowPtr[vv] : g.inPtr[vv];
+                                const int a1 = undirected ? g.rowPtr[vv + 1] : g.inPtr[vv + 1];
+                                const int deg = a1 - a0;
+                                const bool root = vv == src || src < 0;
+                                unsigned long long best = INF_BITS, mn = INF_BITS;
+                                int cnt = 0, ba = -1, bu = -1;
+                                for (int c0 = gw * LB; c0 < deg; c0 += GPW * LB) {
+                                    int mc;
+                                    double ml;
+                                    {
+                                        const int a = a0 + c0 + l;
+                                        bool ok = a < a1;
+                                        const int ac = ok ? a : 0;
+                                        if (filt) ok = ok && ((AHw[ac >> 5] >> (ac & 31)) & 1u) != 0;
+                                        if (undirected) {
+                                            const Arc A = g.arcs[ac];
+                                            mc = A.col;
+                                            ml = A.lat;
+                                        } else {
+                                            mc = g.inCol[ac];
+                                            ml = g.inLat[ac];
+                                        }
+                                        mc = ok ? mc : -1;
+                                    }
+                                    // (the same mask walk as the groups' scan, per wave chunk)
+                                    uint32_t hm = (uint32_t)(__ballot(mc >= 0) >> gbase) & LBMASK;
+                                    if (dbg && !fullPred && l == 0 && hm) atomicAdd(&ctl->dGath, (unsigned int)__popc(hm));
+                                    while (hm) {
+                                        int cu[BKQ], jj[BKQ];
+                                        double lw[BKQ];
+                                        unsigned long long du[BKQ];
+#pragma unroll
+                                        for (int k = 0; k < BKQ; ++k) {
+                                            const bool on = hm != 0u;
+                                            const int j = on ? __ffs(hm) - 1 : 0;
+                                            hm &= hm - 1u;
+                                            const int srcL = gbase + j;
+                                            const int c = __shfl(mc, srcL, 64);
+                                            lw[k] = __shfl(ml, srcL, 64);
+                                            cu[k] = on ? c : -1;
+                                            jj[k] = j;
+                                        }
+#pragma unroll
+                                        for (int k = 0; k < BKQ; ++k) {
+                                            const unsigned long long t2 =
+                                                dec(ld_wg(&D[(size_t)(cu[k] >= 0 ? cu[k] : 0) * LB + l]));
+                                            du[k] = cu[k] >= 0 ? t2 : INF_BITS;
+                                        }
+#pragma unroll
+                                        for (int k = 0; k < BKQ; ++k) {
+                                            if (cu[k] < 0 || root) continue;
+                                            const double cand = b2d(du[k]) + lw[k];
+                                            const unsigned long long cb = d2b(cand);
+                                            mn = cb < mn ? cb : mn;
+                                            if (dv != INF_BITS && du[k] <= dv && cand == b2d(dv)) {
+                                                if (du[k] < best) {
+                                                    best = du[k];
+                                                    cnt = 1;
+                                                    ba = a0 + c0 + jj[k];
+                                                    bu = cu[k];
+                                                } else if (du[k] == best) {
+                                                    ++cnt;
+                                                }
+                                            }
+                                        }
+                                    }
+                                }
+                                // combine the groups' scans (lane l of every group holds
+                                // source l): counts of equal minima add up, so an entry is
+                                // ambiguous exactly as after one sequential scan
+                                for (int o = LB; o < 64; o <<= 1) {
+                                    const unsigned long long ob = __shfl_xor(best, o, 64), om = __shfl_xor(mn, o, 64);
+                                    const int oc = __shfl_xor(cnt, o, 64), oa = __shfl_xor(ba, o, 64), ou = __shfl_xor(bu, o, 64);
+                                    mn = om < mn ? om : mn;
+                                    if (ob < best) {
+                                        best = ob; cnt = oc; ba = oa; bu = ou;
+                                    } else if (ob == best && ob != INF_BITS) {
+                                        cnt += oc;
+                                        if (oa >= 0 && (ba < 0 || oa < ba)) { ba = oa; bu = ou; }
+                                    }
+                                }
+                                const size_t e = (size_t)vv * LB + l;
+                                const bool bad = !root && mn < dv;
+                                if (bad && gw == 0) {
+                                    D[e] = enc_dirty(mn);
+                                    viol = 1;
+                                    DIAG_VIOL(b, vv, l, dv, mn, 1);
+                                }
+                                const uint32_t bm = (uint32_t)(__ballot(bad) >> gbase) & LBMASK;
+                                if (bm && l == 0 && gw == 0) anyC.set(vv);
+                                const bool tree = !root && dv != INF_BITS && ba >= 0;
+                                const bool ea = !root && dv != INF_BITS && (cnt != 1 || best == dv);
+                                const int hx = tree ? ba : -1;
+                                if (gw == 0) {
+                                    const bool isSrc = vv == src;
+                                    lbl_st(&LBL[e], isSrc ? 1.0 : -1.0, isSrc ? 0 : -1,
+                                           ea ? (TIE_AMB | (hx > 0 ? hx : 0)) : hx);
+                                }
+                                if (!fullPred) {
+                                    const int p = tree ? bu : -1;
+                                    wave_append(Q, &ctl->qtail, gw == 0 && p >= 0 && !clm.test_set(p), p);
+                                }
+                            }
+                            fence_wg();
+                            __syncthreads();
+                            if (tid == 0) ctl->htail = 0;   // (every thread read it before the barrier)
                         }
-                    }
-                    const size_t e = (size_t)vv * LB + l;
-                    const bool bad = !root && mn < dv;
-                    if (bad && gw == 0) {
-                        D[e] = enc_dirty(mn);
-                        viol = 1;
-                        DIAG_VIOL(b, vv, l, dv, mn, 1);
-                    }
-                    const uint32_t bm = (uint32_t)(__ballot(bad) >> gbase) & LBMASK;
-                    if (bm && l == 0 && gw == 0) anyC.set(vv);
-                    const bool tree = !root && dv != INF_BITS && ba >= 0;
-                    const bool ea = !root && dv != INF_BITS && (cnt != 1 || best == dv);
-                    const int hx = tree ? ba : -1;
-                    if (gw == 0) {
-                        const bool isSrc = vv == src;
-                        lbl_st(&LBL[e], isSrc ? 1.0 : -1.0, isSrc ? 0 : -1,
-                               ea ? (TIE_AMB | (hx > 0 ? hx : 0)) : hx);
+                        if (fullPred) break;
+                        fence_wg();
+                        __syncthreads();
+                        lo = hi;
+                        hi = uni(ctl->qtail);
+                        __syncthreads();
                     }
                     if (!fullPred) {
-                        const int p = tree ? bu : -1;
-                        wave_append(Q, &ctl->qtail, gw == 0 && p >= 0 && !clm.test_set(p), p);
+                        for (int w = tid; w < nwp; w += NT) clm.st(w, 0u);
+                        if (tid == 0) ctl->qtail = 0;
                     }
                 }
+                if (viol) ctl->changed = 1;
+                if (viol) DIAG_WHY(attempt ? 4u : 2u);
                 fence_wg();
                 __syncthreads();
-                if (tid == 0) ctl->htail = 0;   // (every thread read it before the barrier)
-            }
-            if (fullPred) break;
-            fence_wg();
-            __syncthreads();
-            lo = hi;
-            hi = uni(ctl->qtail);
-            __syncthreads();
-            }
-            if (!fullPred) {
-                for (int w = tid; w < nwp; w += NT) clm.st(w, 0u);
-                if (tid == 0) ctl->qtail = 0;
-            }
-        }
-        if (viol) ctl->changed = 1;
-        if (viol) DIAG_WHY(attempt ? 4u : 2u);
-        fence_wg();
-        __syncthreads();
-        const int anyViol = uni(ctl->changed);
-        __syncthreads();
-        if (tid == 0) {
-            ctl->changed = 0;
-            ctl->ambMask = 0u;
-        }
-        __syncthreads();
-        if (!anyViol || failed) break;
-        if constexpr (PT == 2) {   // no relaxation here to repair with: exact path
-            failed = true;
-            break;
-        }
-        ++repairs;
-        }   // verification loop
-        if constexpr (PT == 1) {
-            // the batch's in-arc flags, LDS -> HBM (bit 1 of the flag word: written)
-            if constexpr (HITS)
-                if (hits) {
-                    fence_wg();
-                    __syncthreads();
-                    const uint4* const H4 = reinterpret_cast<const uint4*>(hb);
-                    uint4* const G4 = reinterpret_cast<uint4*>(AHw);
-                    const int cnt16 = (int)(bs.mStride >> 7);
-                    for (int i = tid; i < cnt16; i += NT) G4[i] = H4[i];
+                const int anyViol = uni(ctl->changed);
+                __syncthreads();
+                if (tid == 0) {
+                    ctl->changed = 0;
+                    ctl->ambMask = 0u;
                 }
-            if (tid == 0) as_global(bs.flags)[b] = (failed ? 1 : 0) | (hits ? 2 : 0);
-            break;
-        }
-        if (dbg && tid == 0) ctl->t2 = (long long)clock64();
-        if constexpr (PRED) {
-            // the one value that crosses to the label part: a violation fails the batch
-            if (tid == 0 && failed) as_global(bs.flags)[b] |= 1;
-            break;
-        }
+                __syncthreads();
+                if (!anyViol || failed) break;
+                if constexpr (!P::relaxes) {   // no relaxation here to repair with: exact path
+                    failed = true;
+                    break;
+                }
+                ++repairs;
+            }   // verification loop
+            if constexpr (P::relax_part) {
+                if constexpr (HITS)
+                    if (hits) flush_hits<NT>(hb, AHw, bs.mStride, tid);
+                if (tid == 0) as_global(bs.flags)[b] = (failed ? 1 : 0) | (hits ? 2 : 0);
+                break;
+            }
+            if (dbg && tid == 0) ctl->t2 = (long long)clock64();
+            if constexpr (P::pred_part) {
+                // the one value that crosses to the label part: a violation fails the batch
+                if (tid == 0 && failed) as_global(bs.flags)[b] |= 1;
+                break;
+            }
 
-        // ================= 3. labels on demand + row writer ==================
-        // Only entries on some target's path need hops and reliability (27%
-        // of the entries at C4).  Each lane resolves a target by walking its
-        // predecessor chain up to the first entry with known labels (at the
-        // latest the source: hops 0, rel 1) and unwinding the walk:
-        // hops[x] = hops[p] + 1, rel[x] = rel[p] * r(p, x) -- the reference's
-        // left fold (topology.c:1430, :1499) in path order, exactly.  Unwound
-        // entries keep their labels for later walks of the same lane; each
-        // label is written once with the only value the fold can give, so a
-        // racing reader sees a complete pair (H >= 0 and R >= 0) or an
-        // unresolved entry and walks on.  The walk stack holds SMAX
-        // (entry, arc) pairs per thread in LDS (the relax bitmaps are dead);
-        // a longer chain is resolved from the top, SMAX levels at a time.
-        // An ambiguous entry (TIE_AMB) on a walked chain makes the row a tie
-        // row; ambiguous entries off every target path never matter.  Very
-        // deep trees (a walk over WALK_BUDGET steps: restarts cost
-        // O(depth^2 / SMAX)) switch to Gauss-Seidel sweeps over all entries
-        // and a second writer pass.
-        // latency floor: the lane's own source must sit at distance exactly 0
-        // in the array its row is written from (latencies are > 0, so only
-        // the source is) -- an array that is not this lane's sends the row to
-        // the exact kernel, never to the table
-        uint32_t relAmb = row >= 0 && dec(ld_wg(&D[(size_t)(src >= 0 ? src : 0) * LB + l])) != 0ull ? 1u : 0u;
-        bool retry = false;
-        for (int pass = 0; pass < 2; ++pass) {
-        bool deep = false;
-        if (!failed && row >= 0) {
-            int2* const stk = reinterpret_cast<int2*>(smem + BCTRL_BYTES);
-            const int T = (int)tab.T;
-            // pass 0: the deep-tree budget; pass 1: only the never-spin net
-            // (every consistent entry is resolved by then)
-            // (32-bit: the [v][LB] entry indices below are 32-bit already)
-            const int stepCap = pass == 0 ? WALK_BUDGET : 4 * n + 64;
-            for (int j = gid; j < T; j += NG) {
-                const int t = g.attached[j];
-                if (t != src) {
-                    const size_t e = (size_t)t * LB + l;
-                    const unsigned long long dt = dec(ld_wg(&D[(size_t)t * LB + l]));
-                    if (dt != INF_BITS) {
-                        // one record per step: an entry's record holds its
-                        // parent arc, the parent's record its labels and the
-                        // next arc up
-                        Lbl cr = lbl_ld(&LBL[e]);
-                        int steps = 0;
-                        int cur = (int)e;
-                        while (!lbl_known(cr)) {
-                            int sp = 0, x = cur, hp = 0;
-                            Lbl xr = cr;
-                            double rp = 0.0;
-                            bool found = false;
-                            while (sp < SMAX) {
-                                const int a = xr.arc;
-                                if (a < 0 || ++steps > stepCap) {
-                                    if (a >= 0 && pass == 0) deep = true;   // -> sweeps
-                                    else { relAmb = 1u; DIAG_WHY(8u); }   // no parent / a cycle: exact path
-                                    sp = 0;
-                                    found = true;
-                                    break;
+            // ================= 3. labels on demand + row writer ==================
+            // Only entries on some target's path need hops and reliability (27%
+            // of the entries at C4).  Each lane resolves a target by walking its
+            // predecessor chain up to the first entry with known labels (at the
+            // latest the source: hops 0, rel 1) and unwinding the walk:
+            // hops[x] = hops[p] + 1, rel[x] = rel[p] * r(p, x) -- the reference's
+            // left fold (topology.c:1430, :1499) in path order, exactly.  Unwound
+            // entries keep their labels for later walks of the same lane; each
+            // label is written once with the only value the fold can give, so a
+            // racing reader sees a complete pair (H >= 0 and R >= 0) or an
+            // unresolved entry and walks on.  The walk stack holds SMAX
+            // (entry, arc) pairs per thread in LDS (the relax bitmaps are dead);
+            // a longer chain is resolved from the top, SMAX levels at a time.
+            // An ambiguous entry (TIE_AMB) on a walked chain makes the row a tie
+            // row; ambiguous entries off every target path never matter.  Very
+            // deep trees (a walk over WALK_BUDGET steps: restarts cost
+            // O(depth^2 / SMAX)) switch to Gauss-Seidel sweeps over all entries
+            // and a second writer pass.
+            // latency floor: the lane's own source must sit at distance exactly 0
+            // in the array its row is written from (latencies are > 0, so only
+            // the source is) -- an array that is not this lane's sends the row to
+            // the exact kernel, never to the table
+            uint32_t relAmb = row >= 0 && dec(ld_wg(&D[(size_t)(src >= 0 ? src : 0) * LB + l])) != 0ull ? 1u : 0u;
+            bool retry = false;
+            for (int pass = 0; pass < 2; ++pass) {
+                bool deep = false;
+                if (!failed && row >= 0) {
+                    int2* const stk = reinterpret_cast<int2*>(smem + BCTRL_BYTES);
+                    const int T = (int)tab.T;
+                    // pass 0: the deep-tree budget; pass 1: only the never-spin net
+                    // (every consistent entry is resolved by then)
+                    // (32-bit: the [v][LB] entry indices below are 32-bit already)
+                    const int stepCap = pass == 0 ? WALK_BUDGET : 4 * n + 64;
+                    for (int j = gid; j < T; j += NG) {
+                        const int t = g.attached[j];
+                        if (t != src) {
+                            const size_t e = (size_t)t * LB + l;
+                            const unsigned long long dt = dec(ld_wg(&D[(size_t)t * LB + l]));
+                            if (dt != INF_BITS) {
+                                // one record per step: an entry's record holds its
+                                // parent arc, the parent's record its labels and the
+                                // next arc up
+                                Lbl cr = lbl_ld(&LBL[e]);
+                                int steps = 0;
+                                int cur = (int)e;
+                                while (!lbl_known(cr)) {
+                                    int sp = 0, x = cur, hp = 0;
+                                    Lbl xr = cr;
+                                    double rp = 0.0;
+                                    bool found = false;
+                                    while (sp < SMAX) {
+                                        const int a = xr.arc;
+                                        if (a < 0 || ++steps > stepCap) {
+                                            if (a >= 0 && pass == 0) deep = true;   // -> sweeps
+                                            else { relAmb = 1u; DIAG_WHY(8u); }   // no parent / a cycle: exact path
+                                            sp = 0;
+                                            found = true;
+                                            break;
+                                        }
+                                        relAmb |= (uint32_t)((a & TIE_AMB) != 0);
+                                        if (a & TIE_AMB) DIAG_WHY(16u);
+                                        stk[sp * NT + tid] = make_int2(x, a);
+                                        ++sp;
+                                        const int pe = g.inCol[a & ~TIE_AMB] * LB + l;
+                                        const Lbl pr = lbl_ld(&LBL[pe]);
+                                        if (lbl_known(pr)) {
+                                            hp = pr.hops;
+                                            rp = pr.rel;
+                                            found = true;
+                                            break;
+                                        }
+                                        x = pe;
+                                        xr = pr;
+                                    }
+                                    if (!found) {           // chain longer than SMAX: its top first
+                                        cur = x;
+                                        cr = xr;
+                                        continue;
+                                    }
+                                    for (int i = sp - 1; i >= 0; --i) {
+                                        const int2 sx = stk[i * NT + tid];
+                                        hp += 1;
+                                        rp = rp * g.inRel[sx.y & ~TIE_AMB];
+                                        lbl_st(&LBL[sx.x], rp, hp, sx.y);
+                                    }
+                                    if (sp == 0) break;     // gave up (deep / inconsistent)
+                                    if (cur == (int)e) break;
+                                    cur = (int)e;           // top segment resolved: walk again
+                                    cr = lbl_ld(&LBL[e]);
                                 }
-                                relAmb |= (uint32_t)((a & TIE_AMB) != 0);
-                                if (a & TIE_AMB) DIAG_WHY(16u);
-                                stk[sp * NT + tid] = make_int2(x, a);
-                                ++sp;
-                                const int pe = g.inCol[a & ~TIE_AMB] * LB + l;
-                                const Lbl pr = lbl_ld(&LBL[pe]);
-                                if (lbl_known(pr)) {
-                                    hp = pr.hops;
-                                    rp = pr.rel;
-                                    found = true;
-                                    break;
-                                }
-                                x = pe;
-                                xr = pr;
                             }
-                            if (!found) {           // chain longer than SMAX: its top first
-                                cur = x;
-                                cr = xr;
-                                continue;
-                            }
-                            for (int i = sp - 1; i >= 0; --i) {
-                                const int2 sx = stk[i * NT + tid];
-                                hp += 1;
-                                rp = rp * g.inRel[sx.y & ~TIE_AMB];
-                                lbl_st(&LBL[sx.x], rp, hp, sx.y);
-                            }
-                            if (sp == 0) break;     // gave up (deep / inconsistent)
-                            if (cur == (int)e) break;
-                            cur = (int)e;           // top segment resolved: walk again
-                            cr = lbl_ld(&LBL[e]);
                         }
                     }
                 }
+                if (deep) ctl->changed = 1;
+                if (deep) DIAG_WHY(32u);
+                fence_wg();
+                __syncthreads();
+                const int anyDeep = uni(ctl->changed);
+                __syncthreads();
+                if (tid == 0) ctl->changed = 0;
+                __syncthreads();
+                if (!anyDeep) break;
+                if (!fullPred) {         // the sweeps read every entry's parent
+                    retry = true;
+                    break;
+                }
+                // Gauss-Seidel: every tree entry whose parent has labels takes them
+                // (+1, * r) until a sweep changes nothing (<= depth sweeps).  These
+                // entries were not walked, so an ambiguous one sends its row to the
+                // exact path (conservative).  Cycles of zero-increment parents stay
+                // unresolved and the second pass's walks flag them.
+                for (int sweep = 0; sweep <= n + 1; ++sweep) {
+                    int ch = 0;
+                    for (size_t e = tid; e < NE; e += NT) {
+                        const Lbl er = lbl_ld(&LBL[e]);
+                        const int a = er.arc;
+                        if (a < 0) continue;
+                        const int ll = (int)(e % LB);
+                        const int arc = a & ~TIE_AMB;
+                        const int pe = g.inCol[arc] * LB + ll;
+                        const Lbl pr = lbl_ld(&LBL[pe]);
+                        if (!lbl_known(pr)) continue;
+                        const int hn = pr.hops + 1;
+                        const double rn = pr.rel * g.inRel[arc];
+                        if (er.hops != hn || er.rel != rn) {
+                            lbl_st(&LBL[e], rn, hn, a);
+                            ch = 1;
+                            if (a & TIE_AMB) atomicOr(&ctl->ambMask, 1u << ll);
+                        }
+                    }
+                    if (ch) ctl->changed = 1;
+                    fence_wg();
+                    __syncthreads();
+                    const int any = uni(ctl->changed);
+                    __syncthreads();
+                    if (tid == 0) ctl->changed = 0;
+                    __syncthreads();
+                    if (!any) break;
+                }
+            }   // label passes
+            if (dbg && tid == 0) dbg[16 * b + 2] = (int)(((long long)clock64() - ctl->t2) >> 10);   // walks
+            // ---- row writer: the lanes' rows are written target block by
+            // target block through an LDS tile (the walk stacks' space): a
+            // group holds one target of 16 rows, so direct stores would scatter
+            // 16 rows x 8-32 B per wave instruction; from the tile each wave
+            // stores a run of consecutive columns of one row (non-temporal:
+            // the table is never re-read here)
+            // the label part: a batch that goes to the redo launch (the condition of
+            // the second attempt below, known once the walks are done) writes no row
+            bool redo = false;
+            if constexpr (P::label_part) {
+                if (relAmb) atomicOr(&ctl->ambMask, 1u << l);
+                fence_wg();
+                __syncthreads();
+                const bool tieBuf = tieDesc != nullptr &&
+                                    __builtin_amdgcn_readfirstlane((int)(ld_wg(&tieDesc->req) != nullptr)) != 0;
+                redo = !failed && (retry || (uni((int)ctl->ambMask) != 0 && !tieBuf));
             }
-        }
-        if (deep) ctl->changed = 1;
-        if (deep) DIAG_WHY(32u);
-        fence_wg();
-        __syncthreads();
-        const int anyDeep = uni(ctl->changed);
-        __syncthreads();
-        if (tid == 0) ctl->changed = 0;
-        __syncthreads();
-        if (!anyDeep) break;
-        if (!fullPred) {         // the sweeps read every entry's parent
-            retry = true;
-            break;
-        }
-        // Gauss-Seidel: every tree entry whose parent has labels takes them
-        // (+1, * r) until a sweep changes nothing (<= depth sweeps).  These
-        // entries were not walked, so an ambiguous one sends its row to the
-        // exact path (conservative).  Cycles of zero-increment parents stay
-        // unresolved and the second pass's walks flag them.
-        for (int sweep = 0; sweep <= n + 1; ++sweep) {
-            int ch = 0;
-            for (size_t e = tid; e < NE; e += NT) {
-                const Lbl er = lbl_ld(&LBL[e]);
-                const int a = er.arc;
-                if (a < 0) continue;
-                const int ll = (int)(e % LB);
-                const int arc = a & ~TIE_AMB;
-                const int pe = g.inCol[arc] * LB + ll;
-                const Lbl pr = lbl_ld(&LBL[pe]);
-                if (!lbl_known(pr)) continue;
-                const int hn = pr.hops + 1;
-                const double rn = pr.rel * g.inRel[arc];
-                if (er.hops != hn || er.rel != rn) {
-                    lbl_st(&LBL[e], rn, hn, a);
-                    ch = 1;
-                    if (a & TIE_AMB) atomicOr(&ctl->ambMask, 1u << ll);
+            if (!failed && !retry && !redo) {
+                const int T = (int)tab.T;
+                // (2 x NT entries of 21 B: inside the walk stacks' SMAX x NT x 8 B)
+                double* const tLat = reinterpret_cast<double*>(smem + BCTRL_BYTES);
+                double* const tRel = tLat + 2 * NT;
+                int32_t* const tHop = reinterpret_cast<int32_t*>(tRel + 2 * NT);
+                int32_t* const tPred = tHop + 2 * NT;
+                uint8_t* const tFlg = reinterpret_cast<uint8_t*>(tPred + 2 * NT);
+                const int wl = tid / NG, wc = tid % NG;     // writer: lane (row), column in block
+                const int wrow = P::writes_rows ? laneRow[wl] : -1;
+                const size_t wbase = (size_t)(wrow >= 0 ? wrow - tab.rowStart : 0) * (size_t)tab.T;
+                __syncthreads();                            // walks done: stacks free
+                // WQ targets per group per block, their loads issued branch-free
+                // level by level (vertex id -> dist + label record + vertex
+                // reliability -> parent vertex -> caller id), so WQ dependent
+                // chains are in flight per thread and a block's two barriers are
+                // shared by WQ x NG targets
+                constexpr int WQ = 2;
+                const int BW = WQ * NG;
+                // the lane's own source (1-vertex igraph path [s]: the fold uses
+                // edge (s,s), :1469-1488; the destination factor is skipped, :1457)
+                const bool srcSelf = row >= 0 && g.hasSelf[src >= 0 ? src : 0];
+                const double srcVrel = row >= 0 ? g.vrel[src >= 0 ? src : 0] : 1.0;
+                const double selfL = srcSelf ? 0.0 + g.selfLat[src] : 0.0;
+                const double selfR = srcSelf ? (1.0 * srcVrel) * g.selfRel[src] : 0.0;
+                for (int j0 = 0; j0 < T; j0 += BW) {
+                    int tq[WQ], pq[WQ];
+                    unsigned long long dq[WQ];
+                    Lbl rq[WQ];
+                    double vq[WQ];
+#pragma unroll
+                    for (int q = 0; q < WQ; ++q) {
+                        const int j = j0 + q * NG + gid;
+                        tq[q] = row >= 0 && j < T ? g.attached[j] : -1;
+                    }
+#pragma unroll
+                    for (int q = 0; q < WQ; ++q) {
+                        const int tc = tq[q] >= 0 ? tq[q] : 0;
+                        dq[q] = dec(ld_wg(&D[(size_t)tc * LB + l]));
+                        rq[q] = lbl_ld(&LBL[(size_t)tc * LB + l]);
+                        vq[q] = g.vrel[tc];
+                    }
+#pragma unroll
+                    for (int q = 0; q < WQ; ++q) {
+                        // (an unreachable target's record is not this batch's: its
+                        // arc field is never followed)
+                        const bool reach = tq[q] >= 0 && tq[q] != src && dq[q] != INF_BITS;
+                        const int pa = reach ? rq[q].arc : -1;
+                        const int x = g.inCol[pa >= 0 ? pa & ~TIE_AMB : 0];
+                        pq[q] = pa >= 0 ? x : -1;
+                    }
+                    if (g.oldId) {
+#pragma unroll
+                        for (int q = 0; q < WQ; ++q) {
+                            const int x = g.oldId[pq[q] >= 0 ? pq[q] : 0];   // device id -> caller's id
+                            pq[q] = pq[q] >= 0 ? x : -1;
+                        }
+                    }
+#pragma unroll
+                    for (int q = 0; q < WQ; ++q) {
+                        const int t = tq[q];
+                        double L = 0.0, Rl = 0.0;
+                        int h = -1, pv = -1;
+                        uint8_t f = 0;
+                        if (t >= 0) {
+                            if (t == src) {
+                                if (srcSelf) {
+                                    L = selfL;
+                                    Rl = selfR;
+                                    h = 1;
+                                } else {
+                                    f |= F_NOEDGE;
+                                }
+                            } else if (dq[q] == INF_BITS) {
+                                f |= F_UNREACHABLE;
+                            } else {
+                                L = b2d(dq[q]);
+                                h = rq[q].hops;
+                                pv = pq[q];
+                                if (srcVrel == 1.0 && vq[q] == 1.0)
+                                    Rl = rq[q].rel;
+                                else
+                                    Rl = fold_rel_batch<LB>(g.vrel, g.inRel, g.inCol, LBL, l, src, t, h);
+                                if (L == 0.0) {                 // topology.c:1848-1852
+                                    L = 1.0;
+                                    f |= F_ZEROLAT;
+                                }
+                            }
+                        }
+                        const int ti = l * BW + q * NG + gid;
+                        tLat[ti] = L;
+                        tRel[ti] = Rl;
+                        tHop[ti] = h;
+                        tPred[ti] = pv;
+                        tFlg[ti] = f;
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int q = 0; q < WQ; ++q) {
+                        const int c = j0 + q * NG + wc;
+                        if (wrow >= 0 && c < T) {
+                            const int ti2 = wl * BW + q * NG + wc;
+                            const size_t o = wbase + (size_t)c;
+                            __builtin_nontemporal_store(tLat[ti2], &tab.lat[o]);
+                            __builtin_nontemporal_store(tRel[ti2], &tab.rel[o]);
+                            __builtin_nontemporal_store(tHop[ti2], &tab.hops[o]);
+                            __builtin_nontemporal_store(tFlg[ti2], &tab.flags[o]);
+                            if (tab.pred) __builtin_nontemporal_store(tPred[ti2], &tab.pred[o]);
+                        }
+                    }
+                    __syncthreads();
                 }
             }
-            if (ch) ctl->changed = 1;
-            fence_wg();
-            __syncthreads();
-            const int any = uni(ctl->changed);
-            __syncthreads();
-            if (tid == 0) ctl->changed = 0;
-            __syncthreads();
-            if (!any) break;
-        }
-        }   // label passes
-        if (dbg && tid == 0) dbg[16 * b + 2] = (int)(((long long)clock64() - ctl->t2) >> 10);   // walks
-        // ---- row writer: the lanes' rows are written target block by
-        // target block through an LDS tile (the walk stacks' space): a
-        // group holds one target of 16 rows, so direct stores would scatter
-        // 16 rows x 8-32 B per wave instruction; from the tile each wave
-        // stores a run of consecutive columns of one row (non-temporal:
-        // the table is never re-read here)
-        // the label part: a batch that goes to the redo launch (the condition of
-        // the second attempt below, known once the walks are done) writes no row
-        bool redo = false;
-        if constexpr (LABEL) {
             if (relAmb) atomicOr(&ctl->ambMask, 1u << l);
             fence_wg();
             __syncthreads();
-            const bool tieBuf = tieDesc != nullptr &&
-                                __builtin_amdgcn_readfirstlane((int)(ld_wg(&tieDesc->req) != nullptr)) != 0;
-            redo = !failed && (retry || (uni((int)ctl->ambMask) != 0 && !tieBuf));
-        }
-        if (!failed && !retry && !redo) {
-            const int T = (int)tab.T;
-            // (2 x NT entries of 21 B: inside the walk stacks' SMAX x NT x 8 B)
-            double* const tLat = reinterpret_cast<double*>(smem + BCTRL_BYTES);
-            double* const tRel = tLat + 2 * NT;
-            int32_t* const tHop = reinterpret_cast<int32_t*>(tRel + 2 * NT);
-            int32_t* const tPred = tHop + 2 * NT;
-            uint8_t* const tFlg = reinterpret_cast<uint8_t*>(tPred + 2 * NT);
-            const int wl = tid / NG, wc = tid % NG;     // writer: lane (row), column in block
-            const int wrow = NOTAB ? -1 : laneRow[wl];
-            const size_t wbase = (size_t)(wrow >= 0 ? wrow - tab.rowStart : 0) * (size_t)tab.T;
-            __syncthreads();                            // walks done: stacks free
-            // WQ targets per group per block, their loads issued branch-free
-            // level by level (vertex id -> dist + label record + vertex
-            // reliability -> parent vertex -> caller id), so WQ dependent
-            // chains are in flight per thread and a block's two barriers are
-            // shared by WQ x NG targets
-            constexpr int WQ = 2;
-            const int BW = WQ * NG;
-            // the lane's own source (1-vertex igraph path [s]: the fold uses
-            // edge (s,s), :1469-1488; the destination factor is skipped, :1457)
-            const bool srcSelf = row >= 0 && g.hasSelf[src >= 0 ? src : 0];
-            const double srcVrel = row >= 0 ? g.vrel[src >= 0 ? src : 0] : 1.0;
-            const double selfL = srcSelf ? 0.0 + g.selfLat[src] : 0.0;
-            const double selfR = srcSelf ? (1.0 * srcVrel) * g.selfRel[src] : 0.0;
-            for (int j0 = 0; j0 < T; j0 += BW) {
-                int tq[WQ], pq[WQ];
-                unsigned long long dq[WQ];
-                Lbl rq[WQ];
-                double vq[WQ];
-#pragma unroll
-                for (int q = 0; q < WQ; ++q) {
-                    const int j = j0 + q * NG + gid;
-                    tq[q] = row >= 0 && j < T ? g.attached[j] : -1;
+            // rows whose target paths meet an ambiguous entry (or that hit the
+            // phase cap) go to k_exact_rows; their rows above are rewritten there
+            needMask = failed ? LBMASK : ctl->ambMask;
+            __syncthreads();
+            if (tid == 0) ctl->ambMask = 0u;
+            __syncthreads();
+            // a tie row's export needs every vertex's parent: the full pass --
+            // in line, or (the post kernel, with a deferred-export buffer) by
+            // k_tie_export over the whole GPU after this kernel, so a tie batch
+            // no longer runs a second full pass here (round 6: the c4q post
+            // kernel was 43 vs 31 ms, a tie batch's in-line pass on its tail)
+            const bool deferTie = P::defers_ties && tieDesc != nullptr &&
+                                  __builtin_amdgcn_readfirstlane((int)(ld_wg(&tieDesc->req) != nullptr)) != 0;
+            if constexpr (P::label_part) {
+                if (redo && tid == 0) {      // -> PART 2 over bs.redo, after this kernel
+                    int32_t* const rd = as_global(bs.redo);
+                    rd[REDO_LIST + atomicAdd(&rd[0], 1)] = b;
+                    atomicAdd(&rd[1], 1);
                 }
-#pragma unroll
-                for (int q = 0; q < WQ; ++q) {
-                    const int tc = tq[q] >= 0 ? tq[q] : 0;
-                    dq[q] = dec(ld_wg(&D[(size_t)tc * LB + l]));
-                    rq[q] = lbl_ld(&LBL[(size_t)tc * LB + l]);
-                    vq[q] = g.vrel[tc];
-                }
-#pragma unroll
-                for (int q = 0; q < WQ; ++q) {
-                    // (an unreachable target's record is not this batch's: its
-                    // arc field is never followed)
-                    const bool reach = tq[q] >= 0 && tq[q] != src && dq[q] != INF_BITS;
-                    const int pa = reach ? rq[q].arc : -1;
-                    const int x = g.inCol[pa >= 0 ? pa & ~TIE_AMB : 0];
-                    pq[q] = pa >= 0 ? x : -1;
-                }
-                if (g.oldId) {
-#pragma unroll
-                    for (int q = 0; q < WQ; ++q) {
-                        const int x = g.oldId[pq[q] >= 0 ? pq[q] : 0];   // device id -> caller's id
-                        pq[q] = pq[q] >= 0 ? x : -1;
-                    }
-                }
-#pragma unroll
-                for (int q = 0; q < WQ; ++q) {
-                    const int t = tq[q];
-                    double L = 0.0, Rl = 0.0;
-                    int h = -1, pv = -1;
-                    uint8_t f = 0;
-                    if (t >= 0) {
-                        if (t == src) {
-                            if (srcSelf) {
-                                L = selfL;
-                                Rl = selfR;
-                                h = 1;
-                            } else {
-                                f |= F_NOEDGE;
-                            }
-                        } else if (dq[q] == INF_BITS) {
-                            f |= F_UNREACHABLE;
-                        } else {
-                            L = b2d(dq[q]);
-                            h = rq[q].hops;
-                            pv = pq[q];
-                            if (srcVrel == 1.0 && vq[q] == 1.0)
-                                Rl = rq[q].rel;
-                            else
-                                Rl = fold_rel_batch<LB>(g.vrel, g.inRel, g.inCol, LBL, l, src, t, h);
-                            if (L == 0.0) {                 // topology.c:1848-1852
-                                L = 1.0;
-                                f |= F_ZEROLAT;
-                            }
-                        }
-                    }
-                    const int ti = l * BW + q * NG + gid;
-                    tLat[ti] = L;
-                    tRel[ti] = Rl;
-                    tHop[ti] = h;
-                    tPred[ti] = pv;
-                    tFlg[ti] = f;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int q = 0; q < WQ; ++q) {
-                    const int c = j0 + q * NG + wc;
-                    if (wrow >= 0 && c < T) {
-                        const int ti2 = wl * BW + q * NG + wc;
-                        const size_t o = wbase + (size_t)c;
-                        __builtin_nontemporal_store(tLat[ti2], &tab.lat[o]);
-                        __builtin_nontemporal_store(tRel[ti2], &tab.rel[o]);
-                        __builtin_nontemporal_store(tHop[ti2], &tab.hops[o]);
-                        __builtin_nontemporal_store(tFlg[ti2], &tab.flags[o]);
-                        if (tab.pred) __builtin_nontemporal_store(tPred[ti2], &tab.pred[o]);
-                    }
-                }
-                __syncthreads();
+                needMask = redo ? 0u : needMask;
+                lastFull = false;
+                break;
             }
-        }
-        if (relAmb) atomicOr(&ctl->ambMask, 1u << l);
-        fence_wg();
-        __syncthreads();
-        // rows whose target paths meet an ambiguous entry (or that hit the
-        // phase cap) go to k_exact_rows; their rows above are rewritten there
-        needMask = failed ? LBMASK : ctl->ambMask;
-        __syncthreads();
-        if (tid == 0) ctl->ambMask = 0u;
-        __syncthreads();
-        // a tie row's export needs every vertex's parent: the full pass --
-        // in line, or (the post kernel, with a deferred-export buffer) by
-        // k_tie_export over the whole GPU after this kernel, so a tie batch
-        // no longer runs a second full pass here (round 6: the c4q post
-        // kernel was 43 vs 31 ms, a tie batch's in-line pass on its tail)
-        const bool deferTie = PT == 2 && tieDesc != nullptr &&
-                              __builtin_amdgcn_readfirstlane((int)(ld_wg(&tieDesc->req) != nullptr)) != 0;
-        if constexpr (LABEL) {
-            if (redo && tid == 0) {      // -> PART 2 over bs.redo, after this kernel
-                int32_t* const rd = as_global(bs.redo);
-                rd[REDO_LIST + atomicAdd(&rd[0], 1)] = b;
-                atomicAdd(&rd[1], 1);
-            }
-            needMask = redo ? 0u : needMask;
-            lastFull = false;
+            if (!fullPred && !failed && (retry || (needMask && !deferTie))) continue;
+            lastFull = fullPred;
             break;
-        }
-        if (!fullPred && !failed && (retry || (needMask && !deferTie))) continue;
-        lastFull = fullPred;
-        break;
         }   // attempts
-        if constexpr (PRED) {
-            __syncthreads();
-#ifdef SHDPE_DIAG_WHY
-            if (why) atomicOr(&ctl->dWhy, why);
-            __syncthreads();
-#endif
-            if (dbg && tid == 0) {
-                atomicOr(&dbg[16 * b + 1], (int)ctl->dWhy);
-                dbg[16 * b + 6] = (int)((ctl->t2 - ctl->t1) >> 10);
-                if (bs.predCnt) {       // the on-demand pass's in-arcs: claimed, gathered
-                    atomicAdd(as_global(bs.predCnt), (unsigned long long)ctl->dClaim);
-                    atomicAdd(as_global(bs.predCnt) + 1, (unsigned long long)ctl->dGath);
-                }
-            }
-            __syncthreads();
-            continue;
-        }
-        if constexpr (PT == 1) {
-            __syncthreads();
-            if (dbg && tid == 0) {
-                dbg[16 * b + 0] = phases;
-                dbg[16 * b + 5] = (int)((ctl->t1 - ctl->t0) >> 10);
-                dbg[16 * b + 15] = repairs;
-                atomicAdd(&dbg[16 * b + 4], (int)ctl->dProcs);
-                atomicAdd(&dbg[16 * b + 9], (int)(ctl->dArcs >> 4));
-                atomicAdd(&dbg[16 * b + 10], (int)ctl->dLanes);
-            }
-            __syncthreads();
-            continue;
-        }
-        if (dbg && tid == 0) ctl->t3 = (long long)clock64();
+        if constexpr (P::exports_ties) {
+            if (dbg && tid == 0) ctl->t3 = (long long)clock64();
 
-        // ---- tie export: hand k_exact_rows the final distances, the parents
-        // and the ambiguous entries, so it emulates the heap only until the
-        // last tied predecessor is popped (tie threshold) ----
-        if (needMask && !failed && tieDesc) {
-            // descriptor read from memory here only: as a kernel argument
-            // it cost the hot loops registers (SGPR spills)
-            const TieBuf tie = *tieDesc;
-            // deferred (attempt 0 of the post kernel): the slot records the
-            // request, k_tie_export fills it after this kernel
-            const bool defer = PT == 2 && !lastFull;
-            if (tid < LB) {
-                int sl = -1;
-                if ((needMask >> tid) & 1u) {
-                    sl = atomicAdd(tie.count, 1);
-                    if (sl >= tie.cap) sl = -1;
-                }
-                tieSlot[tid] = sl;
-                tieThr[tid] = 0ull;
-                if (defer && sl >= 0) {       // thread tid < LB is lane tid of group 0
-                    tie.thr[sl] = 0.0;
-                    tie.req[4 * sl + 0] = b;
-                    tie.req[4 * sl + 1] = tid;
-                    tie.req[4 * sl + 2] = src;
-                    tie.req[4 * sl + 3] = *tie.round;
-                }
-            }
-            __syncthreads();
-            const int sl = defer ? -1 : tieSlot[l];
-            unsigned long long thr = 0ull;
-            for (int v = gid; v < n; v += NG) {
-                if (sl < 0) continue;
-                const size_t e = (size_t)v * LB + l;
-                const int pe = lbl_arc(&LBL[e]);
-                const bool am = pe >= 0 && (pe & TIE_AMB);
-                const size_t o = (size_t)sl * (size_t)tie.n + v;
-                tie.D[o] = b2d(dec(ld_wg(&D[(size_t)v * LB + l])));
-                tie.P[o] = pe;
-                if (am) {   // rare: re-derive the tied (minimum tight) predecessor distance
-                    const unsigned long long dv = dec(ld_wg(&D[(size_t)v * LB + l]));
-                    const int a0 = undirected ? g.rowPtr[v] : g.inPtr[v];
-                    const int a1 = undirected ? g.rowPtr[v + 1] : g.inPtr[v + 1];
-                    unsigned long long mt = INF_BITS;
-                    for (int a = a0; a < a1; ++a) {
-                        const int u = undirected ? g.col[a] : g.inCol[a];
-                        const double w = undirected ? g.lat[a] : g.inLat[a];
-                        const unsigned long long du = dec(ld_wg(&D[(size_t)u * LB + l]));
-                        if (du <= dv && d2b(b2d(du) + w) == dv && du < mt) mt = du;
+            // ---- tie export: hand k_exact_rows the final distances, the parents
+            // and the ambiguous entries, so it emulates the heap only until the
+            // last tied predecessor is popped (tie threshold) ----
+            if (needMask && !failed && tieDesc) {
+                // descriptor read from memory here only: as a kernel argument
+                // it cost the hot loops registers (SGPR spills)
+                const TieBuf tie = *tieDesc;
+                // deferred (attempt 0 of the post kernel): the slot records the
+                // request, k_tie_export fills it after this kernel
+                const bool defer = P::defers_ties && !lastFull;
+                if (tid < LB) {
+                    int sl = -1;
+                    if ((needMask >> tid) & 1u) {
+                        sl = atomicAdd(tie.count, 1);
+                        if (sl >= tie.cap) sl = -1;
                     }
-                    if (mt != INF_BITS) thr = mt > thr ? mt : thr;
+                    tieSlot[tid] = sl;
+                    tieThr[tid] = 0ull;
+                    if (defer && sl >= 0) {       // thread tid < LB is lane tid of group 0
+                        tie.thr[sl] = 0.0;
+                        tie.req[4 * sl + 0] = b;
+                        tie.req[4 * sl + 1] = tid;
+                        tie.req[4 * sl + 2] = src;
+                        tie.req[4 * sl + 3] = *tie.round;
+                    }
                 }
+                __syncthreads();
+                const int sl = defer ? -1 : tieSlot[l];
+                unsigned long long thr = 0ull;
+                for (int v = gid; v < n; v += NG) {
+                    if (sl < 0) continue;
+                    const size_t e = (size_t)v * LB + l;
+                    const int pe = lbl_arc(&LBL[e]);
+                    const bool am = pe >= 0 && (pe & TIE_AMB);
+                    const size_t o = (size_t)sl * (size_t)tie.n + v;
+                    tie.D[o] = b2d(dec(ld_wg(&D[(size_t)v * LB + l])));
+                    tie.P[o] = pe;
+                    if (am) {   // rare: re-derive the tied (minimum tight) predecessor distance
+                        const unsigned long long dv = dec(ld_wg(&D[(size_t)v * LB + l]));
+                        const int a0 = undirected ? g.rowPtr[v] : g.inPtr[v];
+                        const int a1 = undirected ? g.rowPtr[v + 1] : g.inPtr[v + 1];
+                        unsigned long long mt = INF_BITS;
+                        for (int a = a0; a < a1; ++a) {
+                            const int u = undirected ? g.col[a] : g.inCol[a];
+                            const double w = undirected ? g.lat[a] : g.inLat[a];
+                            const unsigned long long du = dec(ld_wg(&D[(size_t)u * LB + l]));
+                            if (du <= dv && d2b(b2d(du) + w) == dv && du < mt) mt = du;
+                        }
+                        if (mt != INF_BITS) thr = mt > thr ? mt : thr;
+                    }
+                }
+                if (thr) atomicMax(&tieThr[l], thr);
+                fence_wg();
+                __syncthreads();
+                if (!defer && gid == 0 && sl >= 0) tie.thr[sl] = b2d(tieThr[l]);
+            } else if (tid < LB) {
+                tieSlot[tid] = -1;
             }
-            if (thr) atomicMax(&tieThr[l], thr);
-            fence_wg();
             __syncthreads();
-            if (!defer && gid == 0 && sl >= 0) tie.thr[sl] = b2d(tieThr[l]);
-        } else if (tid < LB) {
-            tieSlot[tid] = -1;
+            if (dbg && tid == 0) ctl->t4 = (long long)clock64();
+            // 0 fast path, 1 full igraph-heap emulation, 2 + slot: early-stop
+            // emulation with the exported tie data
+            if (gid == 0 && row >= 0)
+                rowAmbig[(size_t)b * LB + l] =
+                    ((needMask >> l) & 1u) ? (uint8_t)(tieSlot[l] >= 0 ? 2 + tieSlot[l] : 1) : (uint8_t)0;
         }
-        __syncthreads();
+        // ---- debug epilogue, the one of every part (SHD_PE_DEBUG_COUNTERS): the batch's
+        // slots dbg[16 b + k] and the parts that own them.  Stored: 0 phases, 15 repairs, 5 relax kcycles (t1 - t0): PART 0, 1;
+        // 6 predecessor pass (t2 - t1): 0, 2, 4, 5; 2 label walks (after the walks),
+        // 3 needMask, 7 labels + rows (t3 - t2), 11 tie export (t4 - t3), 8 after it:
+        // 0, 2, 4, 6; 1 the SHDPE_DIAG_WHY word: 0, 2, 4.  Added (atomicAdd / atomicOr
+        // onto what another kernel or phase of the round left): 4 vertex processings,
+        // 9 arcs / 16, 10 active lanes, and in the relax 12, 13, 14 busy max, busy
+        // mean, queue entries per phase: 0, 1; 1 the DIAG word: 5, 6; predCnt (the
+        // on-demand pass's in-arcs claimed, gathered): 0, 2, 4, 5, not the redo launch,
+        // whose batches the predecessor part counted.
+        if constexpr (!P::exports_ties) __syncthreads();     // (the tie export ends on a barrier)
 #ifdef SHDPE_DIAG_WHY
-        if (failed) why |= 1u;
+        if (P::exports_ties && failed) why |= 1u;
         if (why) atomicOr(&ctl->dWhy, why);
         __syncthreads();
 #endif
-        if (dbg && tid == 0) ctl->t4 = (long long)clock64();
-        // 0 fast path, 1 full igraph-heap emulation, 2 + slot: early-stop
-        // emulation with the exported tie data
-        if (gid == 0 && row >= 0)
-            rowAmbig[(size_t)b * LB + l] =
-                ((needMask >> l) & 1u) ? (uint8_t)(tieSlot[l] >= 0 ? 2 + tieSlot[l] : 1) : (uint8_t)0;
         if (dbg && tid == 0) {
-            if (PT == 0) {
+            if constexpr (P::relaxes) {
                 dbg[16 * b + 0] = phases;
-                dbg[16 * b + 15] = repairs;
                 dbg[16 * b + 5] = (int)((ctl->t1 - ctl->t0) >> 10);
+                dbg[16 * b + 15] = repairs;
                 atomicAdd(&dbg[16 * b + 4], (int)ctl->dProcs);
                 atomicAdd(&dbg[16 * b + 9], (int)(ctl->dArcs >> 4));
                 atomicAdd(&dbg[16 * b + 10], (int)ctl->dLanes);
             }
-            // (the label part adds to the predecessor part's slots, and leaves it slot 6)
-            if (LABEL) atomicOr(&dbg[16 * b + 1], (int)ctl->dWhy);
-            else dbg[16 * b + 1] = (int)ctl->dWhy;
-            dbg[16 * b + 3] = (int)needMask;
-            if (!LABEL) dbg[16 * b + 6] = (int)((ctl->t2 - ctl->t1) >> 10);
-            dbg[16 * b + 7] = (int)((ctl->t3 - ctl->t2) >> 10);
-            dbg[16 * b + 11] = (int)((ctl->t4 - ctl->t3) >> 10);
-            // (the redo launch's batches were counted by the predecessor part)
-            if (!LABEL && bs.predCnt && !(PART == 2 && bs.redoRun)) {       // the on-demand pass's in-arcs: claimed, gathered
-                atomicAdd(as_global(bs.predCnt), (unsigned long long)ctl->dClaim);
-                atomicAdd(as_global(bs.predCnt) + 1, (unsigned long long)ctl->dGath);
+            if constexpr (!P::relax_part) {
+                if (P::has_labels_in_bs) atomicOr(&dbg[16 * b + 1], (int)ctl->dWhy);
+                else dbg[16 * b + 1] = (int)ctl->dWhy;
             }
+            if constexpr (P::exports_ties) dbg[16 * b + 3] = (int)needMask;
+            if constexpr (P::runs_pred_pass) dbg[16 * b + 6] = (int)((ctl->t2 - ctl->t1) >> 10);
+            if constexpr (P::exports_ties) {
+                dbg[16 * b + 7] = (int)((ctl->t3 - ctl->t2) >> 10);
+                dbg[16 * b + 11] = (int)((ctl->t4 - ctl->t3) >> 10);
+            }
+            if constexpr (P::runs_pred_pass)
+                if (bs.predCnt && !(PART == 2 && bs.redoRun)) {
+                    atomicAdd(as_global(bs.predCnt), (unsigned long long)ctl->dClaim);
+                    atomicAdd(as_global(bs.predCnt) + 1, (unsigned long long)ctl->dGath);
+                }
         }
-        fence_wg();
+        if constexpr (P::exports_ties) fence_wg();
         __syncthreads();
-        if (dbg && tid == 0) dbg[16 * b + 8] = (int)(((long long)clock64() - ctl->t4) >> 10);
+        if constexpr (P::exports_ties)
+            if (dbg && tid == 0) dbg[16 * b + 8] = (int)(((long long)clock64() - ctl->t4) >> 10);
     }
 }
 

@@ -44,7 +44,7 @@ def table(E, top, att, split, monkeypatch, env=(), sources=None, tune=False):
         got = [eng.get_row(int(s)) for s in sources]
         rows = {k: np.stack([g[k] for g in got]) for k in FIELDS}
     st = eng.stats()
-    info = eng.post_split_info()
+    info = dict(eng.post_split_info(), **eng.batch_info())     # + perRound, slots, rounds, batches
     eng.close()
     return {k: rows[k] for k in FIELDS}, st, info
 
@@ -79,6 +79,50 @@ def test_rows_exact_split_and_unsplit(E, expected, monkeypatch, case, lb, wpe):
             assert info["redoBatches"] == 0, (ctx, info)   # shallow, tie-free: nothing to redo
     for k in FIELDS:
         assert got[True][k].tobytes() == got[False][k].tobytes(), (case, lb, wpe, k)
+
+
+@pytest.fixture(scope="module")
+def chain_case(oracle_mod):
+    """The 2,400-vertex chain of test_deep_tree_takes_the_redo_launch, its
+    sources and the oracle's rows of them, computed once."""
+    n = 2400
+    top = _chain(n, seed=n)
+    att = np.arange(n, dtype=np.int32)
+    srcs = np.array([0, n - 1, n // 2, n // 3, 7], np.int32)
+    return top, att, srcs, oracle_mod.OracleGraph(top).rows(srcs, att, threads=8), True
+
+
+@pytest.mark.parametrize("wpe", [4, 8])
+@pytest.mark.parametrize("lb", [8, 16])
+@pytest.mark.parametrize("case", ["ba1200", "ties", "chain"])
+def test_rows_exact_one_kernel(E, chain_case, expected, monkeypatch, case, lb, wpe):
+    """SHDPE_BATCH_SPLIT=0: the whole batch in one kernel (relax, full
+    predecessor pass, labels, rows, in-line tie export) computes the table of
+    the split kernels, bit-exact against the oracle.  The chain is deeper than
+    WALK_BUDGET: the kernel's own sweeps and second writer pass write its rows.
+    (The engine offers the 6-wave variant only to the split kernels.)"""
+    if case == "chain":
+        top, att, srcs, exp, tiefree = chain_case
+    else:
+        (top, att, tiefree), srcs, exp = CASES[case], None, expected[case]
+    knobs = (("SHDPE_BATCH_LB", lb), ("SHDPE_BATCH_WPE", wpe))
+    ref, _, rinfo = table(E, top, att, True, monkeypatch, env=knobs, sources=srcs)
+    assert rinfo["split"] == 1, rinfo
+    rows, st, info = table(E, top, att, False, monkeypatch, env=knobs + (("SHDPE_BATCH_SPLIT", 0),), sources=srcs)
+    ctx = f"{case} lb {lb} wpe {wpe} one kernel"
+    assert st["mode"] == 1 and st["batched"] == 1 and st["batchLanes"] == lb and st["batchWaves"] == wpe, (ctx, st)
+    # the one-kernel route ran: no post kernel in the plan, no round of the split kernels
+    assert info["split"] == 0 and info["labelWaves"] == 0 and info["redoBatches"] == 0, (ctx, info)
+    assert st["batchPostWaves"] == 0, (ctx, st)
+    assert info["rounds"] == 0 and info["batches"] == 0, (ctx, info)
+    check_rows(rows, exp, ctx)
+    assert st["rowsTieRepaired"] == 0, (ctx, st)
+    if tiefree:
+        assert st["rowsExact"] == 0, (ctx, st)
+    else:
+        assert st["rowsExact"] > 0, (ctx, st)       # tie rows: the in-line export and the exact kernel
+    for k in FIELDS:
+        assert np.asarray(rows[k]).tobytes() == np.asarray(ref[k]).tobytes(), (ctx, k)
 
 
 @pytest.mark.parametrize("lb", [8, 16])
