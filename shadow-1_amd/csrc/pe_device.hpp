@@ -176,6 +176,8 @@ struct Tuning {
                                // table takes several rounds
     int tieSlotsCap = -1;      // tests only: >= 0 = at most this many tie slots (0: none, the
                                // state of a graph past 2^30 arcs); -1 unchanged
+    int devicePlan = 1;        // tests only: 0 = batch order 2's plan by batch_order_cost on the
+                               // host (the reference), 1 = by the plan kernels (pe_plan_dev.hip)
 };
 
 struct DevScratch {

@@ -94,6 +94,7 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_TUNE_FAIL_WPE", t.failWpe);
     gi("SHDPE_BATCH_ROUND", t.batchRoundCap);
     gi("SHDPE_TIE_SLOTS", t.tieSlotsCap);
+    gi("SHDPE_DEVICE_PLAN", t.devicePlan);
     gi("SHDPE_TUNE_LOG", t.tuneLog);
     gi("SHDPE_PATHS_GROUP", t.pathsGroup);
     gi("SHDPE_PATHS_CHUNK", t.pathsChunk);
@@ -507,6 +508,8 @@ static int build_graph_on_device(const ShdPeGraphDesc* graph, const ShdPeOptions
     return rc;
 }
 
+static int upload_plan_inputs(ShdPe* pe, Shard* sh);
+
 // Create, both entry points: everything after the graph exists is shared.
 static int create_engine(const ShdPeGraphDesc* graph, const int32_t* attached, int32_t nAttached,
                          const ShdPeOptions* opt, int32_t graphBuild, ShdPeBuildInfo* infoOut, ShdPe** out) {
@@ -598,6 +601,8 @@ static int create_engine(const ShdPeGraphDesc* graph, const int32_t* attached, i
         pe->rank.swap(br.rank);
         pe->rowOff.swap(br.rowOff);
         pe->hubGroups = std::move(br.groups);
+        for (auto& sh : pe->shards)
+            if ((rc = upload_plan_inputs(pe.get(), sh.get()))) { shd_pe_destroy(pe.release()); return rc; }
     }
     pe->rowDone.reset(new (std::nothrow) std::atomic<uint8_t>[T]);
     if (!pe->rowDone) { shd_pe_destroy(pe.release()); return SHD_PE_ENOMEM; }
@@ -607,6 +612,31 @@ static int create_engine(const ShdPeGraphDesc* graph, const int32_t* attached, i
         *infoOut = info;
     }
     *out = pe.release();
+    return SHD_PE_OK;
+}
+
+// The device plan's inputs (DevPlan) of a shard, from the host versions create
+// just made; freed with the shard.  Without hub groups (orders 0 and 1) or
+// with more groups than a wave has lanes the shard has none and plans on the
+// host.
+static int upload_plan_inputs(ShdPe* pe, Shard* sh) {
+    const HubGroups& hg = pe->hubGroups;
+    const size_t T = pe->rank.size();
+    if (hg.empty() || hg.G > 64 || T == 0 || pe->rowOff.size() != T || hg.dist.size() != T * (size_t)hg.G)
+        return SHD_PE_OK;
+    HIPCHK(hipSetDevice(sh->device));
+    DevPlan& dp = sh->dplan;
+    int rc;
+    if ((rc = dev_alloc(sh, &dp.rank, T)) || (rc = dev_alloc(sh, &dp.rowOff, T)) ||
+        (rc = dev_alloc(sh, &dp.hubDist, T * (size_t)hg.G)))
+        return rc;
+    HIPCHK(hipMemcpy(dp.rank, pe->rank.data(), T * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dp.rowOff, pe->rowOff.data(), T * 8, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(dp.hubDist, hg.dist.data(), T * (size_t)hg.G * 8, hipMemcpyHostToDevice));
+    dp.T = (int32_t)T;
+    dp.G = hg.G;
+    const double mean = pe->hg.meanArcLatency;
+    dp.unit = mean > 0.0 && std::isfinite(mean) ? mean : 1.0;
     return SHD_PE_OK;
 }
 
@@ -846,12 +876,25 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
     // batch of the round, counted with the round's dist arrays
     const size_t mStride = ((size_t)pe->hg.nArcs() + 127) & ~(size_t)127;
     const bool filter = plan.relax.split && pe->tu.predFilter != 0 && mStride > 0;
+    // the device plan's scratch (its inputs were allocated at create, so the
+    // free memory read below is already less by them): budgeted with the
+    // per-slot scratch still to allocate
+    DevPlan& dp = sh->dplan;
+    size_t planBytes = 0;
+    if (dp.inputs() && pe->tu.devicePlan != 0) {
+        // (sized by the rows alone, like dBatchRows: a trial's lanes need not be the plan's)
+        dp.capRows = dp.capBatches = sh->rowsCap;
+        // (a failed size query: no scratch, the shard plans on the host as before)
+        dp.tempBytes = plan_dev_temp_bytes(dp.capRows, dp.capBatches);
+        if (dp.tempBytes)
+            planBytes = dp.tempBytes + ((size_t)dp.capRows + 64) * (12 + 12) + (size_t)dp.capBatches * 24;
+    }
     size_t roundB = slots;
     if (plan.relax.split) {
         size_t freeB = 0, totalB = 0;
         if (hipMemGetInfo(&freeB, &totalB) != hipSuccess) freeB = (size_t)16 << 30;
         const size_t perD = NS * LB * 8 + (filter ? mStride / 8 : 0);
-        const size_t rest = slots * (perSlot - NS * LB * 8);
+        const size_t rest = slots * (perSlot - NS * LB * 8) + planBytes;
         // (tests only, SHDPE_BATCH_ROUND: fewer batches per round than would fit)
         roundB = batch_round_size(slots, nBatchesAll, perD, rest, freeB, pe->tu.batchRoundCap);
     }
@@ -864,6 +907,20 @@ static int ensure_batch(ShdPe* pe, Shard* sh) {
         (rc = dev_alloc(sh, &sh->dBatchAmb, (size_t)sh->rowsCap + 64)) ||
         (rc = dev_alloc(sh, &sh->bsc.flags, roundB + 16)))
         return rc;
+    if (planBytes) {
+        // without room for the plan's scratch the shard keeps the host planner
+        // (ready() stays false); what was allocated is freed with the shard
+        const size_t cb = (size_t)dp.capBatches;
+        unsigned char* temp = nullptr;
+        if ((rc = dev_alloc(sh, &dp.keyIn, (size_t)dp.capRows)) || (rc = dev_alloc(sh, &dp.keyOut, (size_t)dp.capRows)) ||
+            (rc = dev_alloc(sh, &dp.sorted, (size_t)dp.capRows)) ||
+            (rc = dev_alloc(sh, &dp.rowsTmp, (size_t)dp.capRows + 64)) ||
+            (rc = dev_alloc(sh, &dp.offTmp, (size_t)dp.capRows + 64)) || (rc = dev_alloc(sh, &dp.cost, cb)) ||
+            (rc = dev_alloc(sh, &dp.costSorted, cb)) || (rc = dev_alloc(sh, &dp.idx, cb)) ||
+            (rc = dev_alloc(sh, &dp.perm, cb)) || (rc = dev_alloc(sh, &temp, dp.tempBytes)))
+            (void)hipGetLastError();
+        dp.temp = rc ? nullptr : temp;   // (marks the scratch ready: written last)
+    }
     sh->bsc.next = sh->bsc.queue + slots * NS;
     sh->bsc.nStride = (int64_t)NS;
     sh->bsc.arcHit = nullptr;
@@ -1237,26 +1294,50 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     int32_t nB = 0;
     const int offKind = pe->tu.laneOffset != 0;
     const bool byCost = !batchOrder && !pe->hubGroups.empty();
+    // batch order 2 composes its plan on the device, from the positions in
+    // dRows (the plan kernels, pe_plan_dev.hip): the host neither plans nor
+    // uploads before the relax launch, and reads `order` back behind the
+    // kernels.  (SHDPE_DEVICE_PLAN=0, tests: batch_order_cost, the reference.)
+    const bool onDevice = byCost && sh->dplan.ready() && pe->tu.devicePlan != 0;
     std::vector<double> laneOff;     // per entry of `order`: they depend on who shares the batch
-    const std::vector<int32_t> order =
-        batchOrder ? *batchOrder
-        : byCost ? batch_order_cost(pe->rank, pe->rowOff, pe->hubGroups, pe->hg.meanArcLatency, relax.lb, pos, cnt,
-                                    nB, nullptr, &laneOff, offKind)
-                 : batch_order(pe->rank, pe->rowOff, relax.lb, pos, cnt, nB);
-    if (!byCost) laneOff = lane_offsets(pe->hubGroups, pe->rowOff, order, relax.lb, offKind);
-    nB = (int32_t)(order.size() / (size_t)relax.lb);
-    HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
-    HIPCHK(hipMemcpyAsync(sh->dLaneOff, laneOff.data(), laneOff.size() * 8, hipMemcpyHostToDevice, sh->stream));
-    if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
-    if (sh->bsc.predCnt) HIPCHK(hipMemsetAsync(sh->bsc.predCnt, 0, 16, sh->stream));
-    if (sh->bsc.redo) HIPCHK(hipMemsetAsync(sh->bsc.redo, 0, 8, sh->stream));
-    if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
-    // the slots' deferred-export requests: round -1, which no round's k_tie_export
-    // serves.  A slot the post kernel fills in line (its second attempt: a deep
-    // tree with ties) gets no request, and the words an earlier call -- or the
-    // allocator -- left there would name a batch of this call's round
-    if (sh->tie.req) HIPCHK(hipMemsetAsync(sh->tie.req, 0xFF, (size_t)sh->tie.cap * 16, sh->stream));
-    HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
+    std::vector<int32_t> order;
+    if (onDevice) {
+        nB = (cnt + relax.lb - 1) / relax.lb;
+        order.resize((size_t)nB * (size_t)relax.lb);
+        // the control words of the call go with the plan's last kernel.  The tie
+        // slots' deferred-export requests: round -1, as below
+        PlanControl ctl;
+        ctl.next = sh->bsc.next;
+        ctl.redo = sh->bsc.redo;
+        ctl.predCnt = sh->bsc.predCnt;
+        ctl.tieCount = sh->tie.cap > 0 ? sh->tie.count : nullptr;
+        ctl.tieReq = sh->tie.req;
+        ctl.tieReqWords = sh->tie.req ? (int64_t)sh->tie.cap * 4 : 0;
+        ctl.dbg = sh->dDbg;
+        ctl.dbgWords = sh->dDbg ? (int64_t)nB * 16 : 0;
+        if ((rc = launch_plan_dev(sh->dplan, sh->dRows, cnt, relax.lb, offKind, sh->dBatchRows, sh->dLaneOff, ctl,
+                                  sh->stream)))
+            return rc;
+    } else {
+        order = batchOrder ? *batchOrder
+                : byCost   ? batch_order_cost(pe->rank, pe->rowOff, pe->hubGroups, pe->hg.meanArcLatency, relax.lb,
+                                              pos, cnt, nB, nullptr, &laneOff, offKind)
+                           : batch_order(pe->rank, pe->rowOff, relax.lb, pos, cnt, nB);
+        if (!byCost) laneOff = lane_offsets(pe->hubGroups, pe->rowOff, order, relax.lb, offKind);
+        nB = (int32_t)(order.size() / (size_t)relax.lb);
+        HIPCHK(hipMemcpyAsync(sh->dBatchRows, order.data(), order.size() * 4, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipMemcpyAsync(sh->dLaneOff, laneOff.data(), laneOff.size() * 8, hipMemcpyHostToDevice, sh->stream));
+        if (sh->dDbg) HIPCHK(hipMemsetAsync(sh->dDbg, 0, (size_t)nB * 64, sh->stream));
+        if (sh->bsc.predCnt) HIPCHK(hipMemsetAsync(sh->bsc.predCnt, 0, 16, sh->stream));
+        if (sh->bsc.redo) HIPCHK(hipMemsetAsync(sh->bsc.redo, 0, 8, sh->stream));
+        if (sh->tie.cap > 0) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
+        // the slots' deferred-export requests: round -1, which no round's k_tie_export
+        // serves.  A slot the post kernel fills in line (its second attempt: a deep
+        // tree with ties) gets no request, and the words an earlier call -- or the
+        // allocator -- left there would name a batch of this call's round
+        if (sh->tie.req) HIPCHK(hipMemsetAsync(sh->tie.req, 0xFF, (size_t)sh->tie.cap * 16, sh->stream));
+        HIPCHK(hipMemsetAsync(sh->bsc.next, 0, 4, sh->stream));
+    }
     HIPCHK(hipEventRecord(sh->evA, sh->stream));
     if (!relax.split)
         launch_batch_rows(sh->dg, sh->tab, scratch_at(sh, sh->dBatchRows), sh->dBatchRows, nB, sh->dBatchAmb, relax,
@@ -1267,6 +1348,8 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
     HIPCHK(hipEventRecord(sh->evB, sh->stream));
     std::vector<uint8_t> amb(order.size());
     HIPCHK(hipMemcpyAsync(amb.data(), sh->dBatchAmb, order.size(), hipMemcpyDeviceToHost, sh->stream));
+    if (onDevice)                    // (the kernels only read dBatchRows: still the plan's rows)
+        HIPCHK(hipMemcpyAsync(order.data(), sh->dBatchRows, order.size() * 4, hipMemcpyDeviceToHost, sh->stream));
     int32_t redone[2] = {0, 0};      // [1]: batches of this call that took the redo launch
     if (sh->bsc.redo) HIPCHK(hipMemcpyAsync(redone, sh->bsc.redo, 8, hipMemcpyDeviceToHost, sh->stream));
     HIPCHK(hipStreamSynchronize(sh->stream));
@@ -1278,6 +1361,12 @@ static int relax_batched(ShdPe* pe, Shard* sh, const int32_t* pos, int32_t cnt, 
         std::vector<int32_t> dbg((size_t)nB * 16);
         HIPCHK(hipMemcpy(dbg.data(), sh->dDbg, dbg.size() * 4, hipMemcpyDeviceToHost));
         print_batch_debug(pe, sh, relax, dbg.data(), nB);
+        std::fprintf(stderr, "[shdpe] shard %d batch plan by the %s\n", sh->gindex,
+                     onDevice ? "plan kernels" : batchOrder ? "caller" : "host planner");
+        if (onDevice) {              // the dump carries the plan the kernels ran with
+            laneOff.resize(order.size());
+            HIPCHK(hipMemcpy(laneOff.data(), sh->dLaneOff, laneOff.size() * 8, hipMemcpyDeviceToHost));
+        }
         dump_batches(pe, order, laneOff, dbg, nB, relax.lb);
         if (sh->bsc.predCnt) {
             unsigned long long pc[2] = {0, 0};

@@ -55,6 +55,50 @@ struct BatchTrial {
     double msRelax = 0.0, msPost = 0.0, msLabel = 0.0;   // (msLabel: label part + redo launch)
 };
 
+// The batch plan composed on the device (pe_plan_dev.hip): a shard's copy of
+// what batch_order_cost reads -- uploaded where the host versions are made,
+// at create -- and the scratch of the plan kernels (ensure_batch).
+struct DevPlan {
+    int32_t* rank = nullptr;        // [T]
+    double* rowOff = nullptr;       // [T]
+    double* hubDist = nullptr;      // [T][G], HubGroups::dist
+    int32_t T = 0, G = 0;
+    double unit = 1.0;              // batch_order_cost's latency unit
+    // scratch: null until ensure_batch ran
+    uint32_t *keyIn = nullptr, *keyOut = nullptr;   // [capRows] ranks of the positions, unsorted / sorted
+    int32_t* sorted = nullptr;      // [capRows] positions by rank
+    int32_t* rowsTmp = nullptr;     // [capRows + 64] composed batches before sequencing ...
+    double* offTmp = nullptr;       // ... and their lane offsets
+    double *cost = nullptr, *costSorted = nullptr;  // [capBatches]
+    int32_t *idx = nullptr, *perm = nullptr;        // [capBatches] batch indices, unsorted / by descending cost
+    void* temp = nullptr;           // the sorts' temporary storage
+    size_t tempBytes = 0;
+    int32_t capRows = 0, capBatches = 0;
+    bool inputs() const { return hubDist != nullptr; }
+    bool ready() const { return temp != nullptr; }
+};
+
+// The words of a batched call that k_plan_emit sets in place of the host's
+// memsets (null / 0: not there).
+struct PlanControl {
+    int32_t* next = nullptr;                 // BatchScratch::next
+    int32_t* redo = nullptr;                 // BatchScratch::redo [0], [1]
+    unsigned long long* predCnt = nullptr;   // BatchScratch::predCnt [0], [1]
+    int32_t* tieCount = nullptr;             // TieBuf::count [0]
+    int32_t* tieReq = nullptr;               // TieBuf::req, every word to -1 (round -1)
+    int64_t tieReqWords = 0;
+    int32_t* dbg = nullptr;                  // the batches' debug counters, zeroed
+    int64_t dbgWords = 0;
+};
+
+// pe_plan_dev.hip
+// bytes of temporary storage for calls of up to maxRows rows in maxBatches batches (0: query failed)
+size_t plan_dev_temp_bytes(int32_t maxRows, int32_t maxBatches);
+// The plan of the cnt positions at dPos (device) into dBatchRows / dLaneOff and
+// the control words, all on `st`; nothing waits on the host.
+int launch_plan_dev(const DevPlan& dp, const int32_t* dPos, int32_t cnt, int32_t LB, int32_t kind,
+                    int32_t* dBatchRows, double* dLaneOff, const PlanControl& ctl, hipStream_t st);
+
 // shd_pe_get_path: PathsWalkArgs' arrays for one request (off = 0); the path's vertices follow.
 struct PathOne {
     int64_t off;
@@ -98,6 +142,7 @@ struct Shard {
     int64_t roundsRun = 0, batchesRun = 0;   // shd_pe_batch_info: batch_rounds' rounds and their batches (table passes)
     int32_t* dBatchRows = nullptr;
     double* dLaneOff = nullptr;     // per entry of dBatchRows its lane's bucket key offset
+    DevPlan dplan{};                // batch order 2: the plan's inputs and scratch on the device
     uint8_t* dBatchAmb = nullptr;
     TieBuf tie{};                   // early-stop tie rows (batched path)
     int32_t* dSlots = nullptr;      // per exact row its tie slot, -1 full emulation

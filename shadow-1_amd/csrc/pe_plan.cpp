@@ -336,7 +336,7 @@ std::vector<int32_t> batch_order(const std::vector<int32_t>& rank, const std::ve
 // lane offsets too: with the spread taken as the residual those offsets leave
 // and the constants refitted, the correlation is 0.942 and the replayed take
 // ends where this sequence does (profiles/lane_offsets_sim.json).
-static const double COST_C0 = 0.892, COST_OFF = 0.200, COST_SPREAD = 3.363;
+// (COST_C0, COST_OFF, COST_SPREAD: pe_plan.hpp, shared with the device plan.)
 
 std::vector<int32_t> batch_order_cost(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
                                       const HubGroups& groups, double meanArcLatency, int LB,

@@ -110,6 +110,9 @@ std::vector<double> lane_offsets(const HubGroups& groups, const std::vector<doub
 // composed batches, permuted with them: the sequence does not depend on the
 // kind.  laneOff, if given, receives them and cost the nB costs, both in the
 // order returned.
+// (The constants of the cost, fitted in pe_plan.cpp; pe_plan_dev.hip computes
+// the same cost on the device.)
+constexpr double COST_C0 = 0.892, COST_OFF = 0.200, COST_SPREAD = 3.363;
 std::vector<int32_t> batch_order_cost(const std::vector<int32_t>& rank, const std::vector<double>& rowOff,
                                       const HubGroups& groups, double meanArcLatency, int LB,
                                       const int32_t* pos, int32_t cnt, int32_t& nB,

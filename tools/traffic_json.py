@@ -28,8 +28,9 @@ def main():
     dst = sys.argv[4] if len(sys.argv) > 4 else os.path.join(ROOT, "profiles", f"traffic_{wl}.json")
     # per pass, only the measured step: the LAST dispatch of each path kernel
     # (bench.py runs shd_pe_tune -- both kernel variants -- before it); the
-    # split batch path runs two kernels per step (k_batch_rows<.., 1> relax,
-    # <.., 2> post): the last post dispatch and the relax dispatch before it
+    # split batch path runs several kernels per step (k_batch_rows<.., 1> relax,
+    # then <.., 2> post, or <.., 5> predecessor part, <.., 6> label part and
+    # the <.., 2> redo launch): the last relax dispatch and all that follow it
     per = defaultdict(list)          # (file, kernel family) -> [(dispatch, name, row)]
     for f in glob.glob(os.path.join(outdir, f"pmc_{wl}_*", "**", "*counter_collection*.csv"), recursive=True):
         for r in csv.DictReader(open(f)):
@@ -47,15 +48,20 @@ def main():
         lastName = next(nm for d, nm, _ in rs if d == last)
         keep = {last}
         if ", 2>(" in lastName:
+            # the relax launch of the step and everything after it: the one
+            # post kernel, or its predecessor part (5), label part (6) and the
+            # redo launch (2)
             prev = [d for d, nm, _ in rs if d < last and ", 1>(" in nm]
             if prev:
-                keep.add(max(prev))
+                keep.update(d for d in ids if d >= max(prev))
         for d, nm, r in rs:
             if d in keep:
                 tot[k][r["Counter_Name"]] += float(r["Counter_Value"])
                 disp[k][r["Counter_Name"]].add((f, d))
-                if k == "k_batch_rows" and (", 1>(" in nm or ", 2>(" in nm):
-                    parts["relax" if ", 1>(" in nm else "post"][r["Counter_Name"]] += float(r["Counter_Value"])
+                part = next((p for t, p in ((", 1>(", "relax"), (", 2>(", "post"), (", 5>(", "pred"), (", 6>(", "label"))
+                             if t in nm), None)
+                if k == "k_batch_rows" and part:
+                    parts[part][r["Counter_Name"]] += float(r["Counter_Value"])
     if not tot:
         sys.exit(f"no counters for the path kernels under {outdir}/pmc_{wl}_*")
     k = max(tot, key=lambda x: tot[x].get("FETCH_SIZE", 0.0))
@@ -73,8 +79,9 @@ def main():
         "write_bytes": write,
         "l2_hit_rate": hit / (hit + miss) if hit + miss else None,
         "dispatches_per_step": nl,
-        "dispatch": "the measured step only: the last launch of the pass, with the relax launch before it "
-                    "when the batch path runs split (the tuning launches before them are ignored)",
+        "dispatch": "the measured step only: the last launch of the pass, and when the batch path runs split "
+                    "the step's relax launch with every launch after it (post kernel, or predecessor part, "
+                    "label part and redo launch; the tuning launches before them are ignored)",
         "method": "rocprofv3 --pmc FETCH_SIZE and --pmc WRITE_SIZE in separate passes, KB*1024, "
                   "bench.py --steps 1 --warmup 0 (one launch).  Reads = 2 x FETCH_SIZE (gfx950 "
                   "calibration for random 128-B lines, profiles/r02e_fetch_calibration.json); "
@@ -92,7 +99,7 @@ def main():
             out["parts"][pn] = {"bytes": 2 * pf + pw, "read_bytes": 2 * pf, "write_bytes": pw,
                                 "l2_hit_rate": ph / (ph + pm) if ph + pm else None,
                                 "counters": dict(pc)}
-        if len(sys.argv) > 5:        # per-part counter CSVs: <prefix>_{relax,post}.csv
+        if len(sys.argv) > 5:        # per-part counter CSVs: <prefix>_{relax,post,pred,label}.csv
             for pn, pc in parts.items():
                 with open(f"{sys.argv[5]}_{pn}.csv", "w") as f:
                     f.write("counter,value_per_step\n")
