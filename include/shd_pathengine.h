@@ -36,7 +36,7 @@
 extern "C" {
 #endif
 
-#define SHD_PE_ABI_VERSION 15  /* 7: graph property check (shd_pe_graph_props);
+#define SHD_PE_ABI_VERSION 16  /* 7: graph property check (shd_pe_graph_props);
                                   8: fill from row shards (shd_pe_fill_rowstore_shards);
                                   9: shd_pe_pred_filter_counts;
                                   10: shd_pe_create_built (graph build on the device),
@@ -47,7 +47,8 @@ extern "C" {
                                       info[6];
                                   14: shd_pe_path_load, shd_pe_path_load_info, shd_pe_num_arcs,
                                       shd_pe_arc_list, shd_pe_find_arc, shd_topology_link_load;
-                                  15: shd_pe_sparse_info */
+                                  15: shd_pe_sparse_info;
+                                  16: shd_pe_table_load, shd_pe_table_load_info */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -442,6 +443,62 @@ int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* dst,
  * entries reduced (vertices of all paths), info[1] global atomic adds the
  * reduction issued (counted only under SHD_PE_DEBUG_COUNTERS, else 0). */
 int shd_pe_path_load_info(const ShdPe* pe, int64_t* info, int32_t n);
+
+/* ---- all-pairs link and vertex load of a range of source rows (ABI 16) --
+ * shd_pe_table_load is shd_pe_path_load of the count * T requests
+ * (attached[p], attached[q], w) for p in [start, start + count) and q in
+ * [0, T), T = shd_pe_num_attached, w = weight[(p - start) * ld + q] or 1 when
+ * weight == NULL: arcLoad, vertexLoad and totals[0..3] are exactly what that
+ * call returns (sums modulo 2^64, every non-NULL array overwritten), the path
+ * of a pair is shd_pe_get_paths' path, a pair with a status adds nothing and
+ * counts in totals[3], and p == q adds to vertexLoad only.  out->status is NOT
+ * written: there are count * T requests.  totals come from the table's flags
+ * and hops alone, as in shd_pe_path_load, so totals[1] == sum(vertexLoad) and
+ * totals[2] == sum(arcLoad) check the kernels against the table.
+ *
+ * pe, in or out NULL, a range outside [0, T], or weight != NULL with ld < T:
+ * SHD_PE_EINVAL before anything is written.  count == 0 is success and writes
+ * zeros.  A range that reaches a row another process's engine owns
+ * (shardCount > 1, not gathered): SHD_PE_ENOTOWNED before anything is written;
+ * a range over several local shards is served shard by shard and summed.  Rows
+ * not yet computed are computed first.  Takes the compute lock.  Side effects
+ * are shd_pe_path_load's: no table byte, computed-row flag, ShdPeStats field
+ * or shd_pe_batch_info counter changes.
+ *
+ * Three routes serve the sources.  Where shd_pe_get_paths' batch tier applies
+ * (the split batch kernels), the tree tier: one pass of those kernels that
+ * stores no row, and per round one kernel that seeds every status-0
+ * destination of a source with its weight, claims the shortest-path tree
+ * upwards from the seeds (each claimed vertex derives its parent once, by the
+ * rule shd_pe_get_paths' walks use), sums the subtrees leaves first, checks the
+ * source's sum against the expected total and only then adds the sums to the
+ * shard's accumulator.  A source with an ambiguous parent, a zero-increment
+ * arc, a Bellman violation or an infinite distance on the way, or a failed
+ * check, adds nothing there and is handed on.  The weight rows of a round go up
+ * through page-locked staging; the count x ld matrix is never on the device as
+ * a whole.  On a complete graph one direct kernel adds every pair's edge.
+ * Every other source -- tie rows, handed-on sources, engines without the batch
+ * tier -- runs shd_pe_path_load's pipeline on requests made inside the call.
+ * shd_pe_paths_info and shd_pe_path_load_info afterwards describe that part
+ * alone (all zero when there was none).  A failed scratch or staging
+ * allocation is SHD_PE_ENOMEM.  (Under SHD_PE_DEBUG_ENV: SHDPE_TLOAD_TREE=0
+ * turns the tree tier off; SHDPE_TLOAD_CORRUPT=1 / 2 spoil the first source's
+ * expected total / first claimed vertex, tests.) */
+typedef struct ShdPeTableLoadIn {
+    int32_t start, count;     /* source rows: table positions [start, start+count) */
+    const uint64_t* weight;   /* count x ld, row-major: weight[(p-start)*ld + q] is the weight of
+                                 (attached[p] -> attached[q]); NULL: 1 for every pair */
+    int64_t ld;               /* >= T; ignored when weight == NULL */
+} ShdPeTableLoadIn;
+int shd_pe_table_load(ShdPe* pe, const ShdPeTableLoadIn* in, const ShdPeLoadOut* out);
+/* Of the last shd_pe_table_load call, the first min(n, 8) of: info[0] sources
+ * served by the tree tier, info[1] by the direct kernel, info[2] by the request
+ * route (each source in exactly one of the three); info[3] of info[2], sources
+ * the tree tier had started and handed on after one of its own checks; info[4]
+ * tree entries claimed by the sources of info[0]; info[5] device time of the
+ * call from events, in microseconds; info[6] rounds the tree tier ran; info[7]
+ * global adds its commit issued (SHD_PE_DEBUG_COUNTERS only, else 0). */
+int shd_pe_table_load_info(const ShdPe* pe, int64_t* info, int32_t n);
 
 /* Page-locked host memory for shd_pe_get_rows destinations (DMA target, no
  * staging copy).  No reference counterpart: Shadow's row buffers are plain

@@ -19,17 +19,6 @@
 
 namespace shdpe {
 
-// first arc of row s with col >= t (igraph_get_eid on a sorted incidence row)
-__device__ __forceinline__ int row_lower_bound(const DevGraph& g, int s, int t) {
-    int lo = g.rowPtr[s], hi = g.rowPtr[s + 1];
-    while (lo < hi) {
-        const int mid = lo + ((hi - lo) >> 1);
-        if (g.col[mid] < t) lo = mid + 1;
-        else hi = mid;
-    }
-    return lo;
-}
-
 // One wave per vertex.  The reference walks v's OUT-incident edges in igraph
 // order (ascending neighbour, the self-loop in place) and keeps the first
 // strict minimum of the latency (the minLatency == 0 sentinel of :1592 only
@@ -84,15 +73,6 @@ __global__ __launch_bounds__(256) void k_self_paths(DevGraph g0, const int32_t* 
             flags[w] = 0;
         }
     }
-}
-
-// _topology_verticesAreAdjacent: an arc s -> t exists (s == t: a self-loop);
-// *arc = its CSR index (unset for s == t)
-__device__ __forceinline__ bool find_arc(const DevGraph& g, int s, int t, int* arc) {
-    if (s == t) return g.hasSelf[s] != 0;
-    const int a = row_lower_bound(g, s, t);
-    *arc = a;
-    return a < g.rowPtr[s + 1] && g.col[a] == t;
 }
 
 // _topology_lookupDirectPath over the arc find_arc found: lat = 0.0 + w of the
@@ -835,6 +815,55 @@ __global__ __launch_bounds__(256) void k_paths_load(DevGraph g0, const int64_t* 
         __syncthreads();
         if (tid == 0 && issuedWg) atomicAdd(nIssued, (unsigned long long)issuedWg);
     }
+}
+
+// shd_pe_table_load on a complete graph: the path of (attached[p], attached[q])
+// is the edge itself, by shd_pe_get_paths' status rule (k_paths_size: [s] for
+// p == q, SHD_PE_ENOEDGE where the edge is missing).  blockIdx.y = the row of
+// the block, one thread per destination; the row's own vertex and the totals
+// are summed in LDS first, one global add each per workgroup.
+__global__ __launch_bounds__(256) void k_table_direct(DevGraph g0, TableDirectArgs p) {
+    __shared__ unsigned long long part[5];       // totals[0..3], the source's vertex load
+    const DevGraph g = global_view(g0);
+    const int tid = threadIdx.x;
+    if (tid < 5) part[tid] = 0;
+    __syncthreads();
+    const int r = blockIdx.y, q = (int)(blockIdx.x * 256 + tid);
+    const int32_t* __restrict__ att = as_global(p.attached);
+    unsigned long long* __restrict__ acc = (unsigned long long*)as_global(p.acc);
+    const int s = att[p.row0 + r];
+    if (q < p.T) {
+        const int t = att[q];
+        const unsigned long long w = p.weight ? (unsigned long long)as_global(p.weight)[(size_t)r * (size_t)p.T + q] : 1ull;
+        int a = -1;
+        if (s == t) {
+            atomicAdd(&part[0], 1ull);
+            atomicAdd(&part[1], w);
+            atomicAdd(&part[4], w);
+        } else if (find_arc(g, s, t, &a)) {
+            atomicAdd(&part[0], 1ull);
+            atomicAdd(&part[1], 2 * w);
+            atomicAdd(&part[2], w);
+            atomicAdd(&part[4], w);
+            if (w) {
+                __hip_atomic_fetch_add(acc + a, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(acc + p.nArcs + t, w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        } else {
+            atomicAdd(&part[3], 1ull);
+        }
+    }
+    __syncthreads();
+    if (tid < 4 && part[tid])
+        __hip_atomic_fetch_add((unsigned long long*)as_global(p.out) + tid, part[tid], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (tid == 4 && part[4])
+        __hip_atomic_fetch_add(acc + p.nArcs + s, part[4], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+void launch_table_direct(const DevGraph& gAux, const TableDirectArgs& a, void* stream) {
+    if (a.rows <= 0 || a.T <= 0) return;
+    hipLaunchKernelGGL(k_table_direct, dim3((unsigned)((a.T + 255) / 256), (unsigned)a.rows), dim3(256), 0,
+                       reinterpret_cast<hipStream_t>(stream), gAux, a);
 }
 
 void launch_paths_size(const DevGraph& gAux, const DevTable& tab, const PathsSizeArgs& a, void* stream) {

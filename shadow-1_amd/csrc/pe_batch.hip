@@ -1646,6 +1646,43 @@ void k_batch_rows(DevGraph g0, DevTable tab0, BatchScratch bs, const int32_t* __
     }
 }
 
+// The igraph parent of a vertex at distance dv, from a batch's persisted
+// distance array D ([vertex][LB], lane l), over the vertex's in-arcs [a0, a1)
+// (its own row when undirected): the first tight in-arc, in incidence order,
+// of minimum dist[u].  The one statement of the rule for k_tie_export and
+// k_tree_load.  best: that minimum (INF_BITS: no tight arc); cnt: tight arcs
+// that attain it; arc: the first of them; mn: the least dist[u] + w over every
+// in-arc (mn < dv: a Bellman violation).
+struct ParentPick {
+    unsigned long long best, mn;
+    int cnt, arc;
+    // equal minima, a zero-increment arc (or no tight arc at all): the heap decides
+    __device__ __forceinline__ bool ambiguous(unsigned long long dv) const { return cnt != 1 || best == dv; }
+};
+__device__ __forceinline__ ParentPick pick_parent(const DevGraph& g, bool undirected,
+                                                  const unsigned long long* __restrict__ D, int LB, int l, int a0,
+                                                  int a1, unsigned long long dv) {
+    ParentPick k{INF_BITS, INF_BITS, 0, -1};
+    for (int a = a0; a < a1; ++a) {
+        const int u = undirected ? g.col[a] : g.inCol[a];
+        const double w = undirected ? g.lat[a] : g.inLat[a];
+        const unsigned long long du = dec(D[(size_t)u * LB + l]);
+        const double cand = b2d(du) + w;
+        const unsigned long long cb = d2b(cand);
+        k.mn = cb < k.mn ? cb : k.mn;
+        if (dv != INF_BITS && du <= dv && cand == b2d(dv)) {
+            if (du < k.best) {
+                k.best = du;
+                k.cnt = 1;
+                k.arc = a;
+            } else if (du == k.best) {
+                ++k.cnt;
+            }
+        }
+    }
+    return k;
+}
+
 // k_tie_export: the deferred tie export of one round (launch_tie_export).
 // One thread per (slot, vertex), grid-stride: the vertex's distance, and its
 // parent exactly as the post kernel's full predecessor pass derives it (first
@@ -1679,31 +1716,13 @@ __global__ __launch_bounds__(256) void k_tie_export(DevGraph g0, BatchScratch bs
         if (v != src) {
             const int a0 = undirected ? g.rowPtr[v] : g.inPtr[v];
             const int a1 = undirected ? g.rowPtr[v + 1] : g.inPtr[v + 1];
-            unsigned long long best = INF_BITS, mn = INF_BITS;
-            int cnt2 = 0, ba = -1;
-            for (int a = a0; a < a1; ++a) {
-                const int u = undirected ? g.col[a] : g.inCol[a];
-                const double w = undirected ? g.lat[a] : g.inLat[a];
-                const unsigned long long du = dec(D[(size_t)u * LB + l]);
-                const double cand = b2d(du) + w;
-                const unsigned long long cb = d2b(cand);
-                mn = cb < mn ? cb : mn;
-                if (dv != INF_BITS && du <= dv && cand == b2d(dv)) {
-                    if (du < best) {
-                        best = du;
-                        cnt2 = 1;
-                        ba = a;
-                    } else if (du == best) {
-                        ++cnt2;
-                    }
-                }
-            }
-            if (mn < dv || sl == violSlot) rowAmbig[(size_t)b * LB + l] = 1;   // Bellman violation: full emulation
+            const ParentPick k = pick_parent(g, undirected, D, LB, l, a0, a1, dv);
+            if (k.mn < dv || sl == violSlot) rowAmbig[(size_t)b * LB + l] = 1;   // Bellman violation: full emulation
             if (dv != INF_BITS) {
-                const bool ea = cnt2 != 1 || best == dv;
-                pe = ea ? (TIE_AMB | (ba > 0 ? ba : 0)) : ba;
-                if (ea && best != INF_BITS)
-                    atomicMax(reinterpret_cast<unsigned long long*>(as_global(tie.thr) + sl), best);
+                const bool ea = k.ambiguous(dv);
+                pe = ea ? (TIE_AMB | (k.arc > 0 ? k.arc : 0)) : k.arc;
+                if (ea && k.best != INF_BITS)
+                    atomicMax(reinterpret_cast<unsigned long long*>(as_global(tie.thr) + sl), k.best);
             }
         }
         as_global(tie.P)[o] = pe;
@@ -1783,6 +1802,246 @@ void launch_paths_walk_dist(const DevGraph& g, const BatchScratch& bs, const Pat
     if (a.nReqs <= 0) return;
     hipLaunchKernelGGL(k_paths_walk_dist, dim3((unsigned)((a.nReqs + 255) / 256)), dim3(256), 0,
                        reinterpret_cast<hipStream_t>(stream), g, bs, a);
+}
+
+// k_tree_load (shd_pe_table_load, launch_tree_load): the all-pairs load of the
+// sources of one round of the split kernels, from the round's persisted
+// distance arrays after its post kernel and tie export.  The shortest paths of
+// a source form a tree, the load of a vertex is the weight seeded in its
+// subtree and the load of its parent arc is the same number, so every parent is
+// derived once per (source, vertex) and one leaves-first sum replaces T walks.
+//
+// Persistent workgroups, one batch at a time, each with a private scratch slot
+// of (parent, sum, pending children) per (vertex, lane) that it reuses for its
+// next batch.  Per batch, with a workgroup barrier between the steps:
+//   init    the slot: unclaimed, 0, 0; per lane whether it runs at all (a pad,
+//           a lane the pass flagged: not started)
+//   seed    per (destination, lane): status and hops from the table row ->
+//           the lane's totals and expected sum; a status-0 destination of
+//           non-zero weight adds its weight to its vertex and
+//   claim   walks up from it until it meets a claimed vertex: each vertex it
+//           claims derives its parent (pick_parent) and counts itself as that
+//           parent's child.  Equal minima, a zero-increment arc, a Bellman
+//           violation, an infinite distance or hops the table cannot hold fail
+//           the lane
+//   sum     a scan offers every claimed entry with no pending child; who takes
+//           an entry (compare-and-swap 0 -> TREE_TAKEN on its pending count)
+//           adds its sum to the parent's, counts down the parent's pending
+//           children and, on the last, offers the parent in the same way
+//   check   a lane passes when it did not fail and its source's sum is the
+//           expected one; any other started lane is handed on (handed = 1)
+//   commit  one thread per vertex: the passing lanes' sums, those that share
+//           the parent combined first, added to the vertex's place in acc and
+//           to the place of the arc from the parent (caller's ids, find_arc as
+//           k_paths_load finds it) with device-scope no-return 64-bit adds.
+//           Within a batch the places of different vertices differ, so this
+//           combining is all there is to combine.
+// Nothing reaches acc or the totals before the lane's check.  The slot's
+// atomics are workgroup traffic (workgroup scope); the sums are integers mod
+// 2^64, so every order gives the same result.
+constexpr int TREE_THREADS = 512;
+constexpr int32_t TREE_FREE = -1, TREE_SOURCE = -2, TREE_BUSY = -3;   // parent words that are no in-arc
+constexpr int32_t TREE_TAKEN = -1;                                    // pending word of a summed entry
+
+__device__ __forceinline__ void tree_add(unsigned long long* p, unsigned long long v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+__global__ __launch_bounds__(TREE_THREADS) void k_tree_load(DevGraph g0, DevGraph aux0, DevTable tab0,
+                                                            BatchScratch bs, TreeLoadArgs p) {
+    __shared__ unsigned long long expect[32], tot[32][3], issuedWg, claimedWg;
+    __shared__ unsigned int bad[32];             // requests with a status
+    __shared__ int srcOf[32], posOf[32], run[32], fail[32], pass[32];
+    const DevGraph g = global_view(g0);
+    const DevGraph aux = global_view(aux0);
+    const DevTable tab = global_view(tab0);
+    const int tid = threadIdx.x, n = g.n, LB = p.lb;
+    const int64_t T = tab.T;
+    const bool undirected = g.inCol == g.col;
+    const size_t SE = (size_t)bs.nStride * LB, NE = (size_t)n * LB;
+    int32_t* __restrict__ par = as_global(p.par) + (size_t)blockIdx.x * NE;
+    unsigned long long* __restrict__ sum = (unsigned long long*)as_global(p.sum) + (size_t)blockIdx.x * NE;
+    int32_t* __restrict__ pend = as_global(p.pend) + (size_t)blockIdx.x * NE;
+    const int32_t* __restrict__ attDev = as_global(p.attDev);
+    unsigned long long* __restrict__ acc = (unsigned long long*)as_global(p.acc);
+    unsigned long long* __restrict__ out = (unsigned long long*)as_global(p.out);
+    if (tid == 0) issuedWg = claimedWg = 0;
+    for (int b = blockIdx.x; b < p.nBatches; b += gridDim.x) {
+        const unsigned long long* __restrict__ D = as_global(bs.D) + (size_t)b * SE;
+        const unsigned long long* __restrict__ W =
+            p.weight ? (const unsigned long long*)as_global(p.weight) + (size_t)b * LB * (size_t)T : nullptr;
+        // ---- init
+        if (tid < LB) {
+            const int pos = as_global(p.batchRows)[b * LB + tid];
+            posOf[tid] = pos;
+            run[tid] = pos >= 0 && as_global(p.rowAmbig)[b * LB + tid] == 0;
+            srcOf[tid] = pos >= 0 ? attDev[pos] : -1;
+            fail[tid] = pass[tid] = 0;
+            expect[tid] = tot[tid][0] = tot[tid][1] = tot[tid][2] = 0;
+            bad[tid] = 0;
+        }
+        for (size_t i = tid; i < NE; i += TREE_THREADS) {
+            par[i] = TREE_FREE;
+            sum[i] = 0;
+            pend[i] = 0;
+        }
+        fence_wg();
+        __syncthreads();
+        // ---- seed and claim
+        for (size_t i = tid; i < (size_t)T * LB; i += TREE_THREADS) {
+            const int q = (int)(i / LB), l = (int)(i % LB);
+            if (!run[l]) continue;
+            const int pos = posOf[l], src = srcOf[l];
+            unsigned long long hops = 0;
+            if (q != pos) {
+                const size_t cell = (size_t)(pos - tab.rowStart) * (size_t)T + (size_t)q;
+                if (tab.flags[cell] & (F_UNREACHABLE | F_NOEDGE)) {
+                    atomicAdd(&bad[l], 1u);
+                    continue;
+                }
+                const int h = tab.hops[cell];
+                if (h < 1 || h >= n) {           // (not a table this engine wrote: the request route says so)
+                    fail[l] = 1;
+                    continue;
+                }
+                hops = (unsigned long long)h;
+            }
+            const unsigned long long w = W ? W[(size_t)l * (size_t)T + q] : 1ull;
+            atomicAdd(&tot[l][0], 1ull);
+            if (w == 0) continue;                // adds nothing anywhere
+            atomicAdd(&tot[l][1], w * (hops + 1));
+            atomicAdd(&tot[l][2], w * hops);
+            atomicAdd(&expect[l], w);
+            int x = attDev[q];
+            tree_add(&sum[(size_t)x * LB + l], w);
+            const bool spoil = p.corrupt == 2 && b * LB + l == p.corruptSlot;
+            while (!*(volatile int*)&fail[l]) {
+                const size_t e = (size_t)x * LB + l;
+                int32_t was = TREE_FREE;
+                if (!__hip_atomic_compare_exchange_strong(&par[e], &was, TREE_BUSY, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_WORKGROUP))
+                    break;                       // claimed already: the rest of the way is too
+                const unsigned long long dv = dec(D[e]);
+                if (x == src) {
+                    if (dv != 0ull) fail[l] = 1;
+                    __hip_atomic_store(&par[e], TREE_SOURCE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                    break;
+                }
+                const int a0 = undirected ? g.rowPtr[x] : g.inPtr[x];
+                const int a1 = undirected ? g.rowPtr[x + 1] : g.inPtr[x + 1];
+                const ParentPick k = pick_parent(g, undirected, D, LB, l, a0, a1, dv);
+                if (dv == INF_BITS || k.mn < dv || k.ambiguous(dv) || spoil) {
+                    fail[l] = 1;
+                    break;
+                }
+                const int u = g.inCol[k.arc];    // (undirected: inCol is col)
+                __hip_atomic_store(&par[e], k.arc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                __hip_atomic_fetch_add(&pend[(size_t)u * LB + l], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                x = u;                           // (dist[u] < dist[x]: the walk ends)
+            }
+        }
+        fence_wg();
+        __syncthreads();
+        // ---- sum, leaves first
+        for (size_t i = tid; i < NE; i += TREE_THREADS) {
+            const int l = (int)(i % LB);
+            if (!run[l] || fail[l]) continue;
+            const int32_t pa0 = ld_wg(&par[i]);
+            if (pa0 == TREE_FREE || pa0 == TREE_BUSY) continue;
+            size_t e = i;
+            for (;;) {
+                int32_t zero = 0;
+                if (!__hip_atomic_compare_exchange_strong(&pend[e], &zero, TREE_TAKEN, __ATOMIC_ACQUIRE,
+                                                          __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP))
+                    break;                       // children pending, or taken by another thread
+                const int32_t pa = ld_wg(&par[e]);
+                if (pa < 0) break;               // the source: its sum stays for the check
+                // (the entry's sum is final: every child added before it counted down)
+                const unsigned long long s = __hip_atomic_fetch_add(&sum[e], 0ull, __ATOMIC_RELAXED,
+                                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
+                const size_t eu = (size_t)g.inCol[pa] * LB + l;
+                tree_add(&sum[eu], s);
+                if (__hip_atomic_fetch_sub(&pend[eu], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) != 1) break;
+                e = eu;
+            }
+        }
+        fence_wg();
+        __syncthreads();
+        // ---- check
+        if (tid < LB && run[tid]) {
+            const int l = tid;
+            unsigned long long want = expect[l];
+            if (p.corrupt == 1 && b * LB + l == p.corruptSlot) want += 1;
+            const unsigned long long got = __hip_atomic_fetch_add(&sum[(size_t)srcOf[l] * LB + l], 0ull, __ATOMIC_RELAXED,
+                                                                  __HIP_MEMORY_SCOPE_WORKGROUP);
+            const bool ok = !fail[l] && got == want;
+            pass[l] = ok;
+            as_global(p.handed)[b * LB + l] = ok ? 0 : 1;
+            if (ok) {
+                __hip_atomic_fetch_add(&out[0], tot[l][0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(&out[1], tot[l][1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(&out[2], tot[l][2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(&out[3], (unsigned long long)bad[l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                __hip_atomic_fetch_add(&out[4], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            }
+        }
+        __syncthreads();
+        // ---- commit
+        unsigned long long issued = 0, claimed = 0;
+        for (int v = tid; v < n; v += TREE_THREADS) {
+            const size_t e0 = (size_t)v * LB;
+            unsigned long long vsum = 0;
+            unsigned int todo = 0;               // passing lanes with a parent arc, not yet combined
+            for (int l = 0; l < LB; ++l) {
+                if (!pass[l]) continue;
+                const int32_t pa = ld_wg(&par[e0 + l]);
+                if (pa == TREE_FREE || pa == TREE_BUSY) continue;
+                ++claimed;
+                vsum += ld_wg(&sum[e0 + l]);
+                if (pa >= 0) todo |= 1u << l;
+            }
+            if (todo == 0 && vsum == 0) continue;
+            const int ov = g.oldId ? g.oldId[v] : v;
+            if (vsum) {
+                __hip_atomic_fetch_add(acc + p.nArcs + ov, vsum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ++issued;
+            }
+            while (todo) {
+                const int l = __ffs(todo) - 1;
+                const int32_t pa = ld_wg(&par[e0 + l]);
+                unsigned long long asum = 0;
+                for (int m = l; m < LB; ++m)
+                    if (((todo >> m) & 1u) && ld_wg(&par[e0 + m]) == pa) {
+                        asum += ld_wg(&sum[e0 + m]);
+                        todo &= ~(1u << m);
+                    }
+                if (asum == 0) continue;
+                const int u = g.inCol[pa];
+                const int ou = g.oldId ? g.oldId[u] : u;
+                int a = -1;
+                if (ou != ov && find_arc(aux, ou, ov, &a)) {
+                    __hip_atomic_fetch_add(acc + a, asum, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    ++issued;
+                } else {                         // (never: a parent arc is an arc of the graph)
+                    __hip_atomic_fetch_add(&out[7], 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                }
+            }
+        }
+        if (claimed) atomicAdd(&claimedWg, claimed);
+        if (issued) atomicAdd(&issuedWg, issued);
+        __syncthreads();                         // the slot is free for the next batch
+    }
+    if (tid == 0) {
+        if (claimedWg) __hip_atomic_fetch_add(&out[5], claimedWg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        if (issuedWg) __hip_atomic_fetch_add(&out[6], issuedWg, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+}
+
+void launch_tree_load(const DevGraph& g, const DevGraph& gAux, const DevTable& tab, const BatchScratch& bs,
+                      const TreeLoadArgs& a, int grid, void* stream) {
+    if (a.nBatches <= 0 || grid <= 0) return;
+    hipLaunchKernelGGL(k_tree_load, dim3((unsigned)(grid < a.nBatches ? grid : a.nBatches)), dim3(TREE_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream), g, gAux, tab, bs, a);
 }
 
 int batch_threads(int wpe) { return wpe == 6 ? 768 : BT_THREADS; }

@@ -160,6 +160,9 @@ struct Tuning {
     int pathsChunk = 0;        // ... requests per staging chunk (0: 65,536)
     int pathsFast = 1;         // ... 0: no batch / tie / row tier, every source by the grouped emulation
     int loadSort = 1;          // shd_pe_path_load: 0 keeps the caller's request order (no sort by source)
+    int tloadTree = 1;         // shd_pe_table_load: 0 = no tree tier, every source by the request route
+    int tloadCorrupt = 0;      // tests only: 1 the first source's expected total is off by one, 2 its first
+                               // claimed vertex counts as ambiguous (both: the tree tier hands the source on)
     int loadSlots = 2048;      // ... the reduction's LDS table size (rounded down to a power of two in [8, 2048])
     int predFilter = 1;        // on-demand predecessor pass reads only the in-arcs the relax
                                // flagged (0: every in-arc, BatchScratch::arcHit stays null)
@@ -460,6 +463,40 @@ struct PathsDistArgs {
     uint8_t* failed;         // [count] 1: handed on to the emulation
 };
 void launch_paths_walk_dist(const DevGraph& g, const BatchScratch& bs, const PathsDistArgs& a, void* stream);
+// shd_pe_table_load's tree tier (pe_batch.hip, k_tree_load): the all-pairs load
+// of the sources of one round of the split kernels, over the round's persisted
+// distance arrays.  Entry i of the round is batch i / lb, lane i % lb.
+struct TreeLoadArgs {
+    const int32_t* batchRows;   // the round's [nBatches * lb] table positions (-1 pads)
+    const uint8_t* rowAmbig;    // the round's ambiguity bytes (non-zero: not started)
+    int32_t nBatches, lb;
+    const int32_t* attDev;      // [T] table position -> its vertex in the ids of the path kernels' graph
+    const uint64_t* weight;     // [nBatches * lb][T] the weight rows of the round's entries; null: 1
+    int32_t* par;               // [grid][n * lb] scratch slots: parent in-arc ...
+    uint64_t* sum;              // ... subtree sum ...
+    int32_t* pend;              // ... children that have not arrived
+    int64_t nArcs;
+    uint64_t* acc;              // [nArcs + n] caller's ids, as PathsLoadArgs::acc
+    uint8_t* handed;            // the round's [nBatches * lb]: 1 = started and handed on after a check
+    uint64_t* out;              // [8] added to: totals[0..3] of the sources served, [4] those sources,
+                                // [5] entries claimed by them, [6] global adds issued, [7] commit errors
+    int32_t corrupt;            // tests: 1 / 2 (SHDPE_TLOAD_CORRUPT) on the round's entry corruptSlot
+    int32_t corruptSlot;        // (-1: none)
+};
+// grid: scratch slots (workgroups) to use, at most
+void launch_tree_load(const DevGraph& g, const DevGraph& gAux, const DevTable& tab, const BatchScratch& bs,
+                      const TreeLoadArgs& a, int grid, void* stream);
+// ... and its direct kernel for complete graphs (pe_aux.hip): rows [row0, row0 +
+// rows) of the pair matrix, every path [s, t] (or [s]), one thread per pair
+struct TableDirectArgs {
+    const int32_t* attached;    // [T] caller's ids
+    int32_t T, row0, rows;
+    const uint64_t* weight;     // [rows][T]; null: 1
+    int64_t nArcs;
+    uint64_t* acc;              // [nArcs + n]
+    uint64_t* out;              // [4] totals, added to
+};
+void launch_table_direct(const DevGraph& gAux, const TableDirectArgs& a, void* stream);
 // the same walk over converged min-plus distance rows (pe_dense.hip), a wave per
 // request: PathReq::slot = the source's row of D
 struct PathsDenseArgs {

@@ -86,4 +86,26 @@ __device__ __forceinline__ T ld_wg(T* p) {
 }
 __device__ __forceinline__ void fence_wg() { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "workgroup"); }
 
+// Arc lookups on a graph in the caller's ids (rows sorted by neighbour id),
+// shared by the aux kernels and the table-load commit.
+// first arc of row s with col >= t (igraph_get_eid on a sorted incidence row)
+__device__ __forceinline__ int row_lower_bound(const DevGraph& g, int s, int t) {
+    int lo = g.rowPtr[s], hi = g.rowPtr[s + 1];
+    while (lo < hi) {
+        const int mid = lo + ((hi - lo) >> 1);
+        if (g.col[mid] < t) lo = mid + 1;
+        else hi = mid;
+    }
+    return lo;
+}
+
+// _topology_verticesAreAdjacent: an arc s -> t exists (s == t: a self-loop);
+// *arc = its CSR index (unset for s == t)
+__device__ __forceinline__ bool find_arc(const DevGraph& g, int s, int t, int* arc) {
+    if (s == t) return g.hasSelf[s] != 0;
+    const int a = row_lower_bound(g, s, t);
+    *arc = a;
+    return a < g.rowPtr[s + 1] && g.col[a] == t;
+}
+
 }  // namespace shdpe

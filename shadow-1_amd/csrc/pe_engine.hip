@@ -101,6 +101,8 @@ static void read_tuning(Tuning& t, int32_t flags) {
     gi("SHDPE_PATHS_FAST", t.pathsFast);
     gi("SHDPE_LOAD_SORT", t.loadSort);
     gi("SHDPE_LOAD_SLOTS", t.loadSlots);
+    gi("SHDPE_TLOAD_TREE", t.tloadTree);
+    gi("SHDPE_TLOAD_CORRUPT", t.tloadCorrupt);
 }
 
 extern "C" void shd_pe_default_options(ShdPeOptions* opt) {
@@ -2712,22 +2714,20 @@ extern "C" int shd_pe_get_paths(ShdPe* pe, const int32_t* src, const int32_t* ds
 
 // shd_pe_get_paths' pipeline up to the end of the tiers, with the requests
 // ordered by the table position of their source (SHDPE_LOAD_SORT=0: as given)
-// and a reduction in the copy-out's place.
-extern "C" int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* dst, const uint64_t* weight,
-                                int64_t count, const ShdPeLoadOut* out) {
-    if (!pe || !out || count < 0 || (count > 0 && (!src || !dst))) return SHD_PE_EINVAL;
-    std::lock_guard<std::mutex> lk(pe->mu);
-    for (int64_t& x : pe->pathsInfo) x = 0;
-    pe->loadInfo[0] = pe->loadInfo[1] = 0;
+// and a reduction in the copy-out's place.  The caller holds pe->mu and has
+// zeroed the call's info words; the sums (nArcs + n), the totals and the info
+// words are added to (shd_pe_table_load's request route runs this per block of
+// sources), status[i] is written where given.
+static int path_load_locked(ShdPe* pe, const int32_t* src, const int32_t* dst, const uint64_t* weight,
+                            int64_t count, std::vector<uint64_t>& sum, uint64_t tot[4], int32_t* status) {
     const HostGraph& g = pe->hg;
     const size_t nArcs = (size_t)g.nArcs(), nAcc = nArcs + (size_t)g.n;
-    uint64_t tot[4] = {0, 0, 0, 0};
-    std::vector<uint64_t> sum, part, w;                  // the sums; one shard's; the weights in run order
+    std::vector<uint64_t> part, w;                       // one shard's sums; the weights in run order
     std::vector<int64_t> order, offsets;
     std::vector<int32_t> ssrc, sdst, stat;
+    if (count == 0) return SHD_PE_OK;
     try {                                                // (every host array of the call: 44 B per request)
-        sum.assign(nAcc, 0);
-        part.resize(count > 0 ? nAcc : 0);
+        part.resize(nAcc);
         w.resize((size_t)count);
         order.resize((size_t)count);
         offsets.assign((size_t)count + 1, 0);
@@ -2736,15 +2736,6 @@ extern "C" int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* ds
         stat.resize((size_t)count);
     } catch (const std::bad_alloc&) {
         return SHD_PE_ENOMEM;
-    }
-    auto write_out = [&]() {
-        if (out->arcLoad) std::memcpy(out->arcLoad, sum.data(), nArcs * 8);
-        if (out->vertexLoad) std::memcpy(out->vertexLoad, sum.data() + nArcs, (size_t)g.n * 8);
-        if (out->totals) std::memcpy(out->totals, tot, 32);
-    };
-    if (count == 0) {
-        write_out();
-        return SHD_PE_OK;
     }
     // a source's pass runs once where its requests share a chunk: by table position, the
     // requests without one (bad ids, unattached) last
@@ -2772,7 +2763,7 @@ extern "C" int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* ds
     c.weight = w.data();
     paths_call_init(pe, c, count);
     auto finish = [&](int r) {
-        pe->pathsInfo[5] = (int64_t)std::llround(c.ms * 1000.0);
+        pe->pathsInfo[5] += (int64_t)std::llround(c.ms * 1000.0);
         return r;
     };
     if ((rc = paths_size_all(pe, c, count, offsets.data(), stat.data())) ||
@@ -2792,10 +2783,10 @@ extern "C" int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* ds
             pe->loadInfo[1] += (int64_t)issued;
         }
     }
-    pe->loadInfo[0] = offsets[(size_t)count];
+    pe->loadInfo[0] += offsets[(size_t)count];
     for (int64_t i = 0; i < count; ++i) {
         const uint64_t L = (uint64_t)(offsets[(size_t)i + 1] - offsets[(size_t)i]);
-        if (out->status) out->status[order[(size_t)i]] = stat[(size_t)i];
+        if (status) status[order[(size_t)i]] = stat[(size_t)i];
         if (stat[(size_t)i] != SHD_PE_OK) {
             tot[3] += 1;
             continue;
@@ -2804,8 +2795,328 @@ extern "C" int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* ds
         tot[1] += w[(size_t)i] * L;
         tot[2] += w[(size_t)i] * (L - 1);
     }
-    write_out();
     return finish(SHD_PE_OK);
+}
+
+// The sums of a load call to the caller's arrays (overwritten, each where given).
+static void load_write_out(const ShdPe* pe, const ShdPeLoadOut* out, const std::vector<uint64_t>& sum,
+                           const uint64_t tot[4]) {
+    const size_t nArcs = (size_t)pe->hg.nArcs();
+    if (out->arcLoad) std::memcpy(out->arcLoad, sum.data(), nArcs * 8);
+    if (out->vertexLoad) std::memcpy(out->vertexLoad, sum.data() + nArcs, (size_t)pe->hg.n * 8);
+    if (out->totals) std::memcpy(out->totals, tot, 32);
+}
+
+extern "C" int shd_pe_path_load(ShdPe* pe, const int32_t* src, const int32_t* dst, const uint64_t* weight,
+                                int64_t count, const ShdPeLoadOut* out) {
+    if (!pe || !out || count < 0 || (count > 0 && (!src || !dst))) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(pe->mu);
+    for (int64_t& x : pe->pathsInfo) x = 0;
+    pe->loadInfo[0] = pe->loadInfo[1] = 0;
+    uint64_t tot[4] = {0, 0, 0, 0};
+    std::vector<uint64_t> sum;
+    try {
+        sum.assign((size_t)pe->hg.nArcs() + (size_t)pe->hg.n, 0);
+    } catch (const std::bad_alloc&) {
+        return SHD_PE_ENOMEM;
+    }
+    const int rc = path_load_locked(pe, src, dst, weight, count, sum, tot, out->status);
+    if (rc) return rc;
+    load_write_out(pe, out, sum, tot);
+    return SHD_PE_OK;
+}
+
+// ---- shd_pe_table_load: all-pairs load of a range of source rows --
+namespace {
+
+struct PinnedBuf {
+    void* p = nullptr;
+    ~PinnedBuf() { if (p) (void)hipHostFree(p); }
+    int get(size_t bytes) { return hipHostMalloc(&p, std::max<size_t>(16, bytes), hipHostMallocDefault) == hipSuccess ? SHD_PE_OK : SHD_PE_ENOMEM; }
+};
+struct OwnedEvent {
+    hipEvent_t e = nullptr;
+    bool recorded = false;
+    ~OwnedEvent() { if (e) (void)hipEventDestroy(e); }
+};
+
+// What the tiers of one shd_pe_table_load call add to.
+struct TableLoad {
+    const ShdPeTableLoadIn* in;
+    int64_t T;
+    std::vector<uint64_t> sum;           // nArcs + n
+    uint64_t tot[4] = {0, 0, 0, 0};
+    std::vector<int32_t> rest;           // the table positions left to the request route
+    double ms = 0.0;                     // device time of the tree tier and the direct kernel
+    const uint64_t* row(int32_t p) const { return in->weight + (size_t)(p - in->start) * (size_t)in->ld; }
+};
+
+constexpr int64_t TLOAD_SCRATCH_BYTES = (int64_t)8 << 30;    // the tree tier's slots, at most
+constexpr int64_t TLOAD_BLOCK_REQS = (int64_t)1 << 22;       // requests per block of the request route
+constexpr int64_t TLOAD_DIRECT_BYTES = (int64_t)64 << 20;    // weight rows per block of the direct kernel
+
+}  // namespace
+
+// A device accumulator of the call (nArcs + n sums) added into the host's.
+static int tload_add_acc(Shard* sh, const uint64_t* dAcc, std::vector<uint64_t>& sum) {
+    std::vector<uint64_t> part(sum.size());
+    HIPCHK(hipMemcpyAsync(part.data(), dAcc, part.size() * 8, hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipStreamSynchronize(sh->stream));
+    for (size_t i = 0; i < part.size(); ++i) sum[i] += part[i];
+    return SHD_PE_OK;
+}
+
+// Direct kernel, complete graphs: every path is the edge (the primary shard, as for shd_pe_get_paths).
+static int tload_direct(ShdPe* pe, TableLoad& c) {
+    Shard* sh = pe->shards[0].get();
+    const ShdPeTableLoadIn* in = c.in;
+    const int64_t T = c.T;
+    const size_t nAcc = c.sum.size();
+    HIPCHK(hipSetDevice(sh->device));
+    PathsStage s;
+    s.device = sh->device;
+    PinnedBuf host;
+    OwnedEvent up;
+    int32_t* dAtt = nullptr;
+    uint64_t *dAcc = nullptr, *dOut = nullptr, *dW = nullptr;
+    const int32_t blockRows = (int32_t)std::min<int64_t>({(int64_t)in->count, 65535, std::max<int64_t>(1, TLOAD_DIRECT_BYTES / (8 * T))});
+    int rc;
+    if ((rc = s.get(&dAtt, (size_t)T)) || (rc = s.get(&dAcc, nAcc)) || (rc = s.get(&dOut, 4))) return rc;
+    if (in->weight) {
+        if ((rc = s.get(&dW, (size_t)blockRows * (size_t)T)) || (rc = host.get((size_t)blockRows * (size_t)T * 8))) return rc;
+        HIPCHK(hipEventCreateWithFlags(&up.e, hipEventDisableTiming));
+    }
+    HIPCHK(hipMemcpyAsync(dAtt, pe->attached.data(), (size_t)T * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemsetAsync(dAcc, 0, nAcc * 8, sh->stream));
+    HIPCHK(hipMemsetAsync(dOut, 0, 32, sh->stream));
+    HIPCHK(hipEventRecord(sh->ev0, sh->stream));
+    for (int32_t r0 = 0; r0 < in->count; r0 += blockRows) {
+        const int32_t rn = std::min(blockRows, in->count - r0);
+        if (in->weight) {
+            if (up.recorded) HIPCHK(hipEventSynchronize(up.e));          // the staging is free again
+            for (int32_t r = 0; r < rn; ++r)
+                std::memcpy((uint64_t*)host.p + (size_t)r * (size_t)T, c.row(in->start + r0 + r), (size_t)T * 8);
+            HIPCHK(hipMemcpyAsync(dW, host.p, (size_t)rn * (size_t)T * 8, hipMemcpyHostToDevice, sh->stream));
+            HIPCHK(hipEventRecord(up.e, sh->stream));
+            up.recorded = true;
+        }
+        launch_table_direct(sh->dgAux, TableDirectArgs{dAtt, (int32_t)T, in->start + r0, rn, dW, pe->hg.nArcs(), dAcc, dOut},
+                            sh->stream);
+        HIPCHK(hipGetLastError());
+    }
+    HIPCHK(hipEventRecord(sh->ev1, sh->stream));
+    uint64_t out[4];
+    HIPCHK(hipMemcpyAsync(out, dOut, 32, hipMemcpyDeviceToHost, sh->stream));
+    if ((rc = tload_add_acc(sh, dAcc, c.sum))) return rc;
+    c.ms += elapsed(sh->ev0, sh->ev1);
+    for (int i = 0; i < 4; ++i) c.tot[i] += out[i];
+    pe->tloadInfo[1] += in->count;
+    return SHD_PE_OK;
+}
+
+// Where paths_tier_batch applies (the split batch kernels), and the tier is on.
+static bool tload_tree_applies(const ShdPe* pe) {
+    return pe->tu.tloadTree && pe->tu.pathsFast && pe->mode == 1 && pe->batched && pe->opt.forceMode != 3 &&
+           !pe->hg.latFold;
+}
+
+// Tree tier over the table positions [lo, hi) of shard k: one pass of the split
+// kernels that stores no row, as paths_tier_batch runs it, and after each
+// round's post kernel and tie export one k_tree_load over the round's batches.
+// The round's weight rows go up through page-locked staging while its relax
+// runs.  Left to the request route (c.rest): the rows the pass flagged and the
+// sources the kernel handed on.
+static int tload_tree_shard(ShdPe* pe, size_t k, int32_t lo, int32_t hi, TableLoad& c) {
+    Shard* sh = pe->shards[k].get();
+    const ShdPeTableLoadIn* in = c.in;
+    const size_t T = (size_t)c.T, nAcc = c.sum.size(), n = (size_t)pe->hg.n;
+    int rc;
+    auto all_rest = [&]() {
+        for (int32_t p = lo; p < hi; ++p) c.rest.push_back(p);
+        return SHD_PE_OK;
+    };
+    HIPCHK(hipSetDevice(sh->device));
+    if (!sh->plan.relax.split) return all_rest();
+    if ((rc = ensure_table(pe, sh)) || (rc = ensure_batch(pe, sh))) return rc;
+    if (!sh->plan.relax.split) return all_rest();
+    BatchTrial trial;   // the plan's picks, as paths_tier_batch
+    trial.relax = sh->plan.relax;
+    trial.post = sh->plan.postSplit ? sh->plan.redo : sh->plan.post;
+    trial.noTable = true;
+    const int32_t LB = trial.relax.lb;
+    std::vector<int32_t> pos((size_t)(hi - lo));
+    for (int32_t p = lo; p < hi; ++p) pos[(size_t)(p - lo)] = p;
+    int32_t nB = 0;
+    const std::vector<int32_t> order = batch_order(pe->rank, pe->rowOff, LB, pos.data(), (int32_t)pos.size(), nB);
+    const int32_t roundCap = std::min(sh->batchRound, nB);
+    int64_t firstAt = -1;                // the call's first source in `order` (the debug switches' target)
+    for (size_t i = 0; i < order.size() && pe->tu.tloadCorrupt; ++i)
+        if (order[i] == in->start) firstAt = (int64_t)i;
+    // scratch slots: one per workgroup, (parent, sum, pending) per (vertex, lane)
+    const int64_t slotBytes = (int64_t)n * LB * 16;
+    int grid = std::max(1, std::min<int>(sh->numCUs, roundCap));
+    grid = (int)std::min<int64_t>(grid, std::max<int64_t>(1, TLOAD_SCRATCH_BYTES / slotBytes));
+    if (pe->tu.batchGrid > 0) grid = std::min(grid, pe->tu.batchGrid);
+    PathsStage s;
+    s.device = sh->device;
+    PinnedBuf host;
+    OwnedEvent up;
+    int32_t *dAttDev = nullptr, *dPar = nullptr, *dPend = nullptr;
+    uint64_t *dAcc = nullptr, *dOut = nullptr, *dSum = nullptr, *dW = nullptr;
+    uint8_t* dHanded = nullptr;
+    const size_t slotEntries = (size_t)grid * n * (size_t)LB, roundW = (size_t)roundCap * (size_t)LB * T;
+    if ((rc = s.get(&dAttDev, T)) || (rc = s.get(&dAcc, nAcc)) || (rc = s.get(&dOut, 8)) ||
+        (rc = s.get(&dHanded, order.size())) || (rc = s.get(&dPar, slotEntries)) || (rc = s.get(&dSum, slotEntries)) ||
+        (rc = s.get(&dPend, slotEntries)))
+        return rc;
+    if (in->weight) {
+        if ((rc = s.get(&dW, roundW)) || (rc = host.get(roundW * 8))) return rc;
+        HIPCHK(hipEventCreateWithFlags(&up.e, hipEventDisableTiming));
+    }
+    std::vector<int32_t> attDev(T);
+    for (size_t q = 0; q < T; ++q) attDev[q] = pe->devOf.empty() ? pe->attached[q] : pe->devOf[(size_t)pe->attached[q]];
+    HIPCHK(hipMemcpyAsync(dAttDev, attDev.data(), T * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemsetAsync(dAcc, 0, nAcc * 8, sh->stream));
+    HIPCHK(hipMemsetAsync(dOut, 0, 64, sh->stream));
+    HIPCHK(hipMemsetAsync(dHanded, 0, order.size(), sh->stream));
+    int64_t rounds = 0;
+    const RoundHook treeRound = [&](int32_t r0, int32_t rn) -> int {
+        const size_t ro = (size_t)r0 * LB, cnt = (size_t)rn * LB;
+        if (in->weight) {
+            if (up.recorded) HIPCHK(hipEventSynchronize(up.e));          // the staging is free again
+            for (size_t i = 0; i < cnt; ++i)
+                if (order[ro + i] >= 0) std::memcpy((uint64_t*)host.p + i * T, c.row(order[ro + i]), T * 8);
+            HIPCHK(hipMemcpyAsync(dW, host.p, cnt * T * 8, hipMemcpyHostToDevice, sh->stream));
+            HIPCHK(hipEventRecord(up.e, sh->stream));
+            up.recorded = true;
+        }
+        const bool here = firstAt >= (int64_t)ro && firstAt < (int64_t)(ro + cnt);
+        const TreeLoadArgs a{sh->dBatchRows + ro, sh->dBatchAmb + ro, rn, LB, dAttDev, dW, dPar, dSum, dPend,
+                             pe->hg.nArcs(), dAcc, dHanded + ro, dOut, here ? pe->tu.tloadCorrupt : 0,
+                             here ? (int32_t)(firstAt - (int64_t)ro) : -1};
+        launch_tree_load(sh->dg, sh->dgAux, sh->tab, sh->bsc, a, grid, sh->stream);
+        HIPCHK(hipGetLastError());
+        ++rounds;
+        return SHD_PE_OK;
+    };
+    ExactWork x;
+    const ShdPeStats savedStats = sh->stats;
+    const int64_t savedRounds[2] = {sh->roundsRun, sh->batchesRun};
+    HIPCHK(hipEventRecord(sh->ev0, sh->stream));
+    rc = relax_batched(pe, sh, pos.data(), (int32_t)pos.size(), x, &trial, &order, &treeRound);
+    sh->stats = savedStats;
+    sh->roundsRun = savedRounds[0];
+    sh->batchesRun = savedRounds[1];
+    if (rc) return rc;
+    HIPCHK(hipEventRecord(sh->ev1, sh->stream));
+    std::vector<uint8_t> handed(order.size());
+    uint64_t out[8];
+    HIPCHK(hipMemcpyAsync(handed.data(), dHanded, handed.size(), hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipMemcpyAsync(out, dOut, 64, hipMemcpyDeviceToHost, sh->stream));
+    if ((rc = tload_add_acc(sh, dAcc, c.sum))) return rc;
+    c.ms += elapsed(sh->ev0, sh->ev1);
+    if (out[7]) return SHD_PE_EHIP;      // a parent arc the graph does not hold: never
+    for (int i = 0; i < 4; ++i) c.tot[i] += out[i];
+    int64_t nHanded = 0;
+    for (int32_t p : x.rows) c.rest.push_back(p);
+    for (size_t i = 0; i < order.size(); ++i)
+        if (order[i] >= 0 && handed[i]) {
+            c.rest.push_back(order[i]);
+            ++nHanded;
+        }
+    if ((int64_t)out[4] + nHanded + (int64_t)x.rows.size() != (int64_t)pos.size()) return SHD_PE_EHIP;
+    pe->tloadInfo[0] += (int64_t)out[4];
+    pe->tloadInfo[3] += nHanded;
+    pe->tloadInfo[4] += (int64_t)out[5];
+    pe->tloadInfo[6] += rounds;
+    if (pe->tu.debug) pe->tloadInfo[7] += (int64_t)out[6];
+    return SHD_PE_OK;
+}
+
+// Request route: shd_pe_path_load's pipeline on the pairs of the sources left,
+// made here block by block, source-major (so its sort by source moves nothing).
+static int tload_route(ShdPe* pe, TableLoad& c) {
+    const ShdPeTableLoadIn* in = c.in;
+    const int64_t T = c.T;
+    std::sort(c.rest.begin(), c.rest.end());
+    const size_t per = (size_t)std::max<int64_t>(1, TLOAD_BLOCK_REQS / T);
+    std::vector<int32_t> src, dst;
+    std::vector<uint64_t> w;
+    for (size_t b0 = 0; b0 < c.rest.size(); b0 += per) {
+        const size_t bn = std::min(per, c.rest.size() - b0);
+        try {
+            src.resize(bn * (size_t)T);
+            dst.resize(bn * (size_t)T);
+            if (in->weight) w.resize(bn * (size_t)T);
+        } catch (const std::bad_alloc&) {
+            return SHD_PE_ENOMEM;
+        }
+        for (size_t i = 0; i < bn; ++i) {
+            const int32_t p = c.rest[b0 + i];
+            std::fill_n(src.begin() + (ptrdiff_t)(i * (size_t)T), (size_t)T, pe->attached[(size_t)p]);
+            std::copy(pe->attached.begin(), pe->attached.end(), dst.begin() + (ptrdiff_t)(i * (size_t)T));
+            if (in->weight) std::memcpy(w.data() + i * (size_t)T, c.row(p), (size_t)T * 8);
+        }
+        const int rc = path_load_locked(pe, src.data(), dst.data(), in->weight ? w.data() : nullptr,
+                                        (int64_t)(bn * (size_t)T), c.sum, c.tot, nullptr);
+        if (rc) return rc;
+        pe->tloadInfo[2] += (int64_t)bn;
+    }
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_table_load(ShdPe* pe, const ShdPeTableLoadIn* in, const ShdPeLoadOut* out) {
+    if (!pe || !in || !out) return SHD_PE_EINVAL;
+    const int64_t T = (int64_t)pe->attached.size();
+    if (in->start < 0 || in->count < 0 || (int64_t)in->start + in->count > T) return SHD_PE_EINVAL;
+    if (in->weight && in->ld < T) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(pe->mu);
+    const int32_t lo = in->start, hi = in->start + in->count;
+    if (in->count > 0 && pe->mode != 2 && pe->opt.shardCount > 1 && !pe->gathered &&
+        (lo < pe->ownStart || hi > pe->ownEnd))
+        return SHD_PE_ENOTOWNED;
+    for (int64_t& x : pe->pathsInfo) x = 0;
+    for (int64_t& x : pe->tloadInfo) x = 0;
+    pe->loadInfo[0] = pe->loadInfo[1] = 0;
+    TableLoad c;
+    c.in = in;
+    c.T = T;
+    try {
+        c.sum.assign((size_t)pe->hg.nArcs() + (size_t)pe->hg.n, 0);
+    } catch (const std::bad_alloc&) {
+        return SHD_PE_ENOMEM;
+    }
+    int rc = SHD_PE_OK;
+    if (in->count > 0 && pe->mode == 2) {
+        rc = tload_direct(pe, c);
+    } else if (in->count > 0) {
+        std::vector<int32_t> todo;       // rows not yet computed: first
+        for (int32_t p = std::max(lo, pe->ownStart); p < std::min(hi, pe->ownEnd); ++p)
+            if (!row_done(pe, p)) todo.push_back(p);
+        if ((rc = compute_positions_locked(pe, todo.data(), (int32_t)todo.size()))) return rc;
+        std::vector<uint8_t> seen((size_t)in->count, 0);
+        for (size_t k = 0; k < pe->shards.size() && tload_tree_applies(pe); ++k) {
+            const Shard* sh = pe->shards[k].get();
+            const int32_t a = std::max(lo, sh->rowStart), b = std::min(hi, sh->rowStart + sh->rowCount);
+            if (a >= b) continue;
+            if ((rc = tload_tree_shard(pe, k, a, b, c))) return rc;
+            std::fill(seen.begin() + (a - lo), seen.begin() + (b - lo), (uint8_t)1);
+        }
+        for (int32_t p = lo; p < hi; ++p)
+            if (!seen[(size_t)(p - lo)]) c.rest.push_back(p);
+        rc = tload_route(pe, c);
+    }
+    if (rc) return rc;
+    pe->tloadInfo[5] = (int64_t)std::llround(c.ms * 1000.0) + pe->pathsInfo[5];
+    load_write_out(pe, out, c.sum, c.tot);
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_table_load_info(const ShdPe* pe, int64_t* info, int32_t n) {
+    if (!pe || !info || n < 0) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
+    for (int32_t k = 0; k < std::min<int32_t>(n, 8); ++k) info[k] = pe->tloadInfo[k];
+    return SHD_PE_OK;
 }
 
 extern "C" int shd_pe_path_load_info(const ShdPe* pe, int64_t* info, int32_t n) {

@@ -198,6 +198,7 @@ struct ShdPe {
     int64_t pathsInfo[7] = {0, 0, 0, 0, 0, 0, 0};   // shd_pe_paths_info of the last shd_pe_get_paths
     bool pathsRowTier = false;       // shd_pe_paths_set_row_tier
     int64_t loadInfo[2] = {0, 0};    // shd_pe_path_load_info of the last shd_pe_path_load
+    int64_t tloadInfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // shd_pe_table_load_info of the last shd_pe_table_load
 };
 
 #define HIPCHK(x)                                   \

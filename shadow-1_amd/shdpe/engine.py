@@ -58,6 +58,7 @@ EXPORTS = [
     "shd_pe_paths_set_row_tier",
     "shd_pe_num_arcs", "shd_pe_arc_list", "shd_pe_find_arc", "shd_pe_path_load",
     "shd_pe_path_load_info", "shd_topology_link_load",
+    "shd_pe_table_load", "shd_pe_table_load_info",
 ]
 VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
 VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
@@ -133,6 +134,11 @@ class LoadOutC(C.Structure):
     """ShdPeLoadOut"""
     _fields_ = [("arcLoad", C.c_void_p), ("vertexLoad", C.c_void_p), ("status", C.c_void_p),
                 ("totals", C.c_void_p)]
+
+
+class TableLoadInC(C.Structure):
+    """ShdPeTableLoadIn"""
+    _fields_ = [("start", C.c_int32), ("count", C.c_int32), ("weight", C.c_void_p), ("ld", C.c_int64)]
 
 
 class GraphPropsC(C.Structure):
@@ -273,6 +279,8 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_path_load": (C.c_int, [vp, vp, vp, vp, i64, vp]),
         "shd_topology_link_load": (C.c_int, [vp, vp]),
         "shd_pe_path_load_info": (C.c_int, [vp, vp, i32]),
+        "shd_pe_table_load": (C.c_int, [vp, vp, vp]),
+        "shd_pe_table_load_info": (C.c_int, [vp, vp, i32]),
     }
     # ABI-3 ... ABI-8 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
@@ -287,7 +295,8 @@ def load_library(path: str = LIB_PATH):
                 "shd_pe_graph_digest", "shd_pe_post_split_info",
                 "shd_pe_batch_info", "shd_pe_sparse_info", "shd_pe_paths_set_row_tier", "shd_pe_num_arcs",
                 "shd_pe_arc_list", "shd_pe_find_arc", "shd_pe_path_load",
-                "shd_pe_path_load_info", "shd_topology_link_load"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_pe_path_load_info", "shd_topology_link_load",
+                "shd_pe_table_load", "shd_pe_table_load_info"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -710,6 +719,41 @@ class Engine:
         info = np.zeros(2, np.int64)
         self._chk(self._lib.shd_pe_path_load_info(self.h, _p(info), 2), "shd_pe_path_load_info")
         return {"entries": int(info[0]), "atomics": int(info[1])}
+
+    def table_load(self, start=0, count=None, weight=None) -> dict:
+        """shd_pe_table_load: path_load of every pair (attached[p], attached[q])
+        for p in [start, start + count) (count None: to the last row) and every q,
+        weight[p - start, q] each (None: 1) -> dict(arc, vertex, totals) as
+        path_load gives them; there is no status array.  A 2-D weight array's row
+        stride is passed on as ld, so a column slice of a wider array is not copied."""
+        T = int(self._lib.shd_pe_num_attached(self.h))
+        start = int(start)
+        count = T - start if count is None else int(count)
+        w, ld = None, 0
+        if weight is not None:
+            w = np.asarray(weight, dtype=np.uint64)
+            if w.ndim != 2 or w.shape[0] != count or w.shape[1] < T:
+                raise ValueError("weight must be a (count, >= T) array")
+            if w.strides[1] != 8 or w.strides[0] % 8 or w.strides[0] < 8 * w.shape[1]:
+                w = np.ascontiguousarray(w)
+            ld = w.strides[0] // 8 if count > 1 else w.shape[1]
+        out = _load_out(int(self._lib.shd_pe_num_arcs(self.h)), self.top.n, 0)
+        del out["status"]
+        o = LoadOutC(_p(out["arc"]), _p(out["vertex"]), None, _p(out["totals"]))
+        i = TableLoadInC(start, count, w.ctypes.data if w is not None else None, ld)
+        self._chk(self._lib.shd_pe_table_load(self.h, C.byref(i), C.byref(o)), "shd_pe_table_load")
+        return out
+
+    def table_load_info(self) -> dict:
+        """shd_pe_table_load_info of the last table_load: sources per route (each
+        in exactly one of tree / direct / route), of the route's those the tree
+        tier handed on, tree entries claimed, device ms, the tier's rounds and
+        (debug counters only, else 0) the global adds its commit issued."""
+        info = np.zeros(8, np.int64)
+        self._chk(self._lib.shd_pe_table_load_info(self.h, _p(info), 8), "shd_pe_table_load_info")
+        return {"tree": int(info[0]), "direct": int(info[1]), "route": int(info[2]),
+                "handed_on": int(info[3]), "claimed": int(info[4]), "device_ms": info[5] / 1000.0,
+                "rounds": int(info[6]), "atomics": int(info[7])}
 
     def tune(self):
         """shd_pe_tune: time both k_batch_rows variants on this engine's rows,
