@@ -48,7 +48,9 @@ extern "C" {
                                   14: shd_pe_path_load, shd_pe_path_load_info, shd_pe_num_arcs,
                                       shd_pe_arc_list, shd_pe_find_arc, shd_topology_link_load;
                                   15: shd_pe_sparse_info;
-                                  16: shd_pe_table_load, shd_pe_table_load_info */
+                                  16: shd_pe_table_load, shd_pe_table_load_info;
+                                      later under 16: shd_pe_table_load_set_parent_tier,
+                                      shd_pe_table_load_info's info[8..11] */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -483,7 +485,27 @@ int shd_pe_path_load_info(const ShdPe* pe, int64_t* info, int32_t n);
  * alone (all zero when there was none).  A failed scratch or staging
  * allocation is SHD_PE_ENOMEM.  (Under SHD_PE_DEBUG_ENV: SHDPE_TLOAD_TREE=0
  * turns the tree tier off; SHDPE_TLOAD_CORRUPT=1 / 2 spoil the first source's
- * expected total / first claimed vertex, tests.) */
+ * expected total / first claimed vertex, tests.)
+ *
+ * A fourth route, the parent tier, is off until
+ * shd_pe_table_load_set_parent_tier switches it on.  It serves sources whose
+ * parents stand in an explicit array of in-arc words: on engines of the per-row
+ * sparse kernel, every source from one pass of that kernel that stores no row
+ * (groups of at most one row per resident workgroup; the parents stay in the
+ * workgroups' scratch slots), and, there and in the batched engines' tree tier,
+ * the flagged rows with an early-stop tie slot from the slot's final parents
+ * after the relevance scan and the early-stop emulation.  One kernel per group
+ * seeds, claims upwards over the parent words (read by shd_pe_get_paths' walk
+ * rule: a word that is negative, names no in-arc or has no vertex at its tail
+ * fails the source), sums leaves first and commits only after two checks: the
+ * source's sum is the expected total, and the sums of all claimed vertices add
+ * up to the table's weighted vertex count.  Rows of the full emulation, a tie
+ * slot that failed the emulation's consistency check and every source that
+ * fails a check go to the request route.  Not with forceMode 3 or folded
+ * latencies, and not in the dense mode.  (Under SHD_PE_DEBUG_ENV:
+ * SHDPE_PATHS_FAST=0 turns it off as every fast tier; SHDPE_TLOAD_CORRUPT=1 / 2
+ * / 3 spoil the first source's expected total / parent words / expected
+ * weighted vertex count in this tier too.) */
 typedef struct ShdPeTableLoadIn {
     int32_t start, count;     /* source rows: table positions [start, start+count) */
     const uint64_t* weight;   /* count x ld, row-major: weight[(p-start)*ld + q] is the weight of
@@ -491,13 +513,20 @@ typedef struct ShdPeTableLoadIn {
     int64_t ld;               /* >= T; ignored when weight == NULL */
 } ShdPeTableLoadIn;
 int shd_pe_table_load(ShdPe* pe, const ShdPeTableLoadIn* in, const ShdPeLoadOut* out);
-/* Of the last shd_pe_table_load call, the first min(n, 8) of: info[0] sources
+/* Switches shd_pe_table_load's parent tier on (enable != 0) or off; off by
+ * default.  Takes the compute lock.  pe NULL: SHD_PE_EINVAL.  Independent of
+ * shd_pe_paths_set_row_tier. */
+int shd_pe_table_load_set_parent_tier(ShdPe* pe, int32_t enable);
+/* Of the last shd_pe_table_load call, the first min(n, 12) of: info[0] sources
  * served by the tree tier, info[1] by the direct kernel, info[2] by the request
- * route (each source in exactly one of the three); info[3] of info[2], sources
- * the tree tier had started and handed on after one of its own checks; info[4]
- * tree entries claimed by the sources of info[0]; info[5] device time of the
- * call from events, in microseconds; info[6] rounds the tree tier ran; info[7]
- * global adds its commit issued (SHD_PE_DEBUG_COUNTERS only, else 0). */
+ * route, info[8] by the parent tier over row parents, info[9] by the parent
+ * tier over tie-slot parents (each source in exactly one of the five); info[3]
+ * of info[2], sources a tree or parent tier had started and handed on after one
+ * of its own checks; info[4] tree entries claimed by the sources of info[0];
+ * info[5] device time of the call from events, in microseconds; info[6] rounds
+ * the tree tier ran; info[7] global adds its commit issued; info[10] entries
+ * claimed by the sources of info[8] and info[9]; info[11] global adds the parent
+ * tier's commits issued (info[7], info[11]: SHD_PE_DEBUG_COUNTERS only, else 0). */
 int shd_pe_table_load_info(const ShdPe* pe, int64_t* info, int32_t n);
 
 /* Page-locked host memory for shd_pe_get_rows destinations (DMA target, no

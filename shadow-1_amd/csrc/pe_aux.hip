@@ -866,6 +866,228 @@ void launch_table_direct(const DevGraph& gAux, const TableDirectArgs& a, void* s
                        reinterpret_cast<hipStream_t>(stream), gAux, a);
 }
 
+// k_tree_load_parents (shd_pe_table_load's parent tier, launch_tree_load_parents):
+// k_tree_load's reduction for sources whose parents stand in an explicit array
+// of in-arc words, read by k_paths_walk's rule -- the scratch slots of
+// k_sparse_rows' row-less form, or the tie slots after the early-stop emulation.
+//
+// Persistent workgroups, one listed source at a time, each with a private
+// scratch slot of (sum, pending children, claimed mark) per vertex that it
+// reuses for its next source.  Per source, with a workgroup barrier between
+// the steps:
+//   init    the slot cleared.  A source with a skip byte does not run at all; one
+//           whose tie slot's threshold is NaN (the emulation's consistency check
+//           failed it) is handed on
+//   seed    per destination: status and hops from the table row -> the totals
+//           and the expected sum; a status-0 destination of non-zero weight adds
+//           its weight to its vertex and
+//   claim   walks up from it, marking each vertex once (compare-and-swap) and
+//           counting it as a child of its parent, until the source or a marked
+//           vertex.  A parent word that is negative, names no in-arc, or whose
+//           tail is no vertex fails the source.  A cycle ends on the marks
+//   sum     as k_tree_load: who takes an entry without pending children adds
+//           its sum to the parent's and, after the last child, goes on with it
+//   check   the source passes when it did not fail, (A) the sum at its vertex is
+//           the expected one and (B) the sums of all claimed vertices add up to
+//           the table's weighted vertex count (tot[1]): the chains are as long
+//           as the table's hops say (k_paths_walk's check through L).  A cycle
+//           is never summed and fails (A)
+//   commit  per claimed vertex its sum to the vertex's place in acc and to the
+//           place of the arc from its parent (caller's ids, find_arc), with
+//           device-scope no-return adds.  (Per-workgroup accumulators flushed
+//           once per launch were measured and were slower: DESIGN §8h.)
+// Nothing reaches acc or the totals before the check.  Every loop ends on
+// a mark, a count or a bound; the slot's traffic is workgroup scope.
+constexpr int TPAR_THREADS = 512;
+
+__device__ __forceinline__ void wg_add(unsigned long long* p, unsigned long long v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+__device__ __forceinline__ void dev_add(unsigned long long* p, unsigned long long v) {
+    __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+
+__global__ __launch_bounds__(TPAR_THREADS) void k_tree_load_parents(DevGraph g0, DevGraph aux0, DevTable tab0,
+                                                                    TreeParentsArgs p) {
+    __shared__ unsigned long long expect, tot[3], total, claimedSrc, issuedWg, claimedWg;
+    __shared__ unsigned int bad;
+    __shared__ int run, fail, pass;
+    const DevGraph g = global_view(g0);
+    const DevGraph aux = global_view(aux0);
+    const DevTable tab = global_view(tab0);
+    const int tid = threadIdx.x, n = g.n;
+    const int64_t T = tab.T;
+    unsigned long long* __restrict__ sum = (unsigned long long*)as_global(p.sum) + (size_t)blockIdx.x * (size_t)n;
+    int32_t* __restrict__ pend = as_global(p.pend) + (size_t)blockIdx.x * (size_t)n;
+    int32_t* __restrict__ mark = as_global(p.mark) + (size_t)blockIdx.x * (size_t)n;
+    const int32_t* __restrict__ attDev = as_global(p.attDev);
+    unsigned long long* __restrict__ acc = (unsigned long long*)as_global(p.acc);
+    unsigned long long* __restrict__ out = (unsigned long long*)as_global(p.out);
+    if (tid == 0) issuedWg = claimedWg = 0;
+    for (int i = blockIdx.x; i < p.nSrc; i += gridDim.x) {
+        const int pos = as_global(p.pos)[i];
+        const int slot = p.slot ? as_global(p.slot)[i] : i;
+        const int src = attDev[pos];
+        const int32_t* __restrict__ P = as_global(p.parents) + (size_t)slot * (size_t)p.stride;
+        const unsigned long long* __restrict__ W =
+            p.weight ? (const unsigned long long*)as_global(p.weight) + (size_t)i * (size_t)T : nullptr;
+        const bool target = i == p.corruptAt;
+        // ---- init
+        if (tid == 0) {
+            run = !(p.skip && as_global(p.skip)[i] != 0);
+            const double thr = p.thr ? as_global(p.thr)[slot] : 0.0;
+            fail = thr != thr;
+            pass = 0;
+            expect = tot[0] = tot[1] = tot[2] = total = claimedSrc = 0;
+            bad = 0;
+        }
+        for (int v = tid; v < n; v += TPAR_THREADS) {
+            sum[v] = 0;
+            pend[v] = 0;
+            mark[v] = 0;
+        }
+        fence_wg();
+        __syncthreads();
+        const bool runs = run != 0, sound = fail == 0;   // (the same in every thread)
+        if (!runs) {
+            __syncthreads();                     // (read before the next source's init writes it)
+            continue;
+        }
+        // ---- seed and claim
+        for (int q = tid; q < T && sound; q += TPAR_THREADS) {
+            unsigned long long hops = 0;
+            if (q != pos) {
+                const size_t cell = (size_t)(pos - tab.rowStart) * (size_t)T + (size_t)q;
+                if (tab.flags[cell] & (F_UNREACHABLE | F_NOEDGE)) {
+                    atomicAdd(&bad, 1u);
+                    continue;
+                }
+                const int h = tab.hops[cell];
+                if (h < 1 || h >= n) {           // (not a table this engine wrote: the request route says so)
+                    fail = 1;
+                    continue;
+                }
+                hops = (unsigned long long)h;
+            }
+            const unsigned long long w = W ? W[q] : 1ull;
+            atomicAdd(&tot[0], 1ull);
+            if (w == 0) continue;                // adds nothing anywhere
+            atomicAdd(&tot[1], w * (hops + 1));
+            atomicAdd(&tot[2], w * hops);
+            atomicAdd(&expect, w);
+            int x = attDev[q];
+            wg_add(&sum[x], w);
+            while (!*(volatile int*)&fail) {
+                int32_t was = 0;
+                if (!__hip_atomic_compare_exchange_strong(&mark[x], &was, 1, __ATOMIC_RELAXED, __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_WORKGROUP))
+                    break;                       // claimed already: the rest of the way is too
+                if (x == src) break;
+                const int a = P[x];
+                if (a < 0 || (a & ~TIE_AMB) >= p.nInArcs || (target && p.corrupt == 2)) {
+                    fail = 1;
+                    break;
+                }
+                const int u = g.inCol[a & ~TIE_AMB];
+                if (u < 0 || u >= n) {
+                    fail = 1;
+                    break;
+                }
+                __hip_atomic_fetch_add(&pend[u], 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+                x = u;                           // (every step claims a vertex: at most n of them)
+            }
+        }
+        fence_wg();
+        __syncthreads();
+        // ---- sum, leaves first (every claimed vertex but the source has a checked parent)
+        const bool whole = fail == 0;
+        for (int v = tid; v < n && whole; v += TPAR_THREADS) {
+            if (!ld_wg(&mark[v])) continue;
+            int e = v;
+            for (;;) {
+                int32_t zero = 0;
+                if (!__hip_atomic_compare_exchange_strong(&pend[e], &zero, -1, __ATOMIC_ACQUIRE, __ATOMIC_RELAXED,
+                                                          __HIP_MEMORY_SCOPE_WORKGROUP))
+                    break;                       // children pending, or taken by another thread
+                if (e == src) break;             // its sum stays for the check
+                // (the entry's sum is final: every child added before it counted down)
+                const unsigned long long s = __hip_atomic_fetch_add(&sum[e], 0ull, __ATOMIC_RELAXED,
+                                                                    __HIP_MEMORY_SCOPE_WORKGROUP);
+                const int u = g.inCol[P[e] & ~TIE_AMB];
+                wg_add(&sum[u], s);
+                if (__hip_atomic_fetch_sub(&pend[u], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) != 1) break;
+                e = u;
+            }
+        }
+        fence_wg();
+        __syncthreads();
+        // ---- check
+        {
+            unsigned long long part = 0, cl = 0;
+            for (int v = tid; v < n && whole; v += TPAR_THREADS)
+                if (ld_wg(&mark[v])) {
+                    ++cl;
+                    part += ld_wg(&sum[v]);
+                }
+            if (cl) {
+                atomicAdd(&total, part);
+                atomicAdd(&claimedSrc, cl);
+            }
+        }
+        __syncthreads();
+        if (tid == 0) {
+            const unsigned long long wantA = expect + (target && p.corrupt == 1 ? 1ull : 0ull);
+            const unsigned long long wantB = tot[1] + (target && p.corrupt == 3 ? 1ull : 0ull);
+            const bool ok = whole && ld_wg(&sum[src]) == wantA && total == wantB;
+            pass = ok;
+            as_global(p.handed)[i] = ok ? 0 : 1;
+            if (ok) {
+                dev_add(&out[0], tot[0]);
+                dev_add(&out[1], tot[1]);
+                dev_add(&out[2], tot[2]);
+                dev_add(&out[3], (unsigned long long)bad);
+                dev_add(&out[4], 1ull);
+                claimedWg += claimedSrc;
+            }
+        }
+        __syncthreads();
+        // ---- commit
+        unsigned long long issued = 0;
+        for (int v = tid; v < n && pass; v += TPAR_THREADS) {
+            if (!ld_wg(&mark[v])) continue;
+            const unsigned long long s = ld_wg(&sum[v]);
+            if (s == 0) continue;
+            const int a = v == src ? -1 : (P[v] & ~TIE_AMB);
+            const int ov = g.oldId ? g.oldId[v] : v;
+            dev_add(acc + p.nArcs + ov, s);
+            ++issued;
+            if (a < 0) continue;
+            const int u = g.inCol[a];
+            const int ou = g.oldId ? g.oldId[u] : u;
+            int arc = -1;
+            if (ou != ov && find_arc(aux, ou, ov, &arc)) {
+                dev_add(acc + arc, s);
+                ++issued;
+            } else {                             // (never: a parent arc is an arc of the graph)
+                dev_add(&out[7], 1ull);
+            }
+        }
+        if (issued) atomicAdd(&issuedWg, issued);
+        __syncthreads();                         // the slot is free for the next source
+    }
+    if (tid == 0) {
+        if (claimedWg) dev_add(&out[5], claimedWg);
+        if (issuedWg) dev_add(&out[6], issuedWg);
+    }
+}
+
+void launch_tree_load_parents(const DevGraph& g, const DevGraph& gAux, const DevTable& tab,
+                              const TreeParentsArgs& a, int grid, void* stream) {
+    if (a.nSrc <= 0 || grid <= 0) return;
+    hipLaunchKernelGGL(k_tree_load_parents, dim3((unsigned)(grid < a.nSrc ? grid : a.nSrc)), dim3(TPAR_THREADS), 0,
+                       reinterpret_cast<hipStream_t>(stream), g, gAux, tab, a);
+}
+
 void launch_paths_size(const DevGraph& gAux, const DevTable& tab, const PathsSizeArgs& a, void* stream) {
     if (a.count <= 0) return;
     hipLaunchKernelGGL(k_paths_size, dim3((unsigned)((a.count + 255) / 256)), dim3(256), 0,

@@ -162,7 +162,9 @@ struct Tuning {
     int loadSort = 1;          // shd_pe_path_load: 0 keeps the caller's request order (no sort by source)
     int tloadTree = 1;         // shd_pe_table_load: 0 = no tree tier, every source by the request route
     int tloadCorrupt = 0;      // tests only: 1 the first source's expected total is off by one, 2 its first
-                               // claimed vertex counts as ambiguous (both: the tree tier hands the source on)
+                               // claimed vertex counts as ambiguous (both: the tree tier hands the source on);
+                               // the parent tier: 2 its parent words count as invalid, 3 the expected
+                               // weighted vertex count of its second check is off by one
     int loadSlots = 2048;      // ... the reduction's LDS table size (rounded down to a power of two in [8, 2048])
     int predFilter = 1;        // on-demand predecessor pass reads only the in-arcs the relax
                                // flagged (0: every in-arc, BatchScratch::arcHit stays null)
@@ -486,6 +488,34 @@ struct TreeLoadArgs {
 // grid: scratch slots (workgroups) to use, at most
 void launch_tree_load(const DevGraph& g, const DevGraph& gAux, const DevTable& tab, const BatchScratch& bs,
                       const TreeLoadArgs& a, int grid, void* stream);
+// ... its tree kernel over explicit parent arrays (pe_aux.hip, k_tree_load_parents;
+// shd_pe_table_load_set_parent_tier): listed source i has table position pos[i]
+// and its parents (IN-arc words as k_paths_walk reads them) at parents +
+// slot[i] * stride -- the scratch slots k_sparse_rows' row-less form leaves, or
+// the tie slots after the early-stop emulation.
+struct TreeParentsArgs {
+    const int32_t* pos;         // [nSrc] table positions
+    const int32_t* slot;        // [nSrc] parent array of each source; null: source i has slot i
+    int32_t nSrc;
+    const int32_t* attDev;      // [T] as TreeLoadArgs::attDev
+    const int32_t* parents;
+    int64_t stride;
+    int32_t nInArcs;
+    const uint8_t* skip;        // [nSrc] or null: non-zero = the source does not run (the sparse rowAmbig)
+    const double* thr;          // by slot, or null: NaN = the slot failed the emulation's check, handed on
+    const uint64_t* weight;     // [nSrc][T]; null: 1
+    uint64_t* sum;              // [grid][n] scratch slots: subtree sum ...
+    int32_t* pend;              // ... children that have not arrived ...
+    int32_t* mark;              // ... claimed (1) or not (0)
+    int64_t nArcs;
+    uint64_t* acc;              // [nArcs + n]
+    uint8_t* handed;            // [nSrc] 1 = run and handed on
+    uint64_t* out;              // [8] as TreeLoadArgs::out
+    int32_t corrupt;            // tests: 1 / 2 / 3 (SHDPE_TLOAD_CORRUPT) on listed source corruptAt
+    int32_t corruptAt;          // (-1: none)
+};
+void launch_tree_load_parents(const DevGraph& g, const DevGraph& gAux, const DevTable& tab,
+                              const TreeParentsArgs& a, int grid, void* stream);
 // ... and its direct kernel for complete graphs (pe_aux.hip): rows [row0, row0 +
 // rows) of the pair matrix, every path [s, t] (or [s]), one thread per pair
 struct TableDirectArgs {

@@ -2847,7 +2847,7 @@ struct TableLoad {
     std::vector<uint64_t> sum;           // nArcs + n
     uint64_t tot[4] = {0, 0, 0, 0};
     std::vector<int32_t> rest;           // the table positions left to the request route
-    double ms = 0.0;                     // device time of the tree tier and the direct kernel
+    double ms = 0.0;                     // device time of the tree tiers and the direct kernel
     const uint64_t* row(int32_t p) const { return in->weight + (size_t)(p - in->start) * (size_t)in->ld; }
 };
 
@@ -2911,6 +2911,213 @@ static int tload_direct(ShdPe* pe, TableLoad& c) {
     c.ms += elapsed(sh->ev0, sh->ev1);
     for (int i = 0; i < 4; ++i) c.tot[i] += out[i];
     pe->tloadInfo[1] += in->count;
+    return SHD_PE_OK;
+}
+
+// ---- parent tier (shd_pe_table_load_set_parent_tier) ----------------
+// Where it applies, when switched on: the per-row sparse kernel's engines, and
+// the tie rows with a slot of the batched engines' tree tier.
+static bool tload_parents_apply(const ShdPe* pe) {
+    return pe->tloadParentTier && pe->tu.pathsFast && pe->mode == 1 && pe->opt.forceMode != 3 && !pe->hg.latFold;
+}
+
+namespace {
+
+// One shard's k_tree_load_parents launches of a call: scratch slots, staging
+// and what each launch listed (entry e of dHanded is source who[e], launched
+// over tie slots where tie[e]).
+struct ParentTier {
+    PathsStage s;
+    PinnedBuf host;
+    OwnedEvent up;
+    int32_t *dAttDev = nullptr, *dPend = nullptr, *dMark = nullptr;
+    uint64_t *dAcc = nullptr, *dOut = nullptr, *dSum = nullptr, *dW = nullptr;
+    uint8_t* dHanded = nullptr;
+    bool ownAcc = false;
+    int grid = 0;
+    size_t cap = 0, handedCap = 0;
+    std::vector<int32_t> who;
+    std::vector<uint8_t> tie;
+};
+
+}  // namespace
+
+// cap: sources per launch at most; entries: listed sources of all launches at
+// most.  dAcc / dAttDev: the tree tier's, or null (allocated and zeroed here).
+static int ptier_init(ShdPe* pe, Shard* sh, const TableLoad& c, size_t cap, size_t entries, uint64_t* dAcc,
+                      int32_t* dAttDev, ParentTier& pt) {
+    const size_t T = (size_t)c.T, n = (size_t)pe->hg.n, nAcc = c.sum.size();
+    int rc;
+    pt.s.device = sh->device;
+    pt.cap = cap;
+    pt.handedCap = entries;
+    // scratch slots: one per workgroup, (sum, pending, mark) per vertex
+    const int64_t slotBytes = (int64_t)n * 16;
+    pt.grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)sh->numCUs, cap));
+    pt.grid = (int)std::min<int64_t>(pt.grid, std::max<int64_t>(1, TLOAD_SCRATCH_BYTES / slotBytes));
+    if (pe->tu.batchGrid > 0) pt.grid = std::min(pt.grid, pe->tu.batchGrid);
+    const size_t slots = (size_t)pt.grid * n;
+    if ((rc = pt.s.get(&pt.dOut, 16)) || (rc = pt.s.get(&pt.dHanded, entries)) || (rc = pt.s.get(&pt.dSum, slots)) ||
+        (rc = pt.s.get(&pt.dPend, slots)) || (rc = pt.s.get(&pt.dMark, slots)))
+        return rc;
+    if (c.in->weight) {
+        if ((rc = pt.s.get(&pt.dW, cap * T)) || (rc = pt.host.get(cap * T * 8))) return rc;
+        HIPCHK(hipEventCreateWithFlags(&pt.up.e, hipEventDisableTiming));
+    }
+    pt.dAcc = dAcc;
+    pt.dAttDev = dAttDev;
+    if (!dAcc) {
+        pt.ownAcc = true;
+        if ((rc = pt.s.get(&pt.dAcc, nAcc)) || (rc = pt.s.get(&pt.dAttDev, T))) return rc;
+        std::vector<int32_t> attDev(T);
+        for (size_t q = 0; q < T; ++q)
+            attDev[q] = pe->devOf.empty() ? pe->attached[q] : pe->devOf[(size_t)pe->attached[q]];
+        HIPCHK(hipMemcpy(pt.dAttDev, attDev.data(), T * 4, hipMemcpyHostToDevice));
+        HIPCHK(hipMemsetAsync(pt.dAcc, 0, nAcc * 8, sh->stream));
+    }
+    HIPCHK(hipMemsetAsync(pt.dOut, 0, 128, sh->stream));
+    HIPCHK(hipMemsetAsync(pt.dHanded, 0, entries, sh->stream));
+    return SHD_PE_OK;
+}
+
+// One launch over the nSrc <= cap sources at hostPos (dPos: the same on the
+// device), their weight rows staged first.  tie: over the tie slots dSlot with
+// their thresholds; else over the scratch slots 0 .. nSrc - 1, less dSkip.
+static int ptier_launch(ShdPe* pe, Shard* sh, const TableLoad& c, ParentTier& pt, const int32_t* hostPos,
+                        int32_t nSrc, const int32_t* dPos, const int32_t* dSlot, const uint8_t* dSkip, bool tie) {
+    const size_t T = (size_t)c.T;
+    if (nSrc <= 0) return SHD_PE_OK;
+    if ((size_t)nSrc > pt.cap || pt.who.size() + (size_t)nSrc > pt.handedCap) return SHD_PE_EINVAL;
+    if (c.in->weight) {
+        if (pt.up.recorded) HIPCHK(hipEventSynchronize(pt.up.e));        // the staging is free again
+        for (int32_t i = 0; i < nSrc; ++i) std::memcpy((uint64_t*)pt.host.p + (size_t)i * T, c.row(hostPos[i]), T * 8);
+        HIPCHK(hipMemcpyAsync(pt.dW, pt.host.p, (size_t)nSrc * T * 8, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipEventRecord(pt.up.e, sh->stream));
+        pt.up.recorded = true;
+    }
+    int32_t corruptAt = -1;              // the call's first source (the debug switches' target)
+    for (int32_t i = 0; i < nSrc && pe->tu.tloadCorrupt; ++i)
+        if (hostPos[i] == c.in->start) corruptAt = i;
+    const TreeParentsArgs a{dPos, dSlot, nSrc, pt.dAttDev, tie ? sh->tie.P : sh->sc.pred,
+                            tie ? sh->tie.n : sh->sc.stride, (int32_t)pe->hg.nArcs(), dSkip,
+                            tie ? sh->tie.thr : nullptr, pt.dW, pt.dSum, pt.dPend, pt.dMark,
+                            pe->hg.nArcs(), pt.dAcc, pt.dHanded + pt.who.size(), pt.dOut + (tie ? 8 : 0),
+                            corruptAt >= 0 ? pe->tu.tloadCorrupt : 0, corruptAt};
+    launch_tree_load_parents(sh->dg, sh->dgAux, sh->tab, a, pt.grid, sh->stream);
+    HIPCHK(hipGetLastError());
+    pt.who.insert(pt.who.end(), hostPos, hostPos + nSrc);
+    pt.tie.insert(pt.tie.end(), (size_t)nSrc, (uint8_t)(tie ? 1 : 0));
+    return SHD_PE_OK;
+}
+
+// The early-stop tie rows rows[0, nTie) with their slots: relevance scan, the
+// emulation up to each row's threshold (it leaves the final parents in tie.P),
+// and one launch over tie.P.  (rows / slots stay as they are until ptier_finish.)
+static int ptier_tie_rows(ShdPe* pe, Shard* sh, const TableLoad& c, ParentTier& pt, const std::vector<int32_t>& rows,
+                          const std::vector<int32_t>& slots, int32_t nTie) {
+    int rc;
+    HIPCHK(hipMemcpyAsync(sh->dRows, rows.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+    HIPCHK(hipMemcpyAsync(sh->dSlots, slots.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+    scan_tie_slots(pe, sh, slots, nTie);
+    if ((rc = paths_emulate(pe, sh, sh->dRows, nTie, sh->exactGrid, sh->dSlots))) return rc;
+    return ptier_launch(pe, sh, c, pt, rows.data(), nTie, sh->dRows, sh->dSlots, nullptr, true);
+}
+
+// Synchronises; the sums (where the accumulator is this tier's own), totals and
+// info words of the launches added, handed[e] = listed source e was handed on.
+static int ptier_finish(ShdPe* pe, Shard* sh, TableLoad& c, ParentTier& pt, std::vector<uint8_t>& handed) {
+    int rc;
+    uint64_t out[16];
+    handed.assign(pt.who.size(), 0);
+    if (!handed.empty())
+        HIPCHK(hipMemcpyAsync(handed.data(), pt.dHanded, handed.size(), hipMemcpyDeviceToHost, sh->stream));
+    HIPCHK(hipMemcpyAsync(out, pt.dOut, 128, hipMemcpyDeviceToHost, sh->stream));
+    if (pt.ownAcc) {
+        if ((rc = tload_add_acc(sh, pt.dAcc, c.sum))) return rc;
+    } else {
+        HIPCHK(hipStreamSynchronize(sh->stream));
+    }
+    if (out[7] || out[15]) return SHD_PE_EHIP;   // a parent arc the graph does not hold: never
+    for (int i = 0; i < 4; ++i) c.tot[i] += out[i] + out[8 + i];
+    int64_t nHanded = 0;
+    for (uint8_t h : handed) nHanded += h;
+    pe->tloadInfo[3] += nHanded;
+    pe->tloadInfo[8] += (int64_t)out[4];
+    pe->tloadInfo[9] += (int64_t)out[12];
+    pe->tloadInfo[10] += (int64_t)(out[5] + out[13]);
+    if (pe->tu.debug) pe->tloadInfo[11] += (int64_t)(out[6] + out[14]);
+    return SHD_PE_OK;
+}
+
+// Parent tier over the table positions [lo, hi) of a shard on the per-row
+// sparse kernel: the sources in groups of at most one row per resident
+// workgroup, as paths_rows_sparse runs them.  Per group k_sparse_rows in the
+// form that stores no table row, one k_tree_load_parents over the scratch slots
+// (the rows the kernel flagged skipped by their ambiguity byte), and the
+// group's tie rows with a slot through ptier_tie_rows (enqueued after: the
+// emulation reuses the scratch slots).  Left to the request route (c.rest):
+// the rows flagged for the full emulation and the sources handed on.
+static int tload_parents_sparse(ShdPe* pe, size_t k, int32_t lo, int32_t hi, TableLoad& c) {
+    Shard* sh = pe->shards[k].get();
+    int rc;
+    HIPCHK(hipSetDevice(sh->device));
+    if ((rc = ensure_table(pe, sh)) || (rc = ensure_tie(pe, sh))) return rc;
+    const int32_t count = hi - lo;
+    const int32_t G = std::min(count, std::max(1, pe->tu.pathsGroup > 0 ? std::min(pe->tu.pathsGroup, sh->cfg.grid)
+                                                                          : sh->cfg.grid));
+    ParentTier pt;
+    int32_t* dPos = nullptr;
+    if ((rc = ptier_init(pe, sh, c, (size_t)G, 2 * (size_t)count, nullptr, nullptr, pt)) ||
+        (rc = pt.s.get(&dPos, (size_t)count)))
+        return rc;
+    std::vector<int32_t> pos((size_t)count);
+    for (int32_t p = lo; p < hi; ++p) pos[(size_t)(p - lo)] = p;
+    HIPCHK(hipMemcpyAsync(dPos, pos.data(), (size_t)count * 4, hipMemcpyHostToDevice, sh->stream));
+    std::vector<uint8_t> amb((size_t)G);
+    std::vector<ExactWork> ties;                         // (what the copies read lives until the last synchronise)
+    ties.reserve((size_t)((count + G - 1) / G));
+    const ShdPeStats savedStats = sh->stats;
+    sh->pathSrc = -1;                                    // slot 0 is overwritten
+    int64_t nFull = 0;
+    const int64_t before = pe->tloadInfo[8] + pe->tloadInfo[9];
+    HIPCHK(hipEventRecord(sh->ev0, sh->stream));
+    for (int32_t u0 = 0; u0 < count; u0 += G) {
+        const int32_t g = std::min(G, count - u0);
+        if (sh->dTie) HIPCHK(hipMemsetAsync(sh->tie.count, 0, 4, sh->stream));
+        launch_sparse_rows(sh->dg, sh->tab, sh->sc, dPos + u0, g, sh->dRowAmbig, sh->cfg, nullptr, sh->dTie,
+                           sh->stream, true);
+        HIPCHK(hipGetLastError());
+        if ((rc = ptier_launch(pe, sh, c, pt, pos.data() + u0, g, dPos + u0, nullptr, sh->dRowAmbig, false))) return rc;
+        HIPCHK(hipMemcpyAsync(amb.data(), sh->dRowAmbig, (size_t)g, hipMemcpyDeviceToHost, sh->stream));
+        HIPCHK(hipStreamSynchronize(sh->stream));
+        ties.emplace_back();
+        ExactWork& tie = ties.back();                    // the group's tie rows with a slot
+        for (int32_t i = 0; i < g; ++i) {
+            if (amb[(size_t)i] == 1) {
+                c.rest.push_back(pos[(size_t)(u0 + i)]);
+                ++nFull;
+            } else if (amb[(size_t)i] >= 2) {
+                tie.rows.push_back(pos[(size_t)(u0 + i)]);
+                tie.slots.push_back(amb[(size_t)i] - 2);
+            }
+        }
+        if (!tie.rows.empty() &&
+            (rc = ptier_tie_rows(pe, sh, c, pt, tie.rows, tie.slots, (int32_t)tie.rows.size())))
+            return rc;
+    }
+    HIPCHK(hipEventRecord(sh->ev1, sh->stream));
+    std::vector<uint8_t> handed;
+    rc = ptier_finish(pe, sh, c, pt, handed);
+    sh->stats = savedStats;
+    if (rc) return rc;
+    c.ms += elapsed(sh->ev0, sh->ev1);
+    int64_t nHanded = 0;
+    for (size_t e = 0; e < handed.size(); ++e)
+        if (handed[e]) {
+            c.rest.push_back(pt.who[e]);
+            ++nHanded;
+        }
+    if (pe->tloadInfo[8] + pe->tloadInfo[9] - before + nHanded + nFull != (int64_t)count) return SHD_PE_EHIP;
     return SHD_PE_OK;
 }
 
@@ -3008,6 +3215,13 @@ static int tload_tree_shard(ShdPe* pe, size_t k, int32_t lo, int32_t hi, TableLo
     sh->roundsRun = savedRounds[0];
     sh->batchesRun = savedRounds[1];
     if (rc) return rc;
+    // parent tier: the flagged rows with a tie slot (the head of x) over the slots' final parents
+    ParentTier pt;
+    int32_t nTie = 0;
+    while (tload_parents_apply(pe) && nTie < (int32_t)x.slots.size() && x.slots[(size_t)nTie] >= 0) ++nTie;
+    if (nTie > 0 && ((rc = ptier_init(pe, sh, c, (size_t)nTie, (size_t)nTie, dAcc, dAttDev, pt)) ||
+                     (rc = ptier_tie_rows(pe, sh, c, pt, x.rows, x.slots, nTie))))
+        return rc;
     HIPCHK(hipEventRecord(sh->ev1, sh->stream));
     std::vector<uint8_t> handed(order.size());
     uint64_t out[8];
@@ -3017,13 +3231,21 @@ static int tload_tree_shard(ShdPe* pe, size_t k, int32_t lo, int32_t hi, TableLo
     c.ms += elapsed(sh->ev0, sh->ev1);
     if (out[7]) return SHD_PE_EHIP;      // a parent arc the graph does not hold: never
     for (int i = 0; i < 4; ++i) c.tot[i] += out[i];
-    int64_t nHanded = 0;
-    for (int32_t p : x.rows) c.rest.push_back(p);
+    int64_t nHanded = 0, nTieServed = 0;
+    std::vector<uint8_t> tieHanded;      // (x.rows[j], j < nTie: handed on by the parent tier)
+    if (nTie > 0) {
+        const int64_t before = pe->tloadInfo[9];
+        if ((rc = ptier_finish(pe, sh, c, pt, tieHanded))) return rc;
+        nTieServed = pe->tloadInfo[9] - before;
+    }
+    for (size_t j = 0; j < x.rows.size(); ++j)
+        if (j >= (size_t)nTie || tieHanded[j]) c.rest.push_back(x.rows[j]);
     for (size_t i = 0; i < order.size(); ++i)
         if (order[i] >= 0 && handed[i]) {
             c.rest.push_back(order[i]);
             ++nHanded;
         }
+    if (nTieServed + (int64_t)std::count(tieHanded.begin(), tieHanded.end(), 1) != nTie) return SHD_PE_EHIP;
     if ((int64_t)out[4] + nHanded + (int64_t)x.rows.size() != (int64_t)pos.size()) return SHD_PE_EHIP;
     pe->tloadInfo[0] += (int64_t)out[4];
     pe->tloadInfo[3] += nHanded;
@@ -3102,6 +3324,13 @@ extern "C" int shd_pe_table_load(ShdPe* pe, const ShdPeTableLoadIn* in, const Sh
             if ((rc = tload_tree_shard(pe, k, a, b, c))) return rc;
             std::fill(seen.begin() + (a - lo), seen.begin() + (b - lo), (uint8_t)1);
         }
+        for (size_t k = 0; k < pe->shards.size() && tload_parents_apply(pe) && !pe->batched; ++k) {
+            const Shard* sh = pe->shards[k].get();
+            const int32_t a = std::max(lo, sh->rowStart), b = std::min(hi, sh->rowStart + sh->rowCount);
+            if (a >= b) continue;
+            if ((rc = tload_parents_sparse(pe, k, a, b, c))) return rc;
+            std::fill(seen.begin() + (a - lo), seen.begin() + (b - lo), (uint8_t)1);
+        }
         for (int32_t p = lo; p < hi; ++p)
             if (!seen[(size_t)(p - lo)]) c.rest.push_back(p);
         rc = tload_route(pe, c);
@@ -3115,7 +3344,14 @@ extern "C" int shd_pe_table_load(ShdPe* pe, const ShdPeTableLoadIn* in, const Sh
 extern "C" int shd_pe_table_load_info(const ShdPe* pe, int64_t* info, int32_t n) {
     if (!pe || !info || n < 0) return SHD_PE_EINVAL;
     std::lock_guard<std::mutex> lk(const_cast<ShdPe*>(pe)->mu);
-    for (int32_t k = 0; k < std::min<int32_t>(n, 8); ++k) info[k] = pe->tloadInfo[k];
+    for (int32_t k = 0; k < std::min<int32_t>(n, 12); ++k) info[k] = pe->tloadInfo[k];
+    return SHD_PE_OK;
+}
+
+extern "C" int shd_pe_table_load_set_parent_tier(ShdPe* pe, int32_t enable) {
+    if (!pe) return SHD_PE_EINVAL;
+    std::lock_guard<std::mutex> lk(pe->mu);
+    pe->tloadParentTier = enable != 0;
     return SHD_PE_OK;
 }
 

@@ -198,7 +198,8 @@ struct ShdPe {
     int64_t pathsInfo[7] = {0, 0, 0, 0, 0, 0, 0};   // shd_pe_paths_info of the last shd_pe_get_paths
     bool pathsRowTier = false;       // shd_pe_paths_set_row_tier
     int64_t loadInfo[2] = {0, 0};    // shd_pe_path_load_info of the last shd_pe_path_load
-    int64_t tloadInfo[8] = {0, 0, 0, 0, 0, 0, 0, 0};   // shd_pe_table_load_info of the last shd_pe_table_load
+    int64_t tloadInfo[12] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};   // shd_pe_table_load_info of the last shd_pe_table_load
+    bool tloadParentTier = false;    // shd_pe_table_load_set_parent_tier
 };
 
 #define HIPCHK(x)                                   \

@@ -58,7 +58,7 @@ EXPORTS = [
     "shd_pe_paths_set_row_tier",
     "shd_pe_num_arcs", "shd_pe_arc_list", "shd_pe_find_arc", "shd_pe_path_load",
     "shd_pe_path_load_info", "shd_topology_link_load",
-    "shd_pe_table_load", "shd_pe_table_load_info",
+    "shd_pe_table_load", "shd_pe_table_load_info", "shd_pe_table_load_set_parent_tier",
 ]
 VATTR_IP, VATTR_CITYCODE, VATTR_COUNTRYCODE, VATTR_GEOCODE, VATTR_TYPE = range(5)
 VATTR_NAMES = ("ip", "citycode", "countrycode", "geocode", "type")
@@ -281,6 +281,7 @@ def load_library(path: str = LIB_PATH):
         "shd_pe_path_load_info": (C.c_int, [vp, vp, i32]),
         "shd_pe_table_load": (C.c_int, [vp, vp, vp]),
         "shd_pe_table_load_info": (C.c_int, [vp, vp, i32]),
+        "shd_pe_table_load_set_parent_tier": (C.c_int, [vp, i32]),
     }
     # ABI-3 ... ABI-8 additions: an older build loaded through SHDPE_LIB (same-box
     # A/B) lacks them; the in-tree library must have every symbol
@@ -296,7 +297,8 @@ def load_library(path: str = LIB_PATH):
                 "shd_pe_batch_info", "shd_pe_sparse_info", "shd_pe_paths_set_row_tier", "shd_pe_num_arcs",
                 "shd_pe_arc_list", "shd_pe_find_arc", "shd_pe_path_load",
                 "shd_pe_path_load_info", "shd_topology_link_load",
-                "shd_pe_table_load", "shd_pe_table_load_info"} if os.environ.get("SHDPE_LIB") else set()
+                "shd_pe_table_load", "shd_pe_table_load_info",
+                "shd_pe_table_load_set_parent_tier"} if os.environ.get("SHDPE_LIB") else set()
     for name, (res, args) in sig.items():
         if name in optional and not hasattr(lib, name):
             continue
@@ -744,16 +746,26 @@ class Engine:
         self._chk(self._lib.shd_pe_table_load(self.h, C.byref(i), C.byref(o)), "shd_pe_table_load")
         return out
 
+    def set_table_load_parent_tier(self, on: bool = True):
+        """shd_pe_table_load_set_parent_tier: let table_load serve the per-row sparse
+        mode, and the tie rows with a slot of the batched mode, from explicit
+        parent arrays (off by default)."""
+        self._chk(self._lib.shd_pe_table_load_set_parent_tier(self.h, 1 if on else 0),
+                  "shd_pe_table_load_set_parent_tier")
+
     def table_load_info(self) -> dict:
         """shd_pe_table_load_info of the last table_load: sources per route (each
-        in exactly one of tree / direct / route), of the route's those the tree
-        tier handed on, tree entries claimed, device ms, the tier's rounds and
-        (debug counters only, else 0) the global adds its commit issued."""
-        info = np.zeros(8, np.int64)
-        self._chk(self._lib.shd_pe_table_load_info(self.h, _p(info), 8), "shd_pe_table_load_info")
+        in exactly one of tree / direct / route / parents / tie), of the route's
+        those a tier handed on, tree entries claimed, device ms, the tree tier's
+        rounds, the entries the parent tier's sources claimed and (debug counters
+        only, else 0) the global adds the commits issued.  (A library loaded
+        through SHDPE_LIB from before the parent tier fills the first 8.)"""
+        info = np.zeros(12, np.int64)
+        self._chk(self._lib.shd_pe_table_load_info(self.h, _p(info), 12), "shd_pe_table_load_info")
         return {"tree": int(info[0]), "direct": int(info[1]), "route": int(info[2]),
                 "handed_on": int(info[3]), "claimed": int(info[4]), "device_ms": info[5] / 1000.0,
-                "rounds": int(info[6]), "atomics": int(info[7])}
+                "rounds": int(info[6]), "atomics": int(info[7]), "parents": int(info[8]), "tie": int(info[9]),
+                "parent_claimed": int(info[10]), "parent_atomics": int(info[11])}
 
     def tune(self):
         """shd_pe_tune: time both k_batch_rows variants on this engine's rows,

@@ -16,9 +16,17 @@ of wall time and of the call's device time.
             adds per claimed tree entry
   once      (--step once, for a profiler: one call of leg d, nothing timed)
 
+--parent-tier switches the parent tier on (shd_pe_table_load_set_parent_tier)
+in legs a, d and counters, for the engines the tree tier does not cover (C2:
+the per-row sparse kernel) or covers in part (c4q: the tie rows with a slot).
+Leg b stays the request route alone, and one leg joins the protocol: d_off, leg
+d with the tier off.
+
 (a), (b) and (c) must give identical sums (sha256 over arc, vertex and totals,
 kept in the file); (a) is expected below (b) and (c) by more than the sum of
-their min-max spreads, and the file says whether it is.
+their min-max spreads, and the file says whether it is (`*_by_more_than_spreads`,
+`*_ratio_device`: the slower leg's median over the faster's).  --legs runs a
+part of the protocol; every check applies to the legs that ran.
 
   python tools/table_load_time.py [--out profiles/table_load_c4shape.json]"""
 import argparse
@@ -43,6 +51,8 @@ def _engine(args, flags=0):
     from shdpe import generators as G
     top, att = G.make_config(args.config)
     eng = E.Engine(top, att, debug_flags=flags)     # raises without a gfx950 device: no fallback
+    if args.parent_tier:
+        eng.set_table_load_parent_tier(True)
     eng.tune()
     eng.reset_stats()
     eng.compute_all()
@@ -76,7 +86,8 @@ def _timed(call, info, what, repeats):
 def _result(eng, out, wall, dev, extra=None):
     info = eng.table_load_info()
     res = {"calls_timed": len(wall), "wall_ms": _range(wall), "device_ms": _range(dev),
-           "info": {k: info[k] for k in ("tree", "direct", "route", "handed_on", "claimed", "rounds", "atomics")},
+           "info": {k: info[k] for k in ("tree", "direct", "route", "handed_on", "claimed", "rounds", "atomics",
+                                         "parents", "tie", "parent_claimed", "parent_atomics")},
            "totals": [int(x) for x in out["totals"]], "digest": _digest(out),
            "switches": {k: v for k, v in os.environ.items() if k.startswith("SHDPE_TLOAD_")}}
     res.update(extra or {})
@@ -169,6 +180,7 @@ STEPS = {
     "d": lambda args: {"d_all_rows_unit_weight": step_d(args)},
     "e": lambda args: {"e_all_rows_matrix": step_e(args)},
     "counters": lambda args: {"a_counters": step_table(args, "counters", flags=1 | 2)},
+    "d_off": lambda args: {"d_parent_tier_off": step_d(args)},
     "once": step_once,
 }
 
@@ -179,33 +191,56 @@ def run_steps(args):
         plan.append(("e", {}))
     if args.counters:
         plan.append(("counters", {}))
-    res = {"config": args.config, "unit": "ms"}
+    if args.parent_tier:
+        plan.append(("d_off", {}))
+    if args.legs:
+        plan = [(step, env) for step, env in plan if step in args.legs.split(",")]
+    res = {"config": args.config, "unit": "ms", "parent_tier": bool(args.parent_tier)}
     for step, env in plan:
         part = f"{args.out}.{step}.part"
         cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__),
                "--config", args.config, "--step", step, "--out", part, "--repeats", str(args.repeats),
                "--sources", str(args.sources), "--block", str(args.block)]
+        if args.parent_tier and step not in ("b", "c", "d_off"):
+            cmd.append("--parent-tier")
         rc = subprocess.run(cmd, env={**os.environ, **env}).returncode
         if rc:
             raise SystemExit(f"step {step}: exit status {rc}; no further step was started")
         with open(part) as f:
             res.update(json.load(f))
         os.remove(part)
-    a, b, c = res["a_tree"], res["b_route"], res["c_path_load"]
-    digests = {"a": a["digest"], "b": b["digest"], "c": c["digest"]}
-    if len(set(digests.values())) != 1:
-        raise SystemExit(f"legs a, b and c give different sums: {digests}")
-    res["abc_sums_equal"] = True
-    if a["info"]["tree"] == 0 or b["info"]["tree"] != 0:
-        raise SystemExit(f"the tree tier switch did not take: a {a['info']}, b {b['info']}")
     spread = lambda r: r["device_ms"]["max"] - r["device_ms"]["min"]
-    for other, name in ((b, "b"), (c, "c")):
-        res[f"a_below_{name}_by_more_than_spreads"] = bool(
-            other["device_ms"]["median"] - a["device_ms"]["median"] > spread(a) + spread(other))
-        res[f"{name}_over_a_device"] = other["device_ms"]["median"] / a["device_ms"]["median"]
+    fast = lambda r: r["info"]["tree"] + r["info"]["parents"] + r["info"]["tie"]
+
+    def same_sums(keys):
+        """The legs of `keys` that ran gave identical sums."""
+        digests = {k: res[k]["digest"] for k in keys if k in res}
+        if len(set(digests.values())) > 1:
+            raise SystemExit(f"legs give different sums: {digests}")
+        return sorted(digests)
+
+    def below(fast_leg, slow_leg, name):
+        """fast_leg's median device time below slow_leg's by more than both min-max spreads."""
+        if fast_leg not in res or slow_leg not in res:
+            return
+        f, o = res[fast_leg], res[slow_leg]
+        res[f"{name}_by_more_than_spreads"] = bool(
+            o["device_ms"]["median"] - f["device_ms"]["median"] > spread(f) + spread(o))
+        res[f"{name}_ratio_device"] = o["device_ms"]["median"] / f["device_ms"]["median"]
+
+    res["sums_equal_first_rows"] = same_sums(("a_tree", "b_route", "c_path_load"))
+    res["sums_equal_all_rows"] = same_sums(("d_all_rows_unit_weight", "d_parent_tier_off"))
+    if "a_tree" in res and fast(res["a_tree"]) == 0:
+        raise SystemExit(f"no fast tier served leg a: {res['a_tree']['info']}")
+    if "b_route" in res and fast(res["b_route"]) != 0:
+        raise SystemExit(f"the tier switches did not take in leg b: {res['b_route']['info']}")
+    below("a_tree", "b_route", "a_below_b")
+    below("a_tree", "c_path_load", "a_below_c")
+    below("d_all_rows_unit_weight", "d_parent_tier_off", "d_below_d_off")
     if "a_counters" in res:
         i = res["a_counters"]["info"]
-        res["commit_global_adds_per_claimed_entry"] = i["atomics"] / max(1, i["claimed"])
+        res["commit_global_adds_per_claimed_entry"] = (i["atomics"] + i["parent_atomics"]) / max(
+            1, i["claimed"] + i["parent_claimed"])
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
     with open(args.out, "w") as f:
         json.dump(res, f, indent=1)
@@ -222,6 +257,9 @@ def main():
     ap.add_argument("--step-timeout", type=int, default=240, help="seconds per step")
     ap.add_argument("--leg-e", action="store_true", help="also all rows with a weight matrix, in row blocks")
     ap.add_argument("--counters", action="store_true", help="also leg a with debug counters")
+    ap.add_argument("--parent-tier", action="store_true",
+                    help="switch the parent tier on in legs a, d and counters; adds leg d_off")
+    ap.add_argument("--legs", default=None, help="run only these steps of the protocol (comma-separated)")
     ap.add_argument("--out", default=None, help="default: profiles/table_load_<config>shape.json")
     args = ap.parse_args()
     if args.out is None:
