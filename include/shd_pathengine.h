@@ -50,7 +50,9 @@ extern "C" {
                                   15: shd_pe_sparse_info;
                                   16: shd_pe_table_load, shd_pe_table_load_info;
                                       later under 16: shd_pe_table_load_set_parent_tier,
-                                      shd_pe_table_load_info's info[8..11] */
+                                      shd_pe_table_load_info's info[8..11];
+                                      later under 16: the parent tier serves the dense mode
+                                      (no new symbol, no new info entry) */
 
 /* ---- error codes ------------------------------------------------------ */
 #define SHD_PE_OK            0
@@ -489,20 +491,31 @@ int shd_pe_path_load_info(const ShdPe* pe, int64_t* info, int32_t n);
  *
  * A fourth route, the parent tier, is off until
  * shd_pe_table_load_set_parent_tier switches it on.  It serves sources whose
- * parents stand in an explicit array of in-arc words: on engines of the per-row
+ * parents stand in an explicit array.  In-arc words: on engines of the per-row
  * sparse kernel, every source from one pass of that kernel that stores no row
  * (groups of at most one row per resident workgroup; the parents stay in the
  * workgroups' scratch slots), and, there and in the batched engines' tree tier,
  * the flagged rows with an early-stop tie slot from the slot's final parents
- * after the relevance scan and the early-stop emulation.  One kernel per group
- * seeds, claims upwards over the parent words (read by shd_pe_get_paths' walk
- * rule: a word that is negative, names no in-arc or has no vertex at its tail
- * fails the source), sums leaves first and commits only after two checks: the
- * source's sum is the expected total, and the sums of all claimed vertices add
- * up to the table's weighted vertex count.  Rows of the full emulation, a tie
- * slot that failed the emulation's consistency check and every source that
- * fails a check go to the request route.  Not with forceMode 3 or folded
- * latencies, and not in the dense mode.  (Under SHD_PE_DEBUG_ENV:
+ * after the relevance scan and the early-stop emulation.  Vertex ids: the dense
+ * mode is served from the predecessor pass's parent rows -- per chunk of the
+ * dense batch the min-plus sweeps and the predecessor pass run without the row
+ * writer, and every row the pass did not flag is summed over its parent row
+ * (info[8]); on an undirected graph a chunk's flagged rows take the dense tie
+ * slots, the relevance scan and the early-stop emulation as the table's exact
+ * stage runs them, and are summed over the slots' final parents (info[9]).
+ * One kernel per group seeds, claims upwards over the parents (in-arc words
+ * read by shd_pe_get_paths' walk rule: a word that is negative, names no
+ * in-arc or has no vertex at its tail fails the source; a vertex id outside
+ * [0, n) or equal to its own vertex does too), sums leaves first and commits
+ * only after two checks: the source's sum is the expected total, and the sums
+ * of all claimed vertices add up to the table's weighted vertex count.  Rows
+ * of the full emulation, a tie slot that failed the emulation's consistency
+ * check, in the dense mode the flagged rows of a directed graph and those
+ * beyond a chunk's tie slots, and every source that fails a check go to the
+ * request route.  Not with forceMode 3 or folded latencies.  The accumulator
+ * (arcs + vertices, 8 bytes each) is held once on the device and, with the
+ * call's sum, twice on the host besides the caller's arrays: 3.2 GB each at
+ * 4 x 10^8 arcs.  (Under SHD_PE_DEBUG_ENV:
  * SHDPE_PATHS_FAST=0 turns it off as every fast tier; SHDPE_TLOAD_CORRUPT=1 / 2
  * / 3 spoil the first source's expected total / parent words / expected
  * weighted vertex count in this tier too.) */

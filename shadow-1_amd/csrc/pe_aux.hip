@@ -869,7 +869,9 @@ void launch_table_direct(const DevGraph& gAux, const TableDirectArgs& a, void* s
 // k_tree_load_parents (shd_pe_table_load's parent tier, launch_tree_load_parents):
 // k_tree_load's reduction for sources whose parents stand in an explicit array
 // of in-arc words, read by k_paths_walk's rule -- the scratch slots of
-// k_sparse_rows' row-less form, or the tie slots after the early-stop emulation.
+// k_sparse_rows' row-less form, or the tie slots after the early-stop emulation
+// -- or of vertex ids: the parent rows the dense predecessor pass leaves
+// (PAR_VERTEX below).
 //
 // Persistent workgroups, one listed source at a time, each with a private
 // scratch slot of (sum, pending children, claimed mark) per vertex that it
@@ -893,7 +895,8 @@ void launch_table_direct(const DevGraph& gAux, const TableDirectArgs& a, void* s
 //           as the table's hops say (k_paths_walk's check through L).  A cycle
 //           is never summed and fails (A)
 //   commit  per claimed vertex its sum to the vertex's place in acc and to the
-//           place of the arc from its parent (caller's ids, find_arc), with
+//           place of the arc from its parent (caller's ids, find_arc; over vertex
+//           ids a full out-row's arc at its computed place first), with
 //           device-scope no-return adds.  (Per-workgroup accumulators flushed
 //           once per launch were measured and were slower: DESIGN §8h.)
 // Nothing reaches acc or the totals before the check.  Every loop ends on
@@ -907,6 +910,35 @@ __device__ __forceinline__ void dev_add(unsigned long long* p, unsigned long lon
     __hip_atomic_fetch_add(p, v, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
+// How a source's parents stand in its array (the kernel's compile-time parameter):
+// PAR_INARC   in-arc words, as k_paths_walk reads them (TIE_AMB masked off)
+// PAR_VERTEX  the parent's vertex id in g's ids -- the rows the dense predecessor
+//             pass leaves (k_minplus<MP_PRED>: -1 none, -2 a tie, else the vertex)
+// tpar_parent: the checked read of the claim step, -1 = the word is refused (it
+// is negative, names no in-arc, its tail is no vertex; a vertex id out of
+// [0, n) or the vertex itself).  tpar_tail: the same parent once claimed.
+enum { PAR_INARC = 0, PAR_VERTEX = 1 };
+
+template <int PAR>
+__device__ __forceinline__ int tpar_parent(const DevGraph& g, const int32_t* __restrict__ P, int x, int n,
+                                           int nInArcs) {
+    if constexpr (PAR == PAR_VERTEX) {
+        const int u = P[x];
+        return (u < 0 || u >= n || u == x) ? -1 : u;
+    } else {
+        const int a = P[x];
+        if (a < 0 || (a & ~TIE_AMB) >= nInArcs) return -1;
+        const int u = g.inCol[a & ~TIE_AMB];
+        return (u < 0 || u >= n) ? -1 : u;
+    }
+}
+template <int PAR>
+__device__ __forceinline__ int tpar_tail(const DevGraph& g, const int32_t* __restrict__ P, int x) {
+    if constexpr (PAR == PAR_VERTEX) return P[x];
+    else return g.inCol[P[x] & ~TIE_AMB];
+}
+
+template <int PAR>
 __global__ __launch_bounds__(TPAR_THREADS) void k_tree_load_parents(DevGraph g0, DevGraph aux0, DevTable tab0,
                                                                     TreeParentsArgs p) {
     __shared__ unsigned long long expect, tot[3], total, claimedSrc, issuedWg, claimedWg;
@@ -983,13 +1015,8 @@ __global__ __launch_bounds__(TPAR_THREADS) void k_tree_load_parents(DevGraph g0,
                                                           __HIP_MEMORY_SCOPE_WORKGROUP))
                     break;                       // claimed already: the rest of the way is too
                 if (x == src) break;
-                const int a = P[x];
-                if (a < 0 || (a & ~TIE_AMB) >= p.nInArcs || (target && p.corrupt == 2)) {
-                    fail = 1;
-                    break;
-                }
-                const int u = g.inCol[a & ~TIE_AMB];
-                if (u < 0 || u >= n) {
+                const int u = tpar_parent<PAR>(g, P, x, n, p.nInArcs);
+                if (u < 0 || (target && p.corrupt == 2)) {
                     fail = 1;
                     break;
                 }
@@ -1013,7 +1040,7 @@ __global__ __launch_bounds__(TPAR_THREADS) void k_tree_load_parents(DevGraph g0,
                 // (the entry's sum is final: every child added before it counted down)
                 const unsigned long long s = __hip_atomic_fetch_add(&sum[e], 0ull, __ATOMIC_RELAXED,
                                                                     __HIP_MEMORY_SCOPE_WORKGROUP);
-                const int u = g.inCol[P[e] & ~TIE_AMB];
+                const int u = tpar_tail<PAR>(g, P, e);
                 wg_add(&sum[u], s);
                 if (__hip_atomic_fetch_sub(&pend[u], 1, __ATOMIC_ACQ_REL, __HIP_MEMORY_SCOPE_WORKGROUP) != 1) break;
                 e = u;
@@ -1057,15 +1084,25 @@ __global__ __launch_bounds__(TPAR_THREADS) void k_tree_load_parents(DevGraph g0,
             if (!ld_wg(&mark[v])) continue;
             const unsigned long long s = ld_wg(&sum[v]);
             if (s == 0) continue;
-            const int a = v == src ? -1 : (P[v] & ~TIE_AMB);
             const int ov = g.oldId ? g.oldId[v] : v;
             dev_add(acc + p.nArcs + ov, s);
             ++issued;
-            if (a < 0) continue;
-            const int u = g.inCol[a];
+            if (v == src) continue;
+            const int u = tpar_tail<PAR>(g, P, v);
             const int ou = g.oldId ? g.oldId[u] : u;
             int arc = -1;
-            if (ou != ov && find_arc(aux, ou, ov, &arc)) {
+            bool found = false;
+            if constexpr (PAR == PAR_VERTEX) {
+                // a full out-row (every other vertex, ascending) holds the arc at a
+                // computed place, as k_dense_tie_export finds it: one gather to
+                // confirm it instead of the search's dependent ones
+                const int a0 = aux.rowPtr[ou], a1 = aux.rowPtr[ou + 1];
+                if (a1 - a0 == aux.n - 1 && ou != ov) {
+                    arc = a0 + (ov < ou ? ov : ov - 1);
+                    found = aux.col[arc] == ov;
+                }
+            }
+            if (found || (ou != ov && find_arc(aux, ou, ov, &arc))) {
                 dev_add(acc + arc, s);
                 ++issued;
             } else {                             // (never: a parent arc is an arc of the graph)
@@ -1084,8 +1121,12 @@ __global__ __launch_bounds__(TPAR_THREADS) void k_tree_load_parents(DevGraph g0,
 void launch_tree_load_parents(const DevGraph& g, const DevGraph& gAux, const DevTable& tab,
                               const TreeParentsArgs& a, int grid, void* stream) {
     if (a.nSrc <= 0 || grid <= 0) return;
-    hipLaunchKernelGGL(k_tree_load_parents, dim3((unsigned)(grid < a.nSrc ? grid : a.nSrc)), dim3(TPAR_THREADS), 0,
-                       reinterpret_cast<hipStream_t>(stream), g, gAux, tab, a);
+    const dim3 wgs((unsigned)(grid < a.nSrc ? grid : a.nSrc));
+    hipStream_t st = reinterpret_cast<hipStream_t>(stream);
+    if (a.vertexIds)
+        hipLaunchKernelGGL(k_tree_load_parents<PAR_VERTEX>, wgs, dim3(TPAR_THREADS), 0, st, g, gAux, tab, a);
+    else
+        hipLaunchKernelGGL(k_tree_load_parents<PAR_INARC>, wgs, dim3(TPAR_THREADS), 0, st, g, gAux, tab, a);
 }
 
 void launch_paths_size(const DevGraph& gAux, const DevTable& tab, const PathsSizeArgs& a, void* stream) {

@@ -497,10 +497,10 @@ int launch_dense_rows(const DevGraph& g, const DevTable& tab, const double* W, c
                       double* flopsOut, DenseStage stage) {
     hipStream_t st = reinterpret_cast<hipStream_t>(stream);
     const int64_t ldD = n;
-    const bool all = stage == DENSE_ALL;
+    const bool pred = stage != DENSE_SWEEPS;     // DENSE_ALL, DENSE_PRED: the predecessor pass runs
     hipLaunchKernelGGL(k_dense_init, dim3((unsigned)((n + 255) / 256), nRows), dim3(256), 0, st, g,
                        W, D, dRows, n, ldD, rowActive);
-    if (all) (void)hipMemsetAsync(rowAmb, 0, nRows, st);
+    if (pred) (void)hipMemsetAsync(rowAmb, 0, nRows, st);
     const unsigned gx = (unsigned)((n + TCOL - 1) / TCOL);
     const dim3 gridS((unsigned)((nRows + 16 * MI_SWEEP - 1) / (16 * MI_SWEEP)), gx);
     const int miP = tu.densePredMi >= 3 && tu.densePredMi <= 6 && tu.densePredMi != 5 ? tu.densePredMi
@@ -541,7 +541,7 @@ int launch_dense_rows(const DevGraph& g, const DevTable& tab, const double* W, c
         if (!any || sweeps > n) break;
     }
     if (sweepsOut) *sweepsOut = sweeps + 1;
-    if (!all) {          // the converged rows stay in D: no predecessor pass, no row writer
+    if (!pred) {         // the converged rows stay in D: no predecessor pass, no row writer
         if (flopsOut) *flopsOut = 2.0 * visits * (16.0 * MI_SWEEP) * TCOL * KB;
         return 0;
     }
@@ -557,8 +557,9 @@ int launch_dense_rows(const DevGraph& g, const DevTable& tab, const double* W, c
     else
         hipLaunchKernelGGL((k_minplus<MP_PRED, MI_PRED>), gridP, dim3(256), 0, st, g, W, D, n, ldD,
                            nRows, rowActive, rowChanged, dAny, dRows, P, rowAmb, chunkEpoch, 0);
-    hipLaunchKernelGGL(k_dense_write, dim3((unsigned)((g.T + 255) / 256), nRows), dim3(256), 0, st,
-                       g, tab, D, P, Rl, n, ldD, dRows, rowAmb);
+    if (stage == DENSE_ALL)      // (DENSE_PRED: D, P and rowAmb stay for the caller, no row is written)
+        hipLaunchKernelGGL(k_dense_write, dim3((unsigned)((g.T + 255) / 256), nRows), dim3(256), 0, st,
+                           g, tab, D, P, Rl, n, ldD, dRows, rowAmb);
     // flops: 2 per relaxation; a visit = TR rows x 128 targets x KB u (tile
     // nominal size); the pred pass is one full n x n pass per row
     if (flopsOut)

@@ -490,9 +490,11 @@ void launch_tree_load(const DevGraph& g, const DevGraph& gAux, const DevTable& t
                       const TreeLoadArgs& a, int grid, void* stream);
 // ... its tree kernel over explicit parent arrays (pe_aux.hip, k_tree_load_parents;
 // shd_pe_table_load_set_parent_tier): listed source i has table position pos[i]
-// and its parents (IN-arc words as k_paths_walk reads them) at parents +
-// slot[i] * stride -- the scratch slots k_sparse_rows' row-less form leaves, or
-// the tie slots after the early-stop emulation.
+// and its parents at parents + slot[i] * stride: IN-arc words as k_paths_walk
+// reads them -- the scratch slots k_sparse_rows' row-less form leaves, or the
+// tie slots after the early-stop emulation -- or, with vertexIds, the parent's
+// vertex id in g's ids: the rows of P the dense predecessor pass leaves
+// (launch_dense_rows, DENSE_PRED).
 struct TreeParentsArgs {
     const int32_t* pos;         // [nSrc] table positions
     const int32_t* slot;        // [nSrc] parent array of each source; null: source i has slot i
@@ -501,7 +503,9 @@ struct TreeParentsArgs {
     const int32_t* parents;
     int64_t stride;
     int32_t nInArcs;
-    const uint8_t* skip;        // [nSrc] or null: non-zero = the source does not run (the sparse rowAmbig)
+    int32_t vertexIds;          // non-zero: parents holds vertex ids, not in-arc words
+    const uint8_t* skip;        // [nSrc] or null: non-zero = the source does not run (the sparse rowAmbig,
+                                // the dense rowAmb)
     const double* thr;          // by slot, or null: NaN = the slot failed the emulation's check, handed on
     const uint64_t* weight;     // [nSrc][T]; null: 1
     uint64_t* sum;              // [grid][n] scratch slots: subtree sum ...
@@ -568,10 +572,13 @@ struct PathsLoadArgs {
 };
 void launch_paths_load(const DevGraph& gAux, const PathsLoadArgs& a, void* stream);
 // dense path (pe_dense.hip)
-// launch_dense_rows' stages: everything (sweeps, predecessor pass, row writer),
-// or the sweeps to convergence alone, which leave the distance rows in D and
-// touch neither P, rowAmb nor the table (shd_pe_get_paths' row tier)
-enum DenseStage { DENSE_ALL = 0, DENSE_SWEEPS = 1 };
+// launch_dense_rows' stages: everything (sweeps, predecessor pass, row writer);
+// the sweeps to convergence alone, which leave the distance rows in D and
+// touch neither P, rowAmb nor the table (shd_pe_get_paths' row tier); or the
+// sweeps and the predecessor pass without the row writer, which leave D, the
+// parent rows in P and the tie bytes in rowAmb for the caller and do not touch
+// the table (shd_pe_table_load's parent tier)
+enum DenseStage { DENSE_ALL = 0, DENSE_SWEEPS = 1, DENSE_PRED = 2 };
 void launch_dense_build(const DevGraph& g, double* W, double* Rl, int64_t n, int64_t nArcs,
                         void* stream);
 int launch_dense_rows(const DevGraph& g, const DevTable& tab, const double* W, const double* Rl,

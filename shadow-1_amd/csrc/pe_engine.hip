@@ -2915,10 +2915,12 @@ static int tload_direct(ShdPe* pe, TableLoad& c) {
 }
 
 // ---- parent tier (shd_pe_table_load_set_parent_tier) ----------------
-// Where it applies, when switched on: the per-row sparse kernel's engines, and
-// the tie rows with a slot of the batched engines' tree tier.
+// Where it applies, when switched on: the per-row sparse kernel's engines, the
+// tie rows with a slot of the batched engines' tree tier, and the dense mode
+// (over the predecessor pass's parent rows, §8i).
 static bool tload_parents_apply(const ShdPe* pe) {
-    return pe->tloadParentTier && pe->tu.pathsFast && pe->mode == 1 && pe->opt.forceMode != 3 && !pe->hg.latFold;
+    return pe->tloadParentTier && pe->tu.pathsFast && (pe->mode == 1 || pe->mode == 3) && pe->opt.forceMode != 3 &&
+           !pe->hg.latFold;
 }
 
 namespace {
@@ -2939,6 +2941,21 @@ struct ParentTier {
     std::vector<int32_t> who;
     std::vector<uint8_t> tie;
 };
+
+// The parent arrays of one launch: the sparse kernel's scratch slots, the tie
+// slots with their thresholds (both in-arc words), or rows of the dense
+// predecessor pass's P from row `first` on (vertex ids).
+struct ParentRows {
+    const int32_t* parents;
+    int64_t stride;
+    const double* thr;
+    bool vertexIds, tie;
+};
+ParentRows scratch_parents(const Shard* sh) { return {sh->sc.pred, sh->sc.stride, nullptr, false, false}; }
+ParentRows tie_parents(const Shard* sh) { return {sh->tie.P, sh->tie.n, sh->tie.thr, false, true}; }
+ParentRows dense_parents(const Shard* sh, int64_t n, int64_t first) {
+    return {sh->dP + first * n, n, nullptr, true, false};
+}
 
 }  // namespace
 
@@ -2981,10 +2998,12 @@ static int ptier_init(ShdPe* pe, Shard* sh, const TableLoad& c, size_t cap, size
 }
 
 // One launch over the nSrc <= cap sources at hostPos (dPos: the same on the
-// device), their weight rows staged first.  tie: over the tie slots dSlot with
-// their thresholds; else over the scratch slots 0 .. nSrc - 1, less dSkip.
+// device), their weight rows staged first.  Over the tie slots dSlot with
+// their thresholds; else over the arrays 0 .. nSrc - 1 of pr, less dSkip.
 static int ptier_launch(ShdPe* pe, Shard* sh, const TableLoad& c, ParentTier& pt, const int32_t* hostPos,
-                        int32_t nSrc, const int32_t* dPos, const int32_t* dSlot, const uint8_t* dSkip, bool tie) {
+                        int32_t nSrc, const int32_t* dPos, const int32_t* dSlot, const uint8_t* dSkip,
+                        const ParentRows& pr) {
+    const bool tie = pr.tie;
     const size_t T = (size_t)c.T;
     if (nSrc <= 0) return SHD_PE_OK;
     if ((size_t)nSrc > pt.cap || pt.who.size() + (size_t)nSrc > pt.handedCap) return SHD_PE_EINVAL;
@@ -2998,9 +3017,8 @@ static int ptier_launch(ShdPe* pe, Shard* sh, const TableLoad& c, ParentTier& pt
     int32_t corruptAt = -1;              // the call's first source (the debug switches' target)
     for (int32_t i = 0; i < nSrc && pe->tu.tloadCorrupt; ++i)
         if (hostPos[i] == c.in->start) corruptAt = i;
-    const TreeParentsArgs a{dPos, dSlot, nSrc, pt.dAttDev, tie ? sh->tie.P : sh->sc.pred,
-                            tie ? sh->tie.n : sh->sc.stride, (int32_t)pe->hg.nArcs(), dSkip,
-                            tie ? sh->tie.thr : nullptr, pt.dW, pt.dSum, pt.dPend, pt.dMark,
+    const TreeParentsArgs a{dPos, dSlot, nSrc, pt.dAttDev, pr.parents, pr.stride, (int32_t)pe->hg.nArcs(),
+                            pr.vertexIds ? 1 : 0, dSkip, pr.thr, pt.dW, pt.dSum, pt.dPend, pt.dMark,
                             pe->hg.nArcs(), pt.dAcc, pt.dHanded + pt.who.size(), pt.dOut + (tie ? 8 : 0),
                             corruptAt >= 0 ? pe->tu.tloadCorrupt : 0, corruptAt};
     launch_tree_load_parents(sh->dg, sh->dgAux, sh->tab, a, pt.grid, sh->stream);
@@ -3020,7 +3038,7 @@ static int ptier_tie_rows(ShdPe* pe, Shard* sh, const TableLoad& c, ParentTier& 
     HIPCHK(hipMemcpyAsync(sh->dSlots, slots.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
     scan_tie_slots(pe, sh, slots, nTie);
     if ((rc = paths_emulate(pe, sh, sh->dRows, nTie, sh->exactGrid, sh->dSlots))) return rc;
-    return ptier_launch(pe, sh, c, pt, rows.data(), nTie, sh->dRows, sh->dSlots, nullptr, true);
+    return ptier_launch(pe, sh, c, pt, rows.data(), nTie, sh->dRows, sh->dSlots, nullptr, tie_parents(sh));
 }
 
 // Synchronises; the sums (where the accumulator is this tier's own), totals and
@@ -3087,7 +3105,8 @@ static int tload_parents_sparse(ShdPe* pe, size_t k, int32_t lo, int32_t hi, Tab
         launch_sparse_rows(sh->dg, sh->tab, sh->sc, dPos + u0, g, sh->dRowAmbig, sh->cfg, nullptr, sh->dTie,
                            sh->stream, true);
         HIPCHK(hipGetLastError());
-        if ((rc = ptier_launch(pe, sh, c, pt, pos.data() + u0, g, dPos + u0, nullptr, sh->dRowAmbig, false))) return rc;
+        if ((rc = ptier_launch(pe, sh, c, pt, pos.data() + u0, g, dPos + u0, nullptr, sh->dRowAmbig, scratch_parents(sh))))
+            return rc;
         HIPCHK(hipMemcpyAsync(amb.data(), sh->dRowAmbig, (size_t)g, hipMemcpyDeviceToHost, sh->stream));
         HIPCHK(hipStreamSynchronize(sh->stream));
         ties.emplace_back();
@@ -3118,6 +3137,107 @@ static int tload_parents_sparse(ShdPe* pe, size_t k, int32_t lo, int32_t hi, Tab
             ++nHanded;
         }
     if (pe->tloadInfo[8] + pe->tloadInfo[9] - before + nHanded + nFull != (int64_t)count) return SHD_PE_EHIP;
+    return SHD_PE_OK;
+}
+
+// Parent tier over the table positions [lo, hi) of a shard in the dense mode
+// (§8i): the positions in chunks of the dense batch, as relax_dense chunks
+// them.  Per chunk the sweeps and the predecessor pass without the row writer
+// (DENSE_PRED), then k_tree_load_parents over the chunk's rows of P (vertex
+// ids; the rows with a tie skipped by their rowAmb byte), launched in blocks of
+// sources whose weight rows stay within TLOAD_DIRECT_BYTES of staging.  The
+// chunk's tie rows, on an undirected graph with tie slots: exported while D / P
+// hold them, the relevance scan, k_exact_dense's early stop -- the table's own
+// dense exact stage without k_tie_write -- and the kernel over tie.P (in-arc
+// words).  Left to the request route (c.rest): a chunk's tie rows beyond the
+// slots, every tie row of a directed graph, and the sources handed on.
+static int tload_parents_dense(ShdPe* pe, size_t k, int32_t lo, int32_t hi, TableLoad& c) {
+    Shard* sh = pe->shards[k].get();
+    int rc;
+    HIPCHK(hipSetDevice(sh->device));
+    if ((rc = ensure_table(pe, sh)) || (rc = ensure_dense(pe, sh)) || (rc = ensure_tie(pe, sh))) return rc;
+    const int32_t count = hi - lo, DR = sh->denseRows;
+    const int64_t n = pe->hg.n;
+    const int32_t slotCap = sh->dTie && !pe->hg.directed ? sh->tie.cap : 0;
+    const int32_t block = (int32_t)std::min<int64_t>(count, std::max<int64_t>(1, TLOAD_DIRECT_BYTES / (8 * c.T)));
+    if (slotCap > 0) {
+        if (!sh->dDenseIdx && (rc = dev_alloc(sh, &sh->dDenseIdx, (size_t)sh->rowsCap))) return rc;
+        if ((rc = ensure_xlist(sh))) return rc;
+    }
+    ParentTier pt;
+    int32_t* dPos = nullptr;
+    if ((rc = ptier_init(pe, sh, c, (size_t)block, 2 * (size_t)count, nullptr, nullptr, pt)) ||
+        (rc = pt.s.get(&dPos, (size_t)count)))
+        return rc;
+    std::vector<int32_t> pos((size_t)count), slots((size_t)slotCap);
+    for (int32_t p = lo; p < hi; ++p) pos[(size_t)(p - lo)] = p;
+    for (int32_t i = 0; i < slotCap; ++i) slots[(size_t)i] = i;
+    HIPCHK(hipMemcpyAsync(dPos, pos.data(), (size_t)count * 4, hipMemcpyHostToDevice, sh->stream));
+    if (slotCap > 0)
+        HIPCHK(hipMemcpyAsync(sh->dSlots, slots.data(), (size_t)slotCap * 4, hipMemcpyHostToDevice, sh->stream));
+    std::vector<uint8_t> amb;
+    std::vector<ExactWork> ties;                         // (what the copies read lives until the last synchronise)
+    ties.reserve((size_t)((count + DR - 1) / DR));
+    const ShdPeStats savedStats = sh->stats;
+    int64_t nRest = 0;
+    const int64_t before = pe->tloadInfo[8] + pe->tloadInfo[9];
+    HIPCHK(hipEventRecord(sh->ev0, sh->stream));
+    for (int32_t d0 = 0; d0 < count; d0 += DR) {
+        const int32_t dc = std::min(DR, count - d0);
+        if (launch_dense_rows(sh->dg, sh->tab, sh->dW, sh->dRl, sh->dD, sh->dP, sh->dRowA, sh->dRowB, sh->dRowAmbD,
+                              sh->dAny, sh->dChunkEpoch, dPos + d0, dc, n, pe->tu, sh->stream, nullptr, nullptr,
+                              DENSE_PRED))
+            return SHD_PE_EHIP;
+        HIPCHK(hipGetLastError());
+        amb.resize((size_t)dc);
+        HIPCHK(hipMemcpyAsync(amb.data(), sh->dRowAmbD, (size_t)dc, hipMemcpyDeviceToHost, sh->stream));
+        for (int32_t b0 = 0; b0 < dc; b0 += block)
+            if ((rc = ptier_launch(pe, sh, c, pt, pos.data() + d0 + b0, std::min(block, dc - b0), dPos + d0 + b0, nullptr,
+                                   sh->dRowAmbD + b0, dense_parents(sh, n, b0))))
+                return rc;
+        HIPCHK(hipStreamSynchronize(sh->stream));
+        ties.emplace_back();
+        ExactWork& tie = ties.back();                    // the chunk's tie rows with a slot
+        for (int32_t i = 0; i < dc; ++i) {
+            if (!amb[(size_t)i]) continue;
+            if ((int32_t)tie.rows.size() < slotCap) {
+                tie.rows.push_back(pos[(size_t)(d0 + i)]);
+                tie.denseIdx.push_back(i);
+            } else {
+                c.rest.push_back(pos[(size_t)(d0 + i)]);
+                ++nRest;
+            }
+        }
+        const int32_t nTie = (int32_t)tie.rows.size();
+        if (nTie == 0) continue;
+        sh->pathSrc = -1;                                // the emulation overwrites slot 0
+        HIPCHK(hipMemcpyAsync(sh->dRows, tie.rows.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipMemcpyAsync(sh->dDenseIdx, tie.denseIdx.data(), (size_t)nTie * 4, hipMemcpyHostToDevice, sh->stream));
+        HIPCHK(hipMemsetAsync(sh->tie.thr, 0, (size_t)nTie * 8, sh->stream));
+        launch_dense_tie_export(sh->dg, sh->dD, sh->dP, n, sh->dDenseIdx, sh->dRows, sh->tie, nTie, sh->stream);
+        scan_tie_slots(pe, sh, slots, nTie);
+        HIPCHK(hipMemsetAsync(sh->tie.count + 2, 0, 4, sh->stream));
+        launch_exact_dense(sh->dg, sh->tab, sh->sc, sh->dRows, nTie, sh->exactGrid, sh->exactHc, sh->dXList,
+                           sh->dSlots, sh->tie, sh->tie.count + 2, sh->stream);
+        HIPCHK(hipGetLastError());
+        for (int32_t b0 = 0; b0 < nTie; b0 += block)
+            if ((rc = ptier_launch(pe, sh, c, pt, tie.rows.data() + b0, std::min(block, nTie - b0), sh->dRows + b0,
+                                   sh->dSlots + b0, nullptr, tie_parents(sh))))
+                return rc;
+    }
+    HIPCHK(hipEventRecord(sh->ev1, sh->stream));
+    std::vector<uint8_t> handed;
+    rc = ptier_finish(pe, sh, c, pt, handed);
+    sh->stats = savedStats;
+    if (rc) return rc;
+    c.ms += elapsed(sh->ev0, sh->ev1);
+    int64_t nHanded = 0;
+    for (size_t e = 0; e < handed.size(); ++e)
+        if (handed[e]) {
+            c.rest.push_back(pt.who[e]);
+            ++nHanded;
+        }
+    if (pe->tloadInfo[8] + pe->tloadInfo[9] - before + nHanded + nRest != (int64_t)count) return SHD_PE_EHIP;
     return SHD_PE_OK;
 }
 
@@ -3328,7 +3448,8 @@ extern "C" int shd_pe_table_load(ShdPe* pe, const ShdPeTableLoadIn* in, const Sh
             const Shard* sh = pe->shards[k].get();
             const int32_t a = std::max(lo, sh->rowStart), b = std::min(hi, sh->rowStart + sh->rowCount);
             if (a >= b) continue;
-            if ((rc = tload_parents_sparse(pe, k, a, b, c))) return rc;
+            if ((rc = pe->mode == 3 ? tload_parents_dense(pe, k, a, b, c) : tload_parents_sparse(pe, k, a, b, c)))
+                return rc;
             std::fill(seen.begin() + (a - lo), seen.begin() + (b - lo), (uint8_t)1);
         }
         for (int32_t p = lo; p < hi; ++p)

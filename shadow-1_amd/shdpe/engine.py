@@ -748,8 +748,9 @@ class Engine:
 
     def set_table_load_parent_tier(self, on: bool = True):
         """shd_pe_table_load_set_parent_tier: let table_load serve the per-row sparse
-        mode, and the tie rows with a slot of the batched mode, from explicit
-        parent arrays (off by default)."""
+        mode, the tie rows with a slot of the batched mode and the dense mode (from
+        the predecessor pass's parent rows; an undirected graph's tie rows over the
+        dense tie slots) from explicit parent arrays (off by default)."""
         self._chk(self._lib.shd_pe_table_load_set_parent_tier(self.h, 1 if on else 0),
                   "shd_pe_table_load_set_parent_tier")
 
@@ -758,7 +759,10 @@ class Engine:
         in exactly one of tree / direct / route / parents / tie), of the route's
         those a tier handed on, tree entries claimed, device ms, the tree tier's
         rounds, the entries the parent tier's sources claimed and (debug counters
-        only, else 0) the global adds the commits issued.  (A library loaded
+        only, else 0) the global adds the commits issued.  In the dense mode
+        "parents" counts the sources summed over the predecessor pass's parent rows
+        and "tie" those over the dense tie slots; there are no other keys for it.
+        (A library loaded
         through SHDPE_LIB from before the parent tier fills the first 8.)"""
         info = np.zeros(12, np.int64)
         self._chk(self._lib.shd_pe_table_load_info(self.h, _p(info), 12), "shd_pe_table_load_info")

@@ -22,6 +22,19 @@ the per-row sparse kernel) or covers in part (c4q: the tie rows with a slot).
 Leg b stays the request route alone, and one leg joins the protocol: d_off, leg
 d with the tier off.
 
+--config c3b (the dense mode: 20,000 vertices one edge short of complete, all
+attached; SHDPE_C3_N overrides n, and the n used is written into the file) runs
+its own protocol with the parent tier on, into profiles/dense_tier_c3bshape.json:
+
+  a         rows [0, 256) with a seeded random weight matrix, parent tier on
+  b_trial   16 of those rows with the tier off, one timed call: leg b's limit is
+            sized from it, linearly in the sources
+  b         leg a's rows with the tier off: every source by the request route.
+            Where the trial says that takes more than 20 minutes, legs b and
+            a_16 run on 16 rows instead and the file says so
+  d         all rows with weight == NULL, beside compute_all of the same process
+  d_q       the same on c3bq (quantized latencies: tie rows over the dense slots)
+
 (a), (b) and (c) must give identical sums (sha256 over arc, vertex and totals,
 kept in the file); (a) is expected below (b) and (c) by more than the sum of
 their min-max spreads, and the file says whether it is (`*_by_more_than_spreads`,
@@ -103,7 +116,7 @@ def step_table(args, what, flags=1):
     rows = _rows(args, eng)
     w = _weights(rows, eng.T)
     out, wall, dev = _timed(lambda: eng.table_load(0, rows, w), eng.table_load_info, what, args.repeats)
-    res = _result(eng, out, wall, dev, {"sources": rows, "requests": rows * eng.T})
+    res = _result(eng, out, wall, dev, {"sources": rows, "requests": rows * eng.T, "vertices": eng.top.n})
     eng.close()
     return res
 
@@ -126,7 +139,8 @@ def step_d(args):
     E, eng = _engine(args, flags=1)
     st = eng.stats()
     out, wall, dev = _timed(lambda: eng.table_load(), eng.table_load_info, "d", args.repeats)
-    res = _result(eng, out, wall, dev, {"sources": eng.T, "requests": eng.T * eng.T, "compute_all_ms": st["msTotal"]})
+    res = _result(eng, out, wall, dev, {"sources": eng.T, "requests": eng.T * eng.T, "compute_all_ms": st["msTotal"],
+                                        "vertices": eng.top.n, "rows_exact": st["rowsExact"]})
     eng.close()
     return res
 
@@ -185,7 +199,72 @@ STEPS = {
 }
 
 
+DENSE_CONFIGS = ("c3b", "c3bq")
+DENSE_SOURCES, DENSE_TRIAL, DENSE_B_LIMIT = 256, 16, 1200
+
+
+def _child(args, step, env, key=None, **over):
+    """One step as a child under its own `timeout` -> its result, under `key`
+    where given.  over: the child's config / sources / repeats / timeout /
+    parent_tier where they differ from the protocol's."""
+    a = {**vars(args), **over}
+    part = f"{args.out}.{step}.part"
+    cmd = ["timeout", "-k", "10", str(a["step_timeout"]), sys.executable, os.path.abspath(__file__),
+           "--config", a["config"], "--step", step, "--out", part, "--repeats", str(a["repeats"]),
+           "--sources", str(a["sources"]), "--block", str(a["block"])]
+    if a["parent_tier"]:
+        cmd.append("--parent-tier")
+    t0 = time.perf_counter()
+    rc = subprocess.run(cmd, env={**os.environ, **env}).returncode
+    if rc:
+        raise SystemExit(f"step {step}: exit status {rc}; no further step was started")
+    with open(part) as f:
+        res = json.load(f)
+    os.remove(part)
+    if key:
+        (leg,) = res.values()
+        leg["child_wall_s"] = time.perf_counter() - t0
+        res = {key: leg}
+    return res
+
+
+def run_dense(args):
+    """The dense protocol (the docstring's --config c3b part)."""
+    legs = args.legs.split(",") if args.legs else ["a", "b", "d", "d_q"]
+    res = {"config": args.config, "unit": "ms", "parent_tier": True}
+    rows = min(args.sources, DENSE_SOURCES)
+    if "a" in legs:
+        res.update(_child(args, "a", {}, sources=rows, parent_tier=True))
+    if "b" in legs:
+        res.update(_child(args, "b", {}, key="b_trial", sources=DENSE_TRIAL, repeats=1, parent_tier=False))
+        t = res["b_trial"]
+        per_call_s = t["wall_ms"]["median"] / 1e3 * rows / t["sources"]
+        setup_s = max(0.0, t["child_wall_s"] - 2 * t["wall_ms"]["median"] / 1e3)
+        need_s = setup_s + (1 + args.repeats) * per_call_s
+        res["b_extrapolated_s"] = need_s
+        if need_s > DENSE_B_LIMIT:
+            rows_b = DENSE_TRIAL
+            res["b_note"] = (f"the request route on {rows} sources extrapolates to {need_s:.0f} s, past "
+                             f"{DENSE_B_LIMIT} s: legs b and a_16 ran on {rows_b} sources, and a_below_b compares those")
+            res.update(_child(args, "a", {}, key="a_16", sources=rows_b, parent_tier=True))
+            need_s = setup_s + (1 + args.repeats) * t["wall_ms"]["median"] / 1e3
+        else:
+            rows_b = rows
+        limit = int(min(DENSE_B_LIMIT, 60 + 1.5 * need_s))
+        res["b_timeout_s"] = limit
+        res.update(_child(args, "b", {}, sources=rows_b, parent_tier=False, step_timeout=limit))
+    if "d" in legs:
+        res.update(_child(args, "d", {}, parent_tier=True))
+    if "d_q" in legs:
+        res.update(_child(args, "d", {}, key="d_q_all_rows_unit_weight", config="c3bq", parent_tier=True))
+    used = {leg["vertices"] for leg in res.values() if isinstance(leg, dict) and "vertices" in leg}
+    res["vertices"] = sorted(used)[0] if len(used) == 1 else sorted(used)
+    return res
+
+
 def run_steps(args):
+    if args.config in DENSE_CONFIGS:
+        return finish(args, run_dense(args))
     plan = [("a", {}), ("b", {"SHDPE_TLOAD_TREE": "0"}), ("c", {}), ("d", {})]
     if args.leg_e:
         plan.append(("e", {}))
@@ -197,18 +276,12 @@ def run_steps(args):
         plan = [(step, env) for step, env in plan if step in args.legs.split(",")]
     res = {"config": args.config, "unit": "ms", "parent_tier": bool(args.parent_tier)}
     for step, env in plan:
-        part = f"{args.out}.{step}.part"
-        cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__),
-               "--config", args.config, "--step", step, "--out", part, "--repeats", str(args.repeats),
-               "--sources", str(args.sources), "--block", str(args.block)]
-        if args.parent_tier and step not in ("b", "c", "d_off"):
-            cmd.append("--parent-tier")
-        rc = subprocess.run(cmd, env={**os.environ, **env}).returncode
-        if rc:
-            raise SystemExit(f"step {step}: exit status {rc}; no further step was started")
-        with open(part) as f:
-            res.update(json.load(f))
-        os.remove(part)
+        res.update(_child(args, step, env, parent_tier=args.parent_tier and step not in ("b", "c", "d_off")))
+    finish(args, res)
+
+
+def finish(args, res):
+    """The checks over the legs that ran, and the file."""
     spread = lambda r: r["device_ms"]["max"] - r["device_ms"]["min"]
     fast = lambda r: r["info"]["tree"] + r["info"]["parents"] + r["info"]["tie"]
 
@@ -228,13 +301,14 @@ def run_steps(args):
             o["device_ms"]["median"] - f["device_ms"]["median"] > spread(f) + spread(o))
         res[f"{name}_ratio_device"] = o["device_ms"]["median"] / f["device_ms"]["median"]
 
-    res["sums_equal_first_rows"] = same_sums(("a_tree", "b_route", "c_path_load"))
+    a_leg = "a_16" if "a_16" in res else "a_tree"     # (the dense protocol's leg b on fewer sources)
+    res["sums_equal_first_rows"] = same_sums((a_leg, "b_route", "c_path_load"))
     res["sums_equal_all_rows"] = same_sums(("d_all_rows_unit_weight", "d_parent_tier_off"))
     if "a_tree" in res and fast(res["a_tree"]) == 0:
         raise SystemExit(f"no fast tier served leg a: {res['a_tree']['info']}")
     if "b_route" in res and fast(res["b_route"]) != 0:
         raise SystemExit(f"the tier switches did not take in leg b: {res['b_route']['info']}")
-    below("a_tree", "b_route", "a_below_b")
+    below(a_leg, "b_route", "a_below_b")
     below("a_tree", "c_path_load", "a_below_c")
     below("d_all_rows_unit_weight", "d_parent_tier_off", "d_below_d_off")
     if "a_counters" in res:
@@ -263,7 +337,8 @@ def main():
     ap.add_argument("--out", default=None, help="default: profiles/table_load_<config>shape.json")
     args = ap.parse_args()
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", f"table_load_{args.config}shape.json")
+        name = "dense_tier_c3bshape.json" if args.config in DENSE_CONFIGS else f"table_load_{args.config}shape.json"
+        args.out = os.path.join(ROOT, "profiles", name)
     if args.step:
         res = STEPS[args.step](args)
         with open(args.out, "w") as f:
